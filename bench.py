@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py -- RBCD iterations/sec of the MI355X-native local solver + Q*X roofline.
 
-    python bench.py --gpus N --steps K --warmup W [--workload grid100k|sphere2500|grid:NXxNYxNZ]
+    python bench.py --gpus N --steps K --warmup W [--workload grid100k|sphere2500|grid:NXxNYxNZ] [--dump-outputs DIR]
 
 One "step" = one RBCD iteration from a fixed, settled iterate (identical full work every step; see main()):
 every agent runs QuadraticOptimizer::optimize once (RTR, 3 outer
@@ -34,11 +34,6 @@ import json
 import os
 import sys
 import time
-
-# Agents that share a GPU are solved concurrently, one HIP stream each; the ROCm runtime maps streams onto 4 hardware
-# queues by default, so more than 4 same-colour agents would queue behind each other.  Must be set before the runtime
-# initialises (i.e. before torch / the library are imported).
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")
 
 import numpy as np
 
@@ -83,6 +78,9 @@ def parse_args():
                          "per GPU.  With WORLD_SIZE = 1 (python -m torch.distributed.run --nproc-per-node 1 bench.py "
                          "--gpus 1 --dist) the exchanges are self send / recv through the 1-rank communicator: every line "
                          "of the multi-GPU branch executes on one device")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (every agent's iterate and its "
+                         "solver result) as DIR/<name>.npy, at most 64 MB in all; see dump_outputs()")
     return ap.parse_args()
 
 
@@ -574,6 +572,33 @@ def time_to_tolerance(workload, r, precond, tol=1e-2, max_calls=12, coarse_bits=
                 ms_incl_setup=(1e3 * el + setup_first) if setup_first is not None else 1e3 * el)
 
 
+DUMP_LIMIT_BYTES = 64 * 2 ** 20
+
+
+def dump_outputs(out_dir, agents, world):
+    """--dump-outputs: what the last timed step handed its caller, per agent a of this rank --
+    agent<a>_X.npy: the iterate X after the solve, tiles [n_a, d+1, r] in the caller's pose order (float64);
+    agent<a>_result.npy: [fInit, gradNormInit, fOpt, gradNormOpt, tcg_iterations, rtr_iterations, rtr_accepted] (float64).
+    The ranks share DUMP_LIMIT_BYTES; where the iterates exceed their share, each agent's file holds a fixed sample of its
+    poses (seeded, sorted) and agent<a>_X_poses.npy their indices (float64), so that two runs dump the same rows."""
+    os.makedirs(out_dir, exist_ok=True)
+    Xs = {a: ag.iterate_in_caller_order().cpu().numpy() for a, ag in agents.items()}
+    budget = DUMP_LIMIT_BYTES // max(world, 1) - 4096 * len(agents)  # (the result vectors and .npy headers)
+    total = sum(X.nbytes for X in Xs.values())
+    sampled = total + 8 * sum(len(X) for X in Xs.values())  # (a sampled pose also costs its index)
+    for a, X in sorted(Xs.items()):
+        if total > budget:
+            keep = max(1, int(len(X) * budget / sampled))
+            poses = np.sort(np.random.default_rng(1000 + a).choice(len(X), keep, replace=False))
+            np.save(os.path.join(out_dir, "agent%d_X_poses.npy" % a), poses.astype(np.float64))
+            X = X[poses]
+        np.save(os.path.join(out_dir, "agent%d_X.npy" % a), np.ascontiguousarray(X, dtype=np.float64))
+        res = agents[a].last_result
+        vals = ([res.fInit, res.gradNormInit, res.fOpt, res.gradNormOpt, res.tcg_iterations, res.rtr_iterations,
+                 res.rtr_accepted] if res is not None else [np.nan] * 7)  # (an agent the step did not solve)
+        np.save(os.path.join(out_dir, "agent%d_result.npy" % a), np.array(vals, dtype=np.float64))
+
+
 LINE_LIMIT = 6144  # bytes: the driver's record keeps the last 8 KB of stdout
 
 
@@ -869,6 +894,8 @@ def main():
         elapsed = float(t.item())
     exchange_ms = sum(e0.elapsed_time(e1) for e0, e1 in ex_events)
     cluster.exchange = _exchange
+    if args.dump_outputs:  # (before anything below touches the agents' state)
+        dump_outputs(args.dump_outputs, agents, world)
     # (what the timed steps' cycles streamed: asked NOW -- the probes below set the hierarchy up again)
     ops_state = agent.problem.multilevelOperatorBits()
     ops_active = bool(ops_state["active"])

@@ -1107,18 +1107,16 @@ static int run_many(int count, const dpgo_problem_t* handles, void* after_stream
     for (int q = 0; q < k; ++q)
       if (handles[q] == handles[k]) return fail(DPGO_ERR_INVALID, "a handle appears twice");
   }
-  {  // ROCm maps HIP streams onto GPU_MAX_HW_QUEUES hardware queues (default 4): more concurrently solved handles than
-     // that still complete, but queue behind each other -- say so once instead of silently serialising
+  {  // ROCm maps a process's HIP streams onto 4 hardware queues by default: more concurrently solved handles than that
+     // still complete, but queue behind each other -- say so once instead of silently serialising
     static std::atomic<bool> warned{false};
-    const char* e = std::getenv("GPU_MAX_HW_QUEUES");
-    const int queues = (e && std::atoi(e) > 0) ? std::atoi(e) : 4;
+    const int queues = 4;
     if (count > queues && !warned.exchange(true)) {
       g_warnings.fetch_add(1);
       std::fprintf(stderr,
-                   "dpgo_hip: warning: %d handles are solved concurrently but GPU_MAX_HW_QUEUES is %d: their streams share %d "
-                   "hardware queues and partly serialise; set GPU_MAX_HW_QUEUES >= %d in the environment before the HIP runtime "
-                   "initialises (bench.py does)\n",
-                   count, queues, queues, count);
+                   "dpgo_hip: warning: %d handles are solved concurrently but the HIP runtime maps their streams onto %d "
+                   "hardware queues: they partly serialise\n",
+                   count, queues);
     }
   }
   std::vector<hipStream_t> prev(count);

@@ -355,7 +355,8 @@ int dpgo_optimize(dpgo_problem_t h, const dpgo_ropt_params* params, const double
 int dpgo_optimize_device(dpgo_problem_t h, const dpgo_ropt_params* params, double* X_dev,
                          dpgo_ropt_result* result);
 /* Number of warnings the library has printed to stderr so far (each kind once per process): e.g. more concurrently solved
- * handles (dpgo_optimize_device_many, dpgo_problem_eval_terms_device_many) than GPU_MAX_HW_QUEUES hardware queues. */
+ * handles (dpgo_optimize_device_many, dpgo_problem_eval_terms_device_many) than the 4 hardware queues the HIP runtime gives a
+ * process by default. */
 int dpgo_warning_count(void);
 /* The same solve in two halves, for callers that enqueue a whole sweep without waiting (RBCDCluster.sweep when a process
  * hosts one agent per colour: colour c's solve, colour c+1's pack + exchange and its solve are all stream-ordered; the

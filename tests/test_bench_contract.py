@@ -4,6 +4,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 from conftest import ROOT
@@ -71,13 +72,55 @@ def test_entry_points_exist():
     assert callable(g.build) and callable(g.smoke)
 
 
+def test_dump_outputs_writes_the_agents_results_within_the_size_limit(tmp_path, monkeypatch):
+    """bench.dump_outputs (--dump-outputs DIR): per agent its iterate (float64 tiles in the caller's pose order) and its
+    solver result; beyond the size limit a seeded, sorted sample of poses with their indices, the same rows every run."""
+    import types
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+
+    class Agent:
+        def __init__(self, n, seed):
+            self.X = torch.tensor(np.random.default_rng(seed).standard_normal((n, 4, 5)))
+            self.last_result = types.SimpleNamespace(fInit=4.0, gradNormInit=3.0, fOpt=2.0, gradNormOpt=1.0, tcg_iterations=7,
+                                                     rtr_iterations=3, rtr_accepted=2)
+
+        def iterate_in_caller_order(self):
+            return self.X
+
+    agents = {0: Agent(3000, 0), 3: Agent(1000, 1)}
+    bench.dump_outputs(str(tmp_path / "all"), agents, 1)
+    for a, ag in agents.items():
+        X = np.load(str(tmp_path / "all" / ("agent%d_X.npy" % a)))
+        assert X.dtype == np.float64 and np.array_equal(X, ag.X.numpy())
+        assert np.load(str(tmp_path / "all" / ("agent%d_result.npy" % a))).tolist() == [4.0, 3.0, 2.0, 1.0, 7.0, 3.0, 2.0]
+    assert sorted(os.listdir(str(tmp_path / "all"))) == ["agent0_X.npy", "agent0_result.npy", "agent3_X.npy",
+                                                        "agent3_result.npy"]
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 256 * 1024)  # (the iterates are 640 KB)
+    for run in ("s1", "s2"):
+        bench.dump_outputs(str(tmp_path / run), agents, 1)
+        assert sum(f.stat().st_size for f in (tmp_path / run).iterdir()) <= 256 * 1024
+    for a, ag in agents.items():
+        poses = np.load(str(tmp_path / "s1" / ("agent%d_X_poses.npy" % a)))
+        assert poses.dtype == np.float64 and len(poses) > 0 and np.all(np.diff(poses) > 0)
+        X = np.load(str(tmp_path / "s1" / ("agent%d_X.npy" % a)))
+        assert np.array_equal(X, ag.X.numpy()[poses.astype(np.int64)])
+        assert np.array_equal(X, np.load(str(tmp_path / "s2" / ("agent%d_X.npy" % a))))
+
+
 @pytest.mark.gpu
-def test_bench_prints_one_valid_json_line():
+def test_bench_prints_one_valid_json_line(tmp_path):
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "grid:12x10x6", "--steps", "2",
-                        "--warmup", "1", "--settle", "2", "--cpu-budget-s", "3", "--spmm-reps", "20"],
+                        "--warmup", "1", "--settle", "2", "--cpu-budget-s", "3", "--spmm-reps", "20",
+                        "--dump-outputs", str(tmp_path)],
                        capture_output=True, text=True, cwd=ROOT, timeout=600)
     assert p.returncode == 0, p.stderr[-2000:]
     line, j = records(p.stdout)
+    # --dump-outputs: the one agent's iterate after the last timed step (720 poses, d = 3, r = 5) and its solver result
+    X, res = np.load(str(tmp_path / "agent0_X.npy")), np.load(str(tmp_path / "agent0_result.npy"))
+    assert X.dtype == np.float64 and X.shape == (720, 4, 5) and np.all(np.isfinite(X))
+    assert res.shape == (7,) and res[2] <= res[0] and res[4] > 0
     assert os.path.exists(os.path.join(ROOT, "bench_detail.json"))
     # ---- the driver's line: headline keys, roofline of the timed kernel, the reference-configuration pair
     assert line["metric"] == "rbcd_iterations_per_sec" and line["n_gpus"] == 1 and line["dtype"] == "f64"

@@ -1479,10 +1479,9 @@ def test_inactive_neighbour_in_robust_mode_keeps_the_device_weights(oracle):
 
 
 def test_more_concurrent_handles_than_hardware_queues_warn_once_and_complete():
-    """ROCm maps HIP streams onto GPU_MAX_HW_QUEUES hardware queues (4 by default; bench.py raises it to 16 before the runtime
-    starts).  A caller that solves 8 handles concurrently WITHOUT the variable is not refused and not silently serialised:
-    the solves complete with the results of one-at-a-time solves and the library says so once on stderr
-    (dpgo_warning_count)."""
+    """ROCm maps a process's HIP streams onto 4 hardware queues by default.  A caller that solves 8 handles concurrently is
+    not refused and not silently serialised: the solves complete with the results of one-at-a-time solves and the library
+    says so once on stderr (dpgo_warning_count)."""
     code = r"""
 import os, sys
 sys.path.insert(0, %r)
@@ -1510,11 +1509,11 @@ for rep in range(2):
 assert L.load().dpgo_warning_count() == 1
 print("QUEUES_OK")
 """ % (ROOT_DIR, ROOT_DIR, ROOT_DIR)
-    env = {k: v for k, v in os.environ.items() if k != "GPU_MAX_HW_QUEUES"}
+    env = dict(os.environ)
     env["PYTHONPATH"] = os.path.dirname(os.path.abspath(__file__)) + os.pathsep + env.get("PYTHONPATH", "")
     p = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=600)
     assert p.returncode == 0 and "QUEUES_OK" in p.stdout, (p.stdout[-500:], p.stderr[-2000:])
-    assert p.stderr.count("GPU_MAX_HW_QUEUES is 4") == 1, p.stderr[-2000:]
+    assert p.stderr.count("maps their streams onto 4 hardware queues") == 1, p.stderr[-2000:]
 
 
 def test_concurrent_update_with_different_parameters_solves_each_with_its_own(oracle):
@@ -2489,14 +2488,20 @@ def test_multilevel_on_random_graphs_with_broken_chains(oracle, d, r, n, hub_edg
     rng = np.random.default_rng(3)
     X = oracle.polar_project(oracle.lift(T, r) + 0.1 * rng.standard_normal((n, d + 1, r)), d)
     V = oracle.tangent_project(X, rng.standard_normal(X.shape), d)
+    # the oracle's BLAS on one thread: how a threaded BLAS splits the coarse level's dense products depends on the host's
+    # thread count, and on these ill-conditioned graphs that round-off alone moves the oracle's tCG count by one
+    from threadpoolctl import threadpool_limits
     Zd = matrix_to_tiles(prob.PreConditioner(tiles_to_matrix(X), tiles_to_matrix(V), precond="multilevel"), d)
-    assert np.isfinite(Zd).all() and relerr(Zd, op.precondition(X, V)) < 1e-9
-    assert prob.multilevelInfo()["ks"] == op.amg_setup()["ks"]
+    with threadpool_limits(1):
+        Zo, ks = op.precondition(X, V), op.amg_setup()["ks"]
+    assert np.isfinite(Zd).all() and relerr(Zd, Zo) < 1e-9
+    assert prob.multilevelInfo()["ks"] == ks
     go = dpgo_amd.QuadraticOptimizer(prob, dpgo_amd.ROptParameters(precond="multilevel"))
     Xg = matrix_to_tiles(go.optimize(tiles_to_matrix(X)), d)
     rg = go.getOptResult()
     oo = oracle.QuadraticOptimizer(op, oracle.ROptParameters(), hess_recurrence=True)
-    oo.optimize(X)
+    with threadpool_limits(1):
+        oo.optimize(X)
     assert rg.success and np.isfinite(Xg).all() and rg.fOpt < rg.fInit
     assert rg.rtr_iterations == oo.result.outer_iters and abs(rg.tcg_iterations - oo.result.tcg_iters) <= 1
     # same counts: the same path to round-off.  One tCG step more or less before the trust-region boundary (round-off
