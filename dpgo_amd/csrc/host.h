@@ -134,6 +134,7 @@ inline int free_bsr(Bsr& m) {
   X(persist_max_poses, "DPGO_PERSIST_MAX_POSES",  0,  "largest block the one-launch solve takes (0: every block it can hold)")       \
   X(persist_split,     "DPGO_PERSIST_SPLIT",      0,  "lane groups per pose of the one-launch solve: 1, 4 (0: by size)")             \
   X(persist_mt,        "DPGO_PERSIST_MT",         0,  "tiles per workgroup of the one-launch solve: 1, 2 (0: by size)")              \
+  X(additive_tiles,    "DPGO_ADDITIVE_TILES",     1,  "workgroup tiles per aggregate of the additive one-launch solve: 1, 2 (opt-in: blocks up to ~28 000 poses)") \
   X(poll_first,        "DPGO_POLL_FIRST",        -1,  "s_sleep units before the first sweep of the in-kernel all-reduce")            \
   X(poll_sleep,        "DPGO_POLL_SLEEP",        -1,  "s_sleep units between sweeps of the in-kernel all-reduce")                    \
   X(poll_first_pay,    "DPGO_POLL_FIRST_PAY",    -1,  "the same before the first sweep of a reduction that carries a payload")       \
@@ -252,6 +253,9 @@ struct dpgo_problem_s {
     bool graph = true;
   } add_plan;
   bool add_plan_known = false;
+  // workgroup tiles one aggregate of the additive layout may take: 1, or 2 for blocks no one-tile plan holds
+  // (dpgo_problem_additive_tiles; 0 = DPGO_ADDITIVE_TILES)
+  int add_tiles = 0;
   // the aggregation the plan was found with (host arrays), reused by the symbolic setup that follows: growing and merging
   // the aggregates of a 12 500-pose block is 1.4 ms of host time
   struct AggCache {
@@ -699,6 +703,8 @@ int ml_numeric_setup(dpgo_problem_s* p);
 std::vector<int> ml_current_ks(const dpgo_problem_s* p);
 const dpgo_problem_s::AddPlan& additive_plan(dpgo_problem_s* p);
 int additive_split_of(const dpgo_problem_s* p);
+int additive_tiles(const dpgo_problem_s* p);
+int additive_mt_of(const dpgo_problem_s* p);
 int ml_ensure(dpgo_problem_s* p, double shift, bool additive = false);
 int ml_ops32_ensure(dpgo_problem_s* p);
 int persist_capacity(int device);  // (two resident slots per CU; below)
@@ -723,6 +729,7 @@ bool persist_reserve(dpgo_problem_s* p, int slots, int limit);
 void persist_release(dpgo_problem_s* p);
 bool additive_available(dpgo_problem_s* p);
 PersistGeo persist_geometry(const dpgo_problem_s* p, int free_slots, int share = 1, bool additive = false);
+bool additive_lds_fits(const dpgo_problem_s* p, int split, int mt, int na);
 int launch_rtr_persistent(dpgo_problem_s* p, const dpgo_ropt_params* prm, const double* dinv, bool* used, bool additive);
 void persist_report(dpgo_problem_s* p);
 int rtr_outer_iteration(dpgo_problem_s* p, const dpgo_ropt_params* prm, const double* dinv, Counters& cnt,

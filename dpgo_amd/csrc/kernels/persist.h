@@ -340,8 +340,9 @@ __device__ __forceinline__ void gather_finish(const GatherOps<D, R, SPLIT, QRES>
 constexpr int persist_slots_per_wg(int, int, bool = false) { return 2; }
 
 // ADD: the preconditioner is the ADDITIVE two-level combination  z = proj_X( w Dinv r + P A_c^-1 P^T r )  on the handle's
-// two-level hierarchy with ONE aggregate per workgroup tile (at most Geo::P poses: 16 with 4 lane groups per pose, 64 with
-// one pose per (D+1) lanes -- blocks up to ~14 000 poses in 3-D): block-Jacobi plus the coarse-grid correction of
+// two-level hierarchy with ONE aggregate per workgroup (MT = 1: one tile, at most Geo::P poses -- 16 with 4 lane groups per
+// pose, 64 with one pose per (D+1) lanes: blocks up to ~14 000 poses in 3-D; MT = 2, one pose per (D+1) lanes only, opt-in:
+// the workgroup's two tiles, 2 Geo::P slots -- 128 poses in 3-D, blocks up to ~28 000): block-Jacobi plus the coarse-grid correction of
 // the residual itself, so nothing inside the preconditioner applies an operator to a vector other workgroups hold -- the
 // only exchange is the restricted residual rc (n / P coarse nodes x (D+1) R doubles: an all-gather every workgroup reads
 // in full), and it rides on a reduction the iteration needs anyway.  Per iteration (round 2-5 form, DPGO_ADD_PAYLOAD=0):
@@ -408,7 +409,7 @@ __global__ __launch_bounds__(kBlock, 1) void k_rtr_persist(BsrDev Q, double* X, 
                                                            AddDev add) {
   using GEO = Geo<D, R, SPLIT>;
   constexpr int P = GEO::P, G = GEO::G, T = GEO::T, B = GEO::B, BB = GEO::BB;
-  static_assert(!ADD || MT == 1, "additive preconditioner: one aggregate = one tile per workgroup");
+  static_assert(!ADD || MT == 1 || SPLIT == 1, "additive preconditioner: one aggregate = the workgroup's tiles");
   // resident in LDS: the poses' X (projections need all rotation columns of a pose) and z (Hessian correction; after the
   // tCG loop the same tiles hold the trial point x2); ex: two wave-private exchange tiles (the columns of one pose meet here)
   __shared__ __attribute__((aligned(16))) double Xs[MT][P][T], Zs[MT][P][T];
@@ -416,14 +417,19 @@ __global__ __launch_bounds__(kBlock, 1) void k_rtr_persist(BsrDev Q, double* X, 
   // column: kept out of the registers the tCG loop needs)
   __shared__ __attribute__((aligned(16))) double G1s[MT][P][T], G2s[MT][P][T];
   // (own-tile gathers, persist_local: the step eta of the workgroup's poses, for the H eta gather of the rho test)
-  constexpr bool kLoc = persist_local<SPLIT>();
-  __shared__ __attribute__((aligned(16))) double Es[kLoc ? MT : 1][kLoc ? P : 1][kLoc ? T : 1];
+  // (the two-tile additive layout gathers eta from memory: its 20 KB of LDS hold the rows of A_c^-1 instead)
+  constexpr bool kLoc = persist_local<SPLIT>(), kLocE = kLoc && !(ADD && MT > 1);
+  __shared__ __attribute__((aligned(16))) double Es[kLocE ? MT : 1][kLocE ? P : 1][kLocE ? T : 1];
   __shared__ __attribute__((aligned(16))) double ex[2][kWaves][G][T];
   __shared__ double red[2 * 2 * kWaves * kGranVals];
   __shared__ int ok_s;
-  // additive preconditioner: P_i^T r_i of the tile's poses, the aggregate's coarse solution, its per-wave partial sums;
+  // additive preconditioner: P_i^T r_i of the tile's poses (two tiles: summed over both), the aggregate's coarse solution,
+  // its per-wave partial sums;
   // dynamic LDS: the (D+1) rows of A_c^-1 this workgroup's aggregate needs, (D+1) x N_c doubles
-  __shared__ double ts[ADD ? P : 1][ADD ? T : 1], xc_s[ADD ? T : 1], xw_s[ADD ? kWaves : 1][ADD ? T : 1];
+  // (two tiles: a wave's G rows of ts are the wave's idle exchange tile -- the 10-12 KB that let every (d, r) instance
+  // hold 256 aggregates' coarse rows within the CU's 160 KiB)
+  constexpr bool kTsOwn = ADD && MT == 1;
+  __shared__ double ts[kTsOwn ? P : 1][kTsOwn ? T : 1], xc_s[ADD ? T : 1], xw_s[ADD ? kWaves : 1][ADD ? T : 1];
   __shared__ double tw_s[ADD ? kWaves : 1][ADD ? T : 1];  // per-wave sums of P_i^T r_i
   extern __shared__ double Ms[];
 
@@ -434,10 +440,12 @@ __global__ __launch_bounds__(kBlock, 1) void k_rtr_persist(BsrDev Q, double* X, 
   unsigned step = 0;
   const LaneId L = lane_id<D, SPLIT>();
   const int lp = L.wave * G + L.g;  // pose slot inside a workgroup tile
-  // (additive preconditioner: a workgroup's tile = an aggregate; with graph aggregates its poses are anywhere)
+  // (additive preconditioner: a workgroup's tiles = an aggregate; with graph aggregates its poses are anywhere)
   const int ntiles = ADD ? add.nc : (n + P - 1) / P;
   const int co = L.c * R;
-  __shared__ int pidx_s[ADD ? P : 1];  // ADD: pose of every slot of the tile (-1: empty), for the publishing lanes
+  __shared__ int pidx_s[ADD ? MT * P : 1];  // ADD: pose of every slot of the tiles (-1: empty), for the publishing lanes
+  // the workgroup's tile k holds poses (workgroup-uniform)
+  auto tile_on = [&](int k) { return ADD ? rank < ntiles : rank + k * members < ntiles; };
 
   // ---- resident data of the workgroup's rows (registers; X and z also in LDS)
   // block columns resident in registers (2 blocks per lane group with SPLIT = 4; with SPLIT = 1 the row's first 2 (D+1)
@@ -457,15 +465,15 @@ __global__ __launch_bounds__(kBlock, 1) void k_rtr_persist(BsrDev Q, double* X, 
   double rr[MT][R], ee[MT][R], dl[MT][R], hd[MT][R], zc[MT][R], srow[MT][D], drow[MT][B];
 #pragma unroll
   for (int k = 0; k < MT; ++k) {
-    const int tile = rank + k * members;
+    const int tile = ADD ? rank * MT + k : rank + k * members;  // (ADD: slots [k P, (k + 1) P) of aggregate `rank`)
     pose[k] = tile * P + lp;
     if constexpr (ADD) {
-      if (add.perm) pose[k] = (tile < ntiles && L.g < G) ? add.perm[tile * P + lp] : -1;
+      if (add.perm) pose[k] = (tile_on(k) && L.g < G) ? add.perm[tile * P + lp] : -1;
     }
-    okp[k] = (tile < ntiles) && (L.g < G) && (pose[k] >= 0) && (pose[k] < n);
+    okp[k] = tile_on(k) && (L.g < G) && (pose[k] >= 0) && (pose[k] < n);
     if (!okp[k]) pose[k] = 0;  // (a valid row for the wave-cooperative helpers; never used)
     if constexpr (ADD) {
-      if (L.s == 0 && L.c == 0 && L.g < G) pidx_s[lp] = okp[k] ? pose[k] : -1;
+      if (L.s == 0 && L.c == 0 && L.g < G) pidx_s[k * P + lp] = okp[k] ? pose[k] : -1;
     }
     own[k] = okp[k] && (L.s == 0);
     gather_setup<D, R, SPLIT, QRES>(go[k], Q, pose[k], L.s, L.c, okp[k]);
@@ -478,8 +486,8 @@ __global__ __launch_bounds__(kBlock, 1) void k_rtr_persist(BsrDev Q, double* X, 
           if (add.lab) {  // (both lookups issued together: one round trip)
             const int la = add.lab[j], mp = add.mem_pos[j];
             if (la == rank) lc = mp - add.agg_ptr[rank];
-          } else if (j / P == rank) {
-            lc = j - rank * P;
+          } else if (j / (MT * P) == rank) {
+            lc = j - rank * MT * P;
           }
         } else {
 #pragma unroll
@@ -506,7 +514,7 @@ __global__ __launch_bounds__(kBlock, 1) void k_rtr_persist(BsrDev Q, double* X, 
     }
   }
   wave_sync();
-  [[maybe_unused]] double pcol[B], prow[B];  // column c / row c of the pose's prolongation block
+  [[maybe_unused]] double pcol[MT][B], prow[MT][B];  // column c / row c of the pose's prolongation block
   // (payload form) aggregate threadIdx.x's (D+1) x R entries of the restricted residual, kept for a whole tCG run, and of
   // the restricted H delta the last Hessian-step reduction carried
   [[maybe_unused]] double rct[ADD ? T : 1], hct[ADD ? T : 1];
@@ -514,10 +522,12 @@ __global__ __launch_bounds__(kBlock, 1) void k_rtr_persist(BsrDev Q, double* X, 
   [[maybe_unused]] const __amdgpu_buffer_rsrc_t rrc = vec_rsrc(add.rc, (size_t)(ADD ? add.nc : 0) * T * sizeof(double));
   if constexpr (ADD) {
 #pragma unroll
-    for (int cc = 0; cc < B; ++cc) {
-      pcol[cc] = own[0] ? add.Pb[(size_t)pose[0] * BB + cc * B + L.c] : 0.0;
-      prow[cc] = own[0] ? add.Pb[(size_t)pose[0] * BB + L.c * B + cc] : 0.0;
-    }
+    for (int k = 0; k < MT; ++k)
+#pragma unroll
+      for (int cc = 0; cc < B; ++cc) {
+        pcol[k][cc] = own[k] ? add.Pb[(size_t)pose[k] * BB + cc * B + L.c] : 0.0;
+        prow[k][cc] = own[k] ? add.Pb[(size_t)pose[k] * BB + L.c * B + cc] : 0.0;
+      }
     if (rank < ntiles) {
       // (all of a thread's loads in flight together -- Nc <= kPersistMax (D+1): at most D+1 per row -- instead of one
       // dependent round trip per element: the additive form's set-up was 9 us longer than block-Jacobi's)
@@ -546,7 +556,7 @@ __global__ __launch_bounds__(kBlock, 1) void k_rtr_persist(BsrDev Q, double* X, 
     part[0] = part[1] = 0.0;
 #pragma unroll
     for (int k = 0; k < MT; ++k) {
-      if (rank + k * members >= ntiles) break;  // workgroup-uniform
+      if (!tile_on(k)) break;  // workgroup-uniform
       double zz[R];
       if (own[k]) {
 #pragma unroll
@@ -611,7 +621,7 @@ __global__ __launch_bounds__(kBlock, 1) void k_rtr_persist(BsrDev Q, double* X, 
 
   // ---- ADD: the wave's pose slots leave as lane-linear 16-byte write-through pieces, every pose to its own place (the
   // poses of a graph aggregate are not contiguous)
-  [[maybe_unused]] auto publish_slots = [&](__amdgpu_buffer_rsrc_t rs, const double* wave_tile) {
+  [[maybe_unused]] auto publish_slots = [&](__amdgpu_buffer_rsrc_t rs, const double* wave_tile, int k) {
     if constexpr (ADD && T % 2 == 0) {
       const dbl2* span = reinterpret_cast<const dbl2*>(wave_tile);
 #pragma unroll
@@ -619,7 +629,7 @@ __global__ __launch_bounds__(kBlock, 1) void k_rtr_persist(BsrDev Q, double* X, 
         const int pc = (int)(threadIdx.x & 63) + 64 * it;
         if (pc < G * (T / 2)) {
           const int ps = pc / (T / 2), sub = pc - ps * (T / 2);
-          const int gp = pidx_s[L.wave * G + ps];
+          const int gp = pidx_s[k * P + L.wave * G + ps];
           if (gp >= 0) {
             const dbl2 v = span[pc];
             u32x4 w;
@@ -637,28 +647,30 @@ __global__ __launch_bounds__(kBlock, 1) void k_rtr_persist(BsrDev Q, double* X, 
   // ---- additive preconditioner, first half: r, eta update; x1 = Dinv r (kept in zc); rc = sum over the tile of P_i^T r_i
   // (payload form: `with_rc` = the restriction is wanted -- the first residual of a tCG run; it is left as per-wave sums in
   // tw_s for the reduction that carries it)
-  // P_i^T v_i of the wave's poses (their B columns of v in `tile`), summed over the wave's G pose slots in a fixed order
-  [[maybe_unused]] auto restrict_to_waves = [&](const double (*tile)[T]) {
+  // P_i^T v_i of the wave's poses of the workgroup's tile k (their B columns of v in `tile`), added to the lane's t
+  [[maybe_unused]] auto restrict_add = [&](const double (*tile)[T], int k, double (&t)[R]) {
     if constexpr (ADD) {
-      if (L.s == 0 && L.g < G) {
-        double t[R];
+      if (own[k]) {
 #pragma unroll
-        for (int a = 0; a < R; ++a) t[a] = 0.0;
-        if (own[0]) {
+        for (int cc = 0; cc < B; ++cc) {  // row c of P_i^T v_i = sum_c' P_i[c'][c] v_i[c'][:]
 #pragma unroll
-          for (int cc = 0; cc < B; ++cc) {  // row c of P_i^T v_i = sum_c' P_i[c'][c] v_i[c'][:]
-#pragma unroll
-            for (int a = 0; a < R; ++a) t[a] = fma(pcol[cc], tile[L.g][cc * R + a], t[a]);
-          }
+          for (int a = 0; a < R; ++a) t[a] = fma(pcol[k][cc], tile[L.g][cc * R + a], t[a]);
         }
-        store_col<R>(&ts[lp][co], t);  // zeros for pose slots beyond n
       }
+    }
+  };
+  // the lanes' t summed over the wave's G pose slots in a fixed order
+  // (`idle`: an exchange buffer the caller does not use here -- the wave's rows of ts with two tiles)
+  [[maybe_unused]] auto restrict_to_waves = [&](const double (&t)[R], int idle) {
+    if constexpr (ADD) {
+      double (*wt)[T] = kTsOwn ? reinterpret_cast<double (*)[T]>(&ts[0][0]) + L.wave * G : ex[idle][L.wave];
+      if (L.s == 0 && L.g < G) store_col<R>(&wt[L.g][co], t);  // zeros for pose slots beyond n
       wave_sync();
       if ((int)(threadIdx.x & 63) < T) {
         const int e = threadIdx.x & 63;
-        double sum = ts[L.wave * G][e];
+        double sum = wt[0][e];
 #pragma unroll
-        for (int m = 1; m < G; ++m) sum += ts[L.wave * G + m][e];
+        for (int m = 1; m < G; ++m) sum += wt[m][e];
         tw_s[L.wave][e] = sum;
       }
     }
@@ -666,25 +678,33 @@ __global__ __launch_bounds__(kBlock, 1) void k_rtr_persist(BsrDev Q, double* X, 
   auto phase_add_restrict = [&](bool first, double alpha, double (&part)[1], bool with_rc = true) {
     part[0] = 0.0;
     if constexpr (ADD) {
-      if (own[0]) {
+      double t[R];
 #pragma unroll
-        for (int a = 0; a < R; ++a) {
-          if (!first) {
-            ee[0][a] = fma(alpha, dl[0][a], ee[0][a]);
-            rr[0][a] = fma(alpha, hd[0][a], rr[0][a]);
+      for (int a = 0; a < R; ++a) t[a] = 0.0;
+#pragma unroll
+      for (int k = 0; k < MT; ++k) {
+        if (own[k]) {
+#pragma unroll
+          for (int a = 0; a < R; ++a) {
+            if (!first) {
+              ee[k][a] = fma(alpha, dl[k][a], ee[k][a]);
+              rr[k][a] = fma(alpha, hd[k][a], rr[k][a]);
+            }
+            part[0] = fma(rr[k][a], rr[k][a], part[0]);
           }
-          part[0] = fma(rr[0][a], rr[0][a], part[0]);
+          store_col<R>(&ex[0][L.wave][L.g][co], rr[k]);
         }
-        store_col<R>(&ex[0][L.wave][L.g][co], rr[0]);
+        wave_sync();  // the pose's B columns of r are in LDS
+        if (own[k]) jacobi_col<D, R>(&ex[0][L.wave][L.g][0], drow[k], zc[k]);  // x1 (unweighted), until z replaces it
+        if (with_rc || !kAddPayload) restrict_add(ex[0][L.wave], k, t);
+        if (k + 1 < MT) wave_sync();  // (ex[0] is rewritten by the next tile)
       }
-      wave_sync();  // the pose's B columns of r are in LDS
-      if (own[0]) jacobi_col<D, R>(&ex[0][L.wave][L.g][0], drow[0], zc[0]);  // x1 (unweighted), until z replaces it
       if constexpr (kAddPayload) {
-        if (with_rc) restrict_to_waves(ex[0][L.wave]);
+        if (with_rc) restrict_to_waves(t, 1);
         return;
       }
       // fixed order: every wave adds up its own G pose slots, then the waves in order; the all-gathered coarse residual
-      restrict_to_waves(ex[0][L.wave]);
+      restrict_to_waves(t, 1);
       __syncthreads();
       if ((int)threadIdx.x < T && rank < ntiles) {
         double sum = tw_s[0][threadIdx.x];
@@ -768,33 +788,38 @@ __global__ __launch_bounds__(kBlock, 1) void k_rtr_persist(BsrDev Q, double* X, 
         xc_s[threadIdx.x] = sum;
       }
       __syncthreads();
-      double xx[R];
-      if (own[0]) {
 #pragma unroll
-        for (int a = 0; a < R; ++a) {
-          double v = add.w * zc[0][a];
+      for (int k = 0; k < MT; ++k) {
+        double xx[R];
+        if (own[k]) {
 #pragma unroll
-          for (int cc = 0; cc < B; ++cc) v = fma(prow[cc], xc_s[cc * R + a], v);
-          xx[a] = v;
+          for (int a = 0; a < R; ++a) {
+            double v = add.w * zc[k][a];
+#pragma unroll
+            for (int cc = 0; cc < B; ++cc) v = fma(prow[k][cc], xc_s[cc * R + a], v);
+            xx[a] = v;
+          }
+          store_col<R>(&ex[1][L.wave][L.g][co], xx);
         }
-        store_col<R>(&ex[1][L.wave][L.g][co], xx);
-      }
-      wave_sync();
-      if (own[0]) {
-        double out[R], s[D];
-        proj_col<D, R>(&Xs[0][lp][0], &ex[1][L.wave][L.g][0], L.c, xx, out, s);
-        const size_t off = (size_t)pose[0] * T + co;
-#pragma unroll
-        for (int a = 0; a < R; ++a) {
-          part[0] = fma(out[a], rr[0][a], part[0]);
-          zc[0][a] = out[a];
-          Zs[0][lp][co + a] = out[a];
-          if constexpr (T % 2 != 0) st_agent(z + off + a, out[a]);
-        }
-      }
-      if constexpr (T % 2 == 0) {
         wave_sync();
-        publish_slots(rz, &Zs[0][L.wave * G][0]);
+        if (own[k]) {
+          double out[R], s[D];
+          proj_col<D, R>(&Xs[k][lp][0], &ex[1][L.wave][L.g][0], L.c, xx, out, s);
+          const size_t off = (size_t)pose[k] * T + co;
+#pragma unroll
+          for (int a = 0; a < R; ++a) {
+            part[0] = fma(out[a], rr[k][a], part[0]);
+            zc[k][a] = out[a];
+            Zs[k][lp][co + a] = out[a];
+            if constexpr (T % 2 != 0) st_agent(z + off + a, out[a]);
+          }
+        }
+        if constexpr (T % 2 == 0) {
+          wave_sync();
+          publish_slots(rz, &Zs[k][L.wave * G][0], k);
+        } else if (k + 1 < MT) {
+          wave_sync();  // (ex[1] is rewritten by the next tile)
+        }
       }
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     }
@@ -823,7 +848,7 @@ __global__ __launch_bounds__(kBlock, 1) void k_rtr_persist(BsrDev Q, double* X, 
     }
 #pragma unroll
     for (int k = 0; k < MT; ++k) {
-      if (rank + k * members >= ntiles) break;
+      if (!tile_on(k)) break;
       double* xt = &ex[k & 1][L.wave][L.g][0];
       if (own[k]) {
         if (L.c < D) {
@@ -849,10 +874,18 @@ __global__ __launch_bounds__(kBlock, 1) void k_rtr_persist(BsrDev Q, double* X, 
         }
       }
     }
-    if constexpr (ADD && kAddPayload) {  // P^T (H delta) of the tile rides on the reduction of <delta, H delta>
-      if (own[0]) store_col<R>(&ex[1][L.wave][L.g][co], hd[0]);
-      wave_sync();
-      restrict_to_waves(ex[1][L.wave]);
+    if constexpr (ADD && kAddPayload) {  // P^T (H delta) of the tiles rides on the reduction of <delta, H delta>
+      double t[R];
+#pragma unroll
+      for (int a = 0; a < R; ++a) t[a] = 0.0;
+#pragma unroll
+      for (int k = 0; k < MT; ++k) {
+        if (MT > 1) wave_sync();  // (ex[1] was read by the last tile above / by the previous restriction)
+        if (own[k]) store_col<R>(&ex[1][L.wave][L.g][co], hd[k]);
+        wave_sync();
+        restrict_add(ex[1][L.wave], k, t);
+      }
+      restrict_to_waves(t, 0);
     }
   };
 
@@ -863,7 +896,7 @@ __global__ __launch_bounds__(kBlock, 1) void k_rtr_persist(BsrDev Q, double* X, 
                           const double (&col)[R]) {
     if constexpr (ADD && T % 2 == 0) {
       wave_sync();
-      publish_slots(rs, wave_tile);
+      publish_slots(rs, wave_tile, k);
     } else if constexpr (T % 2 == 0) {
       wave_sync();
       const int p0w = tile * P + L.wave * G;
@@ -909,7 +942,7 @@ __global__ __launch_bounds__(kBlock, 1) void k_rtr_persist(BsrDev Q, double* X, 
         gather_issue<D, R, SPLIT, QRES>(go[k], Q, ry, L.s, L.c, xc, qc, own_y);
         gather_finish<D, R, SPLIT, QRES>(go[k], Q, ry, L.s, L.c, xc, qc, eg);
       }
-      if (rank + k * members >= ntiles) continue;  // workgroup-uniform (the gather above is wave-cooperative)
+      if (!tile_on(k)) continue;  // workgroup-uniform (the gather above is wave-cooperative)
       double* xt = &ex[k & 1][L.wave][L.g][0];
       if (own[k]) {
         const size_t off = (size_t)pose[k] * T + co;
@@ -1122,7 +1155,7 @@ __global__ __launch_bounds__(kBlock, 1) void k_rtr_persist(BsrDev Q, double* X, 
   double p1[1] = {0.0};  // <eta, g1>
 #pragma unroll
   for (int k = 0; k < MT; ++k) {
-    if (rank + k * members >= ntiles) break;  // workgroup-uniform
+    if (!tile_on(k)) break;  // workgroup-uniform
     double a2[R];
     if (own[k]) {
 #pragma unroll
@@ -1137,7 +1170,7 @@ __global__ __launch_bounds__(kBlock, 1) void k_rtr_persist(BsrDev Q, double* X, 
       qf_col<D, R>(&ex[0][L.wave][L.g][0], L.c, a2);
       store_col<R>(&Zs[k][lp][co], a2);
       store_col<R>(&ex[1][L.wave][L.g][co], ee[k]);
-      if constexpr (kLoc) store_col<R>(&Es[k][lp][co], ee[k]);
+      if constexpr (kLocE) store_col<R>(&Es[k][lp][co], ee[k]);
     }
     publish_tile(xbuf, rx2, &Zs[k][L.wave * G][0], rank + k * members, k, a2);
     publish_tile(ebuf, reta, &ex[1][L.wave][0][0], rank + k * members, k, ee[k]);
@@ -1162,10 +1195,10 @@ __global__ __launch_bounds__(kBlock, 1) void k_rtr_persist(BsrDev Q, double* X, 
     double h[R];
     {
       double xc[GG::NB][R], qc[GG::NB][B];
-      gather_issue<D, R, SPLIT, QRES>(go[k], Q, reta, L.s, L.c, xc, qc, kLoc ? &Es[0][0][0] : nullptr);
+      gather_issue<D, R, SPLIT, QRES>(go[k], Q, reta, L.s, L.c, xc, qc, kLocE ? &Es[0][0][0] : nullptr);
       gather_finish<D, R, SPLIT, QRES>(go[k], Q, reta, L.s, L.c, xc, qc, h);
     }
-    if (rank + k * members >= ntiles) continue;
+    if (!tile_on(k)) continue;
     if (own[k]) store_col<R>(&ex[0][L.wave][L.g][co], ee[k]);  // the pose's columns of eta
     wave_sync();
     if (own[k]) {

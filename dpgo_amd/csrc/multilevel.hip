@@ -809,7 +809,14 @@ std::vector<int> ml_current_ks(const dpgo_problem_s* p) {
 //   2. else one pose per (d+1) lanes (tile = 64 poses in 3-D): graph aggregates grown to S poses, fragments merged up to
 //      min(tile, 3 S / 2), with the smallest S (from ceil(n / 230) in steps of an eighth) that leaves <= 256 aggregates
 //      (12 500-pose slab: S = 55, 230 aggregates; 6 250-pose grid: S = 28, 221) -- blocks up to ~14 000 poses;
-//   3. without graph aggregates (DPGO_ML_GRAPH=0): index runs of one tile.
+//   3. without graph aggregates (DPGO_ML_GRAPH=0): index runs of one tile;
+//   4. opt-in (additive_tiles(p) == 2), none of the above fits: graph aggregates of the workgroup's TWO tiles (128 poses in
+//      3-D, 168 in 2-D), grown and merged as in 2 with tile = 2 P1 -- blocks up to ~28 000 poses -- if the instance's
+//      LDS holds that many aggregates' coarse rows (additive_lds_fits).
+int additive_tiles(const dpgo_problem_s* p) {
+  const int t = p->add_tiles ? p->add_tiles : options().additive_tiles;
+  return t == 2 ? 2 : 1;
+}
 const dpgo_problem_s::AddPlan& additive_plan(dpgo_problem_s* p) {
   if (p->add_plan_known) return p->add_plan;
   p->add_plan = dpgo_problem_s::AddPlan();
@@ -864,6 +871,22 @@ const dpgo_problem_s::AddPlan& additive_plan(dpgo_problem_s* p) {
     p->add_plan = dpgo_problem_s::AddPlan{4, P4, P4, 0, (n + P4 - 1) / P4, false};
   else if ((n + P1 - 1) / P1 <= kPersistMax)
     p->add_plan = dpgo_problem_s::AddPlan{1, P1, P1, 0, (n + P1 - 1) / P1, false};
+  const int P2 = 2 * P1;
+  if (!p->add_plan.split && graph_ok && additive_tiles(p) == 2 && (long long)n <= (long long)kPersistMax * P2) {
+    auto& A = p->add_agg;
+    for (int S = std::max(8, (n + 229) / 230); S <= P2; S += std::max(2, S / 8)) {
+      const int cap = std::min(P2, S + S / 2);
+      ml_graph_aggregates(p->h_rowptr, p->h_colidx, n, S, A.lab, A.ptr, A.mem, A.parent, A.pslot);
+      const int na = ml_merge_small_aggregates(p->h_rowptr, p->h_colidx, n, S, cap, A.lab, A.ptr, A.mem, A.parent, A.pslot);
+      if (na <= kPersistMax) {
+        if (!additive_lds_fits(p, 1, 2, na)) break;  // (static + coarse-row LDS beyond the CU's: no plan)
+        p->add_plan = dpgo_problem_s::AddPlan{1, P2, S, cap, na, true};
+        A.S = S, A.cap = cap;
+        return p->add_plan;
+      }
+    }
+    p->add_agg = dpgo_problem_s::AggCache();
+  }
   return p->add_plan;
 }
 
@@ -873,7 +896,11 @@ int additive_split_of(const dpgo_problem_s* p) {
   const auto& L = p->ml[0];
   const int P4 = ml_tile(p->b, 4), P1 = ml_tile(p->b, 1);
   const int tile = L.graph ? (L.tile_perm ? L.perm_tile : 0) : L.k;
-  return tile == P4 ? 4 : (tile == P1 ? 1 : 0);
+  return tile == P4 ? 4 : (tile == P1 || (tile == 2 * P1 && L.graph && additive_tiles(p) == 2) ? 1 : 0);
+}
+// workgroup tiles per aggregate of that layout (1 or 2)
+int additive_mt_of(const dpgo_problem_s* p) {
+  return additive_split_of(p) == 1 && p->ml[0].perm_tile == 2 * ml_tile(p->b, 1) ? 2 : 1;
 }
 
 // Make the hierarchy match the handle's Q (lazily, like the reference's constructPreconditioner inside the first
@@ -884,7 +911,8 @@ int ml_ensure(dpgo_problem_s* p, double shift, bool additive) {
   // (additive_plan) and put back when the V-cycle is asked for again
   if (additive && !additive_split_of(p)) {
     const auto& plan = additive_plan(p);
-    if (!plan.split) return fail(DPGO_ERR_UNSUPPORTED, "additive preconditioner: the block does not fit 256 aggregates of one workgroup tile");
+    if (!plan.split) return fail(DPGO_ERR_UNSUPPORTED, "additive preconditioner: the block does not fit 256 aggregates of one workgroup tile" +
+                                                           std::string(additive_tiles(p) == 2 ? " or two" : ""));
     std::vector<int> ks{plan.graph ? -plan.S : plan.S};
     if (plan.graph && plan.cap) ks.push_back(-plan.cap);
     CHK(ml_symbolic_setup(p, ks, plan.graph ? plan.tile : 0));
@@ -1204,6 +1232,20 @@ int dpgo_problem_additive_plan(dpgo_problem_t p, int* lane_groups, int* tile, in
 }
 
 
+int dpgo_problem_additive_tiles(dpgo_problem_t p, int* tiles) {
+  if (!p || !tiles) return fail(DPGO_ERR_INVALID, "null handle / pointer");
+  if (*tiles < 0 || *tiles > 2) return fail(DPGO_ERR_INVALID, "additive tiles: 1 or 2 (0 queries)");
+  if (*tiles > 0 && *tiles != additive_tiles(p)) {
+    p->add_tiles = *tiles;
+    p->add_plan_known = false;  // (the plan and the hierarchy built for it follow the new value at the next solve)
+    p->add_agg = dpgo_problem_s::AggCache();
+    if (p->ml_additive_layout && !p->ml_user_ks) ml_free(p);
+  }
+  *tiles = additive_tiles(p);
+  return DPGO_OK;
+}
+
+
 int dpgo_problem_setup_multilevel(dpgo_problem_t p, int nks, const int* ks, double omega, double shift) {
   CHK(check_ready(p));
   if (nks < 0 || nks > 8 || (nks > 0 && !ks) || !(omega > 0.0) || !(shift >= 0.0))
@@ -1216,6 +1258,8 @@ int dpgo_problem_setup_multilevel(dpgo_problem_t p, int nks, const int* ks, doub
     int perm_tile = 0;
     if (v.size() == 2 && v[0] < 0 && v[1] < 0 && p->split == 4)
       perm_tile = -v[1] <= ml_tile(p->b, 4) ? ml_tile(p->b, 4) : (-v[1] <= ml_tile(p->b, 1) ? ml_tile(p->b, 1) : 0);
+    if (!perm_tile && v.size() == 2 && v[0] < 0 && v[1] < 0 && p->split == 4 && additive_tiles(p) == 2 && -v[1] <= 2 * ml_tile(p->b, 1))
+      perm_tile = 2 * ml_tile(p->b, 1);  // (the two-tile layout, opt-in)
     CHK(ml_symbolic_setup(p, v, perm_tile));
   }
   p->ml_user_ks = nks > 0;

@@ -138,6 +138,26 @@ void persist_release(dpgo_problem_s* p) {
 bool additive_available(dpgo_problem_s* p) {
   return p->persist && !p->persist_failed_once && additive_plan(p).split != 0;
 }
+// LDS of one workgroup (gfx950: 160 KiB per CU; every persistent instance runs one workgroup per CU)
+constexpr size_t kPersistLds = 160 * 1024;
+// The additive instance of this layout fits one CU with `na` aggregates: its static LDS (as compiled for the handle's
+// (d, r)) plus the (d+1) rows of A_c^-1 per workgroup, (d+1)^2 na doubles.  With two tiles per workgroup the static part
+// grows with (d+1) r; an instance the compiler could not place is refused here, not at the launch.
+bool additive_lds_fits(const dpgo_problem_s* p, int split, int mt, int na) {
+  hipFuncAttributes a{};
+  bool ok = false;
+  auto query = [&]() -> int {
+    DISPATCH(p->d, p->r, {
+      const void* f = split == 4 ? reinterpret_cast<const void*>(&k_rtr_persist<D, R, 4, 1, true>)
+                                 : mt == 2 ? reinterpret_cast<const void*>(&k_rtr_persist<D, R, 1, 2, true>)
+                                           : reinterpret_cast<const void*>(&k_rtr_persist<D, R, 1, 1, true>);
+      ok = hipFuncGetAttributes(&a, f) == hipSuccess;
+    });
+    return DPGO_OK;
+  };
+  if (query() != DPGO_OK || !ok) return false;
+  return a.sharedSizeBytes + sizeof(double) * (size_t)p->b * p->b * na <= kPersistLds;
+}
 // `free_slots`: what may be reserved.  Alone on the device (share = 1): the lowest-latency layout that fits (4 lane groups
 // per pose while the tiles fit, then one pose per (d+1) lanes).  Sharing the device with `share` concurrently solved
 // agents: the lowest-latency layout of which `share` copies fit side by side; if there is none, the most compact one
@@ -146,7 +166,8 @@ PersistGeo persist_geometry(const dpgo_problem_s* p, int free_slots, int share, 
   if (additive) {  // fixed by the hierarchy (after ml_ensure); one workgroup per CU (the rows of the coarse inverse live in its LDS)
     const int sp = additive_split_of(p);
     if (!sp) return PersistGeo();
-    PersistGeo g{sp, 1, p->ml[1].n, 0};
+    PersistGeo g{sp, additive_mt_of(p), p->ml[1].n, 0};
+    if (g.mt == 2 && !additive_lds_fits(p, sp, g.mt, g.wgs)) return PersistGeo();  // (the V-cycle runs instead)
     g.slots = g.wgs * persist_slots_per_wg(sp, 1, true);
     if (g.wgs > kPersistMax || g.slots > free_slots) return PersistGeo();
     return g;
@@ -278,6 +299,7 @@ int launch_rtr_persistent(dpgo_problem_s* p, const dpgo_ropt_params* prm, const 
   } while (0)
   DISPATCH(p->d, p->r, {
     if (additive && p->persist_split == 4) PERSIST_LAUNCH(4, 1, true, lds);
+    else if (additive && p->persist_mt == 2) PERSIST_LAUNCH(1, 2, true, lds);
     else if (additive) PERSIST_LAUNCH(1, 1, true, lds);
     else if (p->persist_split == 4 && p->persist_mt == 1) PERSIST_LAUNCH(4, 1, false, 0);
     else if (p->persist_split == 4) PERSIST_LAUNCH(4, 2, false, 0);
@@ -532,6 +554,11 @@ int rtr_outer_iteration(dpgo_problem_s* p, const dpgo_ropt_params* prm, const do
 // (round 6: an additive iteration is two chip-wide reductions, as a block-Jacobi one -- 11.0 against 9.6 us on a 12 500-pose
 // slab, 8.7 against 6.6 on sphere2500; it was 15.7 / 10.6 with three: 18 units)
 constexpr int kAutoUnitsJacobi = 10, kAutoUnitsAdditive = 13, kAutoSetupUnits = 2800, kAutoMinProducts = 6;
+// (the two-tile additive layout, dpgo_problem_additive_tiles = 2, has a unit of its own, not reported by
+// dpgo_auto_rule_constants: 10 x the ratio of the two in-kernel iterations on the same 25 000-pose rank share of
+// grid:50x50x20 -- additive on two tiles 33.8 us (the instance spills), block-Jacobi on two tiles 15.4 us;
+// profiles/two_tile_additive.txt)
+constexpr int kAutoUnitsAdditive2 = 22;
 int auto_units_jacobi(dpgo_problem_s* p) {
   const int share = std::max(1, p->persist_share);
   if (share == 1 || !p->persist) return kAutoUnitsJacobi;
@@ -548,10 +575,11 @@ int auto_units_jacobi(dpgo_problem_s* p) {
 }
 int auto_units_additive(dpgo_problem_s* p) {  // (after additive_available(p): the plan exists)
   const int share = std::max(1, p->persist_share);
-  if (share == 1) return kAutoUnitsAdditive;
+  const int units = p->add_plan.tile == 2 * ml_tile(p->b, 1) ? kAutoUnitsAdditive2 : kAutoUnitsAdditive;
+  if (share == 1) return units;
   const int cap = persist_capacity(p->device);
   const double part = std::max((double)(p->add_plan.na * persist_slots_per_wg(p->add_plan.split, 1, true)) / cap, 1.0 / share);
-  return std::max(1, (int)std::lround(kAutoUnitsAdditive * part * share));
+  return std::max(1, (int)std::lround(units * part * share));
 }
 void auto_update(dpgo_problem_s* p, const dpgo_ropt_params* prm, int used, int products) {
   const int budget = std::max(1, prm->RTR_iterations) * std::max(1, prm->RTR_tCG_iterations);
@@ -653,7 +681,8 @@ int run_optimize(dpgo_problem_s* p, const dpgo_ropt_params* prm, dpgo_ropt_resul
     if (prm->method != DPGO_METHOD_RTR) return fail(DPGO_ERR_UNSUPPORTED, "the additive preconditioner exists inside the tCG loop only");
     if (!additive_split_of(p) && !additive_plan(p).split)
       return fail(DPGO_ERR_UNSUPPORTED, "additive preconditioner: block too large (at most 256 aggregates of one workgroup tile, " +
-                                            std::to_string(ml_tile(p->b, 1)) + " poses)");
+                                            std::to_string(ml_tile(p->b, 1)) + " poses" +
+                                            (additive_tiles(p) == 2 ? ", or of two" : "; dpgo_problem_additive_tiles: two") + ")");
     CHK(ml_ensure(p, prm->precond_shift, /*additive=*/true));
     dinv = p->dinv;
   } else if (prm->precond != DPGO_PRECOND_NONE) {

@@ -615,6 +615,14 @@ class QuadraticProblem:
         out["ks"] = ([-out["growth"]] + ([-out["merge_cap"]] if out["merge_cap"] else [])) if out["graph"] else [out["tile"]]
         return out
 
+    def additiveTiles(self, tiles: Optional[int] = None) -> int:
+        """Workgroup tiles one aggregate of the additive layout may take (dpgo_problem_additive_tiles): 1 (default,
+        DPGO_ADDITIVE_TILES) or 2, the opt-in for blocks no one-tile plan holds (up to 256 aggregates of 128 poses in
+        3-D, 168 in 2-D).  tiles = None queries; setting drops the cached plan.  Returns the current value."""
+        v = C.c_int(0 if tiles is None else int(tiles))
+        L.check(self._lib.dpgo_problem_additive_tiles(self._h, C.byref(v)))
+        return int(v.value)
+
     def multilevelGet(self, level: int, what: str) -> np.ndarray:
         """Copy of one item of the built hierarchy: "P" (prolongation blocks of a level), "rowptr" / "colidx" / "A"
         (Galerkin operator of a level >= 1), "inverse" (dense inverse of the last level), "labels" (graph aggregates:

@@ -54,8 +54,8 @@ extern "C" {
 /* DEFAULT.  A multilevel preconditioner whenever it pays, block-Jacobi otherwise, decided per handle from the solves
  * themselves (a function of their product counts only, so repeated runs reproduce; every change of Q starts over):
  *  - a block WITHOUT coupling to other agents runs multilevel from its first solve and never hands back;
- *  - a coupled block the additive one-launch solve can hold (dpgo_problem_additive_plan: up to ~14 000 poses in 3-D)
- *    follows a COST RULE, in units of a tenth of a block-Jacobi product (dpgo_auto_rule_constants): Q -- hence the
+ *  - a coupled block the additive one-launch solve can hold (dpgo_problem_additive_plan: up to ~14 000 poses in 3-D;
+ *    with dpgo_problem_additive_tiles = 2 up to ~28 000, charged a per-product cost of its own) follows a COST RULE, in units of a tenth of a block-Jacobi product (dpgo_auto_rule_constants): Q -- hence the
  *    hierarchy -- is constant across RBCD sweeps, so its set-up (2 800 units = 280 block-Jacobi products: 2.8-3.0 ms
  *    against 10 us) is paid once.  When the block-Jacobi solves since Q last changed have cost as much as one set-up
  *    (and the last one ran >= 6 products), or one of them used >= half its tCG budget, the next solve runs additive on
@@ -77,7 +77,8 @@ extern "C" {
  * of the residual; same tree prolongations and Galerkin coarse operator as the multilevel cycle; ONE aggregate per
  * workgroup of the one-launch solve: graph aggregates of at most 16 (3-D) / 20 (2-D) poses while 256 of them cover the
  * block, beyond that -- up to ~14 000 poses in 3-D -- of at most 64 / 84 poses with the growth's fragments merged,
- * dpgo_problem_additive_plan): nothing inside it applies an operator to a distributed vector, so a whole preconditioned
+ * dpgo_problem_additive_plan; opt-in, dpgo_problem_additive_tiles = 2: beyond that -- up to ~28 000 poses in 3-D -- of at
+ * most 128 / 168 poses, the workgroup's two tiles): nothing inside it applies an operator to a distributed vector, so a whole preconditioned
  * tCG iteration runs inside the persistent kernel (three in-kernel reductions).  Where the persistent kernel cannot run
  * (larger blocks: DPGO_ERR_UNSUPPORTED; no free resident slots or a time-out: silently) the solve uses the multilevel
  * V-cycle on the same hierarchy instead.  What DPGO_PRECOND_AUTO selects for such blocks when it selects a multilevel
@@ -266,6 +267,12 @@ int dpgo_multilevel_merged_aggregates(int n, const int32_t* rowptr, const int32_
  * (merge_cap 0: plain greedy growth; graph 0: index runs of `tile` poses, DPGO_ML_GRAPH=0), aggregates = workgroups. */
 int dpgo_problem_additive_plan(dpgo_problem_t h, int* lane_groups, int* tile, int* growth, int* merge_cap, int* aggregates,
                                int* graph);
+/* Workgroup tiles one aggregate of the additive layout may take.  In: 1 or 2 sets the value, 0 queries; out: the current
+ * value (default 1, or DPGO_ADDITIVE_TILES in the environment).  2 is an opt-in for blocks that have no one-tile plan:
+ * graph aggregates of at most 128 (3-D) / 168 (2-D) poses on the workgroup's two tiles (tile = 2 x 64 / 84, lane_groups 1),
+ * grown from the smallest size of the schedule that leaves <= 256 of them; blocks with a one-tile plan keep it.  Setting
+ * a new value drops the cached plan, and the hierarchy if it was built for the additive layout. */
+int dpgo_problem_additive_tiles(dpgo_problem_t h, int* tiles);
 int dpgo_problem_setup_multilevel(dpgo_problem_t h, int nks, const int* ks, double omega, double shift);
 int dpgo_problem_multilevel_info(dpgo_problem_t h, int* nlevels, int* sizes, int* ks, int* nnzb);
 int dpgo_problem_multilevel_get(dpgo_problem_t h, int level, int what, void* out_host);
