@@ -1,0 +1,214 @@
+"""Certificate of global optimality and the Riemannian staircase (C ABI dpgo_problem_certify*).
+
+  QuadraticProblem.certify(X)            lambda_min of C(X) = Q - Lambda(X) on the complement of the known null space, by a
+                                         preconditioned block LOBPCG on the device -> CertificateResult (+ witness)
+  QuadraticProblem.certificateApply(X, V)  V C(X) (tests)
+  solveCertifiedPGO(measurements)        SE-Sync's staircase on one handle per rank: solve, certify, escape to rank r + 1
+                                         along the witness while the iterate is a saddle; rounds the certified iterate
+
+Certification is defined for a problem WITHOUT a linear term G (the global or central problem: no shared loop closures, no
+priors).  CERTIFIED is numerical (the eigen-solver's smallest Ritz value on the complement is >= -eta scale with a small
+residual), not a lower-bound proof; NOT_CERTIFIED is a proof up to rounding (the witness has w^T C w < -eta scale).
+"""
+from __future__ import annotations
+
+import ctypes as C
+from dataclasses import dataclass, field
+from typing import List, Optional
+
+import numpy as np
+
+from . import lib as L
+from .measurements import RelativeSEMeasurements
+
+PRECONDS = {"none": L.PRECOND_NONE, "jacobi": L.PRECOND_BLOCK_JACOBI, "multilevel": L.PRECOND_MULTILEVEL,
+            "auto": L.PRECOND_AUTO, "additive": L.PRECOND_ADDITIVE}
+
+
+@dataclass
+class CertificateResult:
+    """dpgo_certify_result; status CERTIFIED | NOT_CERTIFIED | NOT_CONVERGED; witness: (n, d+1) unit vector or None."""
+    status: str
+    lambda_min: float
+    residual: float
+    gradnorm: float
+    scale: float
+    iterations: int
+    products: int
+    deflated: int
+    deflation_residual: float
+    elapsedMs: float
+    witness: Optional[np.ndarray] = None
+
+    @staticmethod
+    def from_c(c: L.CertifyResultC, witness=None) -> "CertificateResult":
+        return CertificateResult(L.CERT_STATUS[c.status], c.lambda_min, c.residual, c.gradnorm, c.scale, c.iterations,
+                                 c.products, c.deflated, c.deflation_residual, c.elapsedMs, witness)
+
+
+def certify_params(eta: Optional[float] = None, tol_rel: Optional[float] = None, max_iterations: Optional[int] = None,
+                   precond: Optional[str] = None, precond_shift: Optional[float] = None,
+                   seed: Optional[int] = None) -> L.CertifyParamsC:
+    """dpgo_certify_params: the library's defaults (dpgo_certify_params_default) with the given fields replaced."""
+    c = L.CertifyParamsC()
+    L.load().dpgo_certify_params_default(C.byref(c))
+    if eta is not None:
+        c.eta = float(eta)
+    if tol_rel is not None:
+        c.tol_rel = float(tol_rel)
+    if max_iterations is not None:
+        c.max_iterations = int(max_iterations)
+    if precond is not None:
+        if precond not in PRECONDS:
+            raise ValueError("unknown preconditioner %r (one of %s)" % (precond, sorted(PRECONDS)))
+        c.precond = PRECONDS[precond]
+    if precond_shift is not None:
+        c.precond_shift = float(precond_shift)
+    if seed is not None:
+        c.seed = int(seed)
+    if not (c.eta >= 0 and c.tol_rel > 0 and c.max_iterations >= 1 and c.precond_shift >= 0):
+        raise ValueError("bad certification parameters (eta >= 0, tol_rel > 0, max_iterations >= 1, precond_shift >= 0)")
+    return c
+
+
+def check_certifiable(pose_graph, X=None) -> None:
+    """Host-side checks made before any device work: no linear term G (shared loop closures, priors), a compiled (d, r),
+    X of shape (r, (d+1) n)."""
+    r, d, n = pose_graph.r(), pose_graph.d(), pose_graph.n()
+    if len(pose_graph.sharedLoopClosures()) > 0 or len(pose_graph.priors_) > 0:
+        raise ValueError("certification is defined for a problem without a linear term G (no shared loop closures, "
+                         "no priors): certify the assembled global problem on one central handle")
+    if not L.load().dpgo_supported(d, r):
+        raise ValueError("(d, r) = (%d, %d) has no compiled kernels" % (d, r))
+    if X is not None:
+        X = np.asarray(X)
+        if X.shape != (r, (d + 1) * n):
+            raise ValueError("X has shape %s, expected (%d, %d)" % (X.shape, r, (d + 1) * n))
+
+
+def certify(problem, X, witness: bool = True, **params) -> CertificateResult:
+    """QuadraticProblem.certify: certificate of the rank-r iterate X (host matrix r x (d+1)n)."""
+    check_certifiable(problem.pose_graph_, X)
+    cp = certify_params(**params)
+    problem.refresh()
+    Xc = problem._in(X, "X")
+    n, d = problem.num_poses(), problem.dimension()
+    w = np.empty(n * (d + 1)) if witness else None
+    cr = L.CertifyResultC()
+    L.check(problem._lib.dpgo_problem_certify(problem._h, L.ptr(Xc), C.byref(cp), C.byref(cr),
+                                              L.ptr(w) if w is not None else None))
+    return CertificateResult.from_c(cr, w.reshape(n, d + 1) if w is not None else None)
+
+
+def certificate_apply(problem, X, V) -> np.ndarray:
+    """QuadraticProblem.certificateApply: V C(X) for host matrices X, V (r x (d+1)n)."""
+    check_certifiable(problem.pose_graph_, X)
+    check_certifiable(problem.pose_graph_, V)
+    problem.refresh()
+    Xc, Vc, o = problem._in(X, "X"), problem._in(V, "V"), problem._out()
+    L.check(problem._lib.dpgo_problem_certificate_apply(problem._h, L.ptr(Xc), L.ptr(Vc), L.ptr(o)))
+    return o
+
+
+@dataclass
+class CertifiedPGOResult:
+    """Outcome of solveCertifiedPGO.  status: CERTIFIED | RANK_LIMIT (a saddle at the largest compiled / allowed rank) |
+    NOT_CONVERGED (the eigen-solver's budget ended).  f: f(X) of the final rank-r iterate -- a lower bound on the PGO optimum
+    when CERTIFIED; gap = f(rounded) - f(X) >= 0: an upper bound on the suboptimality of the rounded trajectory."""
+    trajectory: np.ndarray  # d x (d+1)n, pose 0 at the origin (round_trajectory)
+    rank: int
+    status: str
+    f: float
+    f_rounded: float
+    gap: float
+    certificate: CertificateResult
+    X: np.ndarray  # the final rank-r iterate, r x (d+1)n
+    escapes: List[dict] = field(default_factory=list)  # one entry per escape: rank, lambda_min, alpha, f before / after
+
+
+def _poses_to_matrix(T: np.ndarray, r: int) -> np.ndarray:
+    """tiles [n, d+1, d] -> r x (d+1)n, the rotation block lifted by [I_d; 0]."""
+    n, b, d = T.shape
+    X = np.zeros((r, n * b), order="F")
+    X[:d, :] = T.reshape(n * b, d).T
+    return X
+
+
+def solveCertifiedPGO(measurements: RelativeSEMeasurements, r0: Optional[int] = None, r_max: Optional[int] = None,
+                      params: Optional[dict] = None, X0=None, ropt=None, grad_tol: float = 1e-9, max_solves: int = 50,
+                      device: int = 0) -> CertifiedPGOResult:
+    """SE-Sync's Riemannian staircase for one robot's pose graph (measurements of robot 0 only).
+
+    r0: first rank (default d); r_max: last rank (default: the largest compiled one); params: certify() keyword arguments;
+    X0: initial poses as tiles [n, d+1, d] or an r0 x (d+1)n matrix (default: chordal initialisation); ropt: the
+    ROptParameters of the solves at every rank (default: RTR to |rgrad| <= grad_tol, repeated up to max_solves times)."""
+    from .solver import PoseGraph, QuadraticOptimizer, QuadraticProblem, ROptParameters
+    from .trajectory import round_trajectory
+
+    d = measurements.d
+    n = int(max(int(np.max(measurements.p1)), int(np.max(measurements.p2)))) + 1 if len(measurements) else 0
+    r0 = d if r0 is None else int(r0)
+    lib = L.load()
+    if r0 < d or not lib.dpgo_supported(d, r0):
+        raise ValueError("r0 = %d: need d <= r0 and a compiled (d, r0)" % r0)
+    if r_max is None:
+        r_max = r0
+        while lib.dpgo_supported(d, r_max + 1):
+            r_max += 1
+    if np.any(measurements.r1 != measurements.r2):
+        raise ValueError("solveCertifiedPGO takes the measurements of one pose graph (no inter-robot edges)")
+    params = dict(params or {})
+    if ropt is None:
+        ropt = ROptParameters(gradnorm_tol=grad_tol, RTR_iterations=50, RTR_tCG_iterations=100)
+    if X0 is None:
+        from .initialization import chordal_initialization
+        X = _poses_to_matrix(chordal_initialization(measurements, n, device=device), r0)
+    else:
+        X0 = np.asarray(X0, dtype=np.float64)
+        X = _poses_to_matrix(X0, r0) if X0.ndim == 3 else np.asfortranarray(X0)
+
+    import torch
+    r = r0
+    escapes: List[dict] = []
+    while True:
+        pg = PoseGraph(0, r, d)
+        pg.setMeasurements(measurements)
+        problem = QuadraticProblem(pg, device=device)
+        opt = QuadraticOptimizer(problem, ropt)
+        for _ in range(max_solves):
+            X = opt.optimize(X)
+            if opt.getOptResult().gradNormOpt <= ropt.gradnorm_tol:
+                break
+        cert = problem.certify(X, **params)
+        if cert.status == "CERTIFIED":
+            status = "CERTIFIED"
+            break
+        if cert.status == "NOT_CONVERGED":
+            status = "NOT_CONVERGED"
+            break
+        if r + 1 > r_max or not lib.dpgo_supported(d, r + 1):
+            status = "RANK_LIMIT"
+            break
+        # escape the saddle: rank r + 1 along e_{r+1} w^T
+        pg_next = PoseGraph(0, r + 1, d)
+        pg_next.setMeasurements(measurements)
+        problem_next = QuadraticProblem(pg_next, device=device)
+        dev = torch.device("cuda", device)
+        X_dev = torch.from_numpy(np.ascontiguousarray(np.asfortranarray(X).T)).to(dev)
+        w_dev = torch.from_numpy(np.ascontiguousarray(cert.witness.reshape(-1))).to(dev)
+        Xn_dev = torch.empty((n * (d + 1), r + 1), dtype=torch.float64, device=dev)
+        torch.cuda.synchronize(dev)
+        alpha = C.c_double(0.0)
+        L.check(lib.dpgo_certify_escape_device(problem_next._h, r, L.ptr(X_dev), L.ptr(w_dev), float(ropt.gradnorm_tol),
+                                               L.ptr(Xn_dev), C.byref(alpha)))
+        f_before = problem.f(X)
+        X = np.asfortranarray(Xn_dev.cpu().numpy().T)
+        escapes.append(dict(rank=r, lambda_min=cert.lambda_min, gradnorm=cert.gradnorm, alpha=alpha.value,
+                            f_before=f_before, f_after=problem_next.f(X)))
+        r += 1
+    f = problem.f(X)
+    T = round_trajectory(X, r, d, device=device)
+    Xr = np.zeros((r, T.shape[1]), order="F")
+    Xr[:d, :] = T
+    f_rounded = problem.f(Xr)
+    return CertifiedPGOResult(T, r, status, f, f_rounded, f_rounded - f, cert, X, escapes)

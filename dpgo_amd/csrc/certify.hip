@@ -1,0 +1,691 @@
+// certify.hip -- certificate of global optimality of a rank-r iterate (SE-Sync / DC2-PGO verification) and the
+// Riemannian-staircase escape along its witness.  DESIGN.md section 10.
+//
+// C(X) = Q - Lambda(X), Lambda = blockdiag(Lambda_i), Lambda_i = [sym(Y_i^T (XQ)_rot,i) 0; 0 0].  The smallest eigenvalue of
+// C on the complement of the known null space Z (rows of X, translation indicator) is found by a preconditioned block
+// LOBPCG whose block is one r-row tile vector (the handle's compiled (d, r) instance): products with C, Gram blocks and
+// per-pose linear combinations run on the device (kernels/certify.h); only the r x r Gram blocks and the coefficient
+// matrices of the 3r x 3r Rayleigh-Ritz problem cross PCIe.
+#include "host.h"
+
+namespace dpgo_host {
+namespace {
+
+// ---------------------------------------------------------------- small dense linear algebra (row-major n x n)
+// Cholesky A = L L^T in place (lower triangle); false if a pivot is not positive
+bool cholesky(std::vector<double>& A, int n) {
+  for (int j = 0; j < n; ++j) {
+    double s = A[j * n + j];
+    for (int k = 0; k < j; ++k) s -= A[j * n + k] * A[j * n + k];
+    if (!(s > 0.0)) return false;
+    const double l = std::sqrt(s);
+    A[j * n + j] = l;
+    for (int i = j + 1; i < n; ++i) {
+      double t = A[i * n + j];
+      for (int k = 0; k < j; ++k) t -= A[i * n + k] * A[j * n + k];
+      A[i * n + j] = t / l;
+    }
+    for (int k = j + 1; k < n; ++k) A[j * n + k] = 0.0;
+  }
+  return true;
+}
+
+// symmetric eigen-decomposition by cyclic Jacobi: ascending eigenvalues w, eigenvectors in the COLUMNS of V
+void jacobi_eig(std::vector<double> A, int n, std::vector<double>& w, std::vector<double>& V) {
+  V.assign((size_t)n * n, 0.0);
+  for (int i = 0; i < n; ++i) V[i * n + i] = 1.0;
+  for (int sweep = 0; sweep < 100; ++sweep) {
+    double off = 0.0, tot = 0.0;
+    for (int i = 0; i < n; ++i)
+      for (int j = 0; j < n; ++j) (i == j ? tot : off) += A[i * n + j] * A[i * n + j];
+    if (off <= 1e-32 * (tot + off) || off == 0.0) break;
+    for (int p = 0; p < n - 1; ++p)
+      for (int q = p + 1; q < n; ++q) {
+        const double apq = A[p * n + q];
+        if (apq == 0.0) continue;
+        const double theta = (A[q * n + q] - A[p * n + p]) / (2.0 * apq);
+        const double t = (theta >= 0 ? 1.0 : -1.0) / (std::fabs(theta) + std::sqrt(theta * theta + 1.0));
+        const double c = 1.0 / std::sqrt(t * t + 1.0), s = t * c;
+        for (int k = 0; k < n; ++k) {  // A <- A J
+          const double akp = A[k * n + p], akq = A[k * n + q];
+          A[k * n + p] = c * akp - s * akq;
+          A[k * n + q] = s * akp + c * akq;
+        }
+        for (int k = 0; k < n; ++k) {  // A <- J^T A
+          const double apk = A[p * n + k], aqk = A[q * n + k];
+          A[p * n + k] = c * apk - s * aqk;
+          A[q * n + k] = s * apk + c * aqk;
+        }
+        for (int k = 0; k < n; ++k) {
+          const double vkp = V[k * n + p], vkq = V[k * n + q];
+          V[k * n + p] = c * vkp - s * vkq;
+          V[k * n + q] = s * vkp + c * vkq;
+        }
+      }
+  }
+  std::vector<int> ord(n);
+  for (int i = 0; i < n; ++i) ord[i] = i;
+  std::stable_sort(ord.begin(), ord.end(), [&](int a, int b) { return A[a * n + a] < A[b * n + b]; });
+  w.resize(n);
+  std::vector<double> Vs((size_t)n * n);
+  for (int j = 0; j < n; ++j) {
+    w[j] = A[ord[j] * n + ord[j]];
+    for (int i = 0; i < n; ++i) Vs[i * n + j] = V[i * n + ord[j]];
+  }
+  V.swap(Vs);
+}
+
+// X = L^-T Y for lower-triangular L (n x n) and Y (n x m), in place
+void solve_lt(const std::vector<double>& Lm, int n, std::vector<double>& Y, int m) {
+  for (int i = n - 1; i >= 0; --i)
+    for (int j = 0; j < m; ++j) {
+      double s = Y[i * m + j];
+      for (int k = i + 1; k < n; ++k) s -= Lm[k * n + i] * Y[k * m + j];
+      Y[i * m + j] = s / Lm[i * n + i];
+    }
+}
+
+// ---------------------------------------------------------------- the solver's device state
+struct Cert {
+  dpgo_problem_s* p;
+  int d, r, n;
+  bool sym = false;     // products read the symmetric copy of Q
+  double* S = nullptr;  // Lambda blocks at X (k_grad)
+  double* zero = nullptr;  // a zero iterate: the multilevel cycle's projection at it is the identity
+  double* part = nullptr;  // per-workgroup partials
+  double* red = nullptr;   // reduced Gram blocks (device)
+  double* coef = nullptr;  // coefficient matrices of k_cert_combine (device)
+  double* hbuf = nullptr;  // pinned: reduced Gram blocks (host)
+  double* hcoef = nullptr; // pinned: coefficient ring
+  int coef_slot = 0;
+  int products = 0;
+  int precond = DPGO_PRECOND_NONE;
+  double shift = 0.1;
+  TmpDev tmp;
+  static constexpr int kCoefSlots = 8;
+  static constexpr int kCoefCap = kCertMaxOut * kCertMaxBlocks * 36;
+  static constexpr int kGramWg = 512;  // workgroups of k_cert_gram (partials: kGramWg x kCertMaxPairs x 36)
+
+  ~Cert() {
+    if (hbuf) (void)hipHostFree(hbuf);
+    if (hcoef) (void)hipHostFree(hcoef);
+  }
+  size_t vec_bytes() const { return (size_t)n * (d + 1) * r * sizeof(double); }
+  int flat_grid() const {
+    const size_t cols = (size_t)n * (d + 1);
+    return (int)std::max<size_t>(1, std::min<size_t>(kMaxGrid, (cols + kBlock - 1) / kBlock));
+  }
+  int vec(double** out) {
+    CHK(tmp.alloc(out, vec_bytes()));
+    return DPGO_OK;
+  }
+  int init() {
+    CHK(tmp.alloc(&S, sizeof(double) * (size_t)n * d * d));
+    CHK(tmp.alloc(&part, sizeof(double) * (size_t)std::max(kPartialCap * 36, kGramWg * kCertMaxPairs * 36)));
+    CHK(tmp.alloc(&red, sizeof(double) * kCertMaxPairs * 36));
+    CHK(tmp.alloc(&coef, sizeof(double) * kCoefSlots * kCoefCap));
+    HIPC(hipHostMalloc(&hbuf, sizeof(double) * kCertMaxPairs * 36, hipHostMallocDefault));
+    HIPC(hipHostMalloc(&hcoef, sizeof(double) * kCoefSlots * kCoefCap, hipHostMallocDefault));
+    return DPGO_OK;
+  }
+
+  // CW = W C(X); with wcw != null also W CW^T (r x r, row-major) on the host
+  int apply(const double* W, double* CW, std::vector<double>* wcw = nullptr) {
+    int g = 0;
+    if (sym) {
+      g = p->grid_outer_sym();
+      DISPATCH(d, r, hipLaunchKernelGGL((k_cert_apply<D, R, 1, BsrSymDev>), dim3(g), dim3(kBlock), 0, p->stream,
+                                        p->sym.dev(), S, W, CW, part, n));
+    } else {
+      g = p->grid_s();
+      DISPATCH(d, r, LAUNCH_SPLIT(p, k_cert_apply, g, p->Q.dev(), S, W, CW, part, n));
+    }
+    HIPC(hipGetLastError());
+    ++products;
+    if (wcw) CHK(reduce(g, r * r, *wcw));
+    return DPGO_OK;
+  }
+  int reduce(int nwg, int E, std::vector<double>& out) {
+    hipLaunchKernelGGL(k_cert_reduce, dim3((E + kBlock - 1) / kBlock), dim3(kBlock), 0, p->stream, part, nwg, E, red);
+    HIPC(hipGetLastError());
+    HIPC(hipMemcpyAsync(hbuf, red, sizeof(double) * E, hipMemcpyDeviceToHost, p->stream));
+    HIPC(hipStreamSynchronize(p->stream));
+    out.assign(hbuf, hbuf + E);
+    return DPGO_OK;
+  }
+  // G[k] = B[x_k] B[y_k]^T for every pair k (r x r blocks, row-major, concatenated)
+  int gram(const std::vector<const double*>& B, const std::vector<std::pair<int, int>>& pairs, std::vector<double>& G) {
+    if (B.size() > (size_t)kCertMaxBlocks || pairs.size() > (size_t)kCertMaxPairs || pairs.empty())
+      return fail(DPGO_ERR_INVALID, "certify: Gram pass too large");
+    CertIn in{};
+    CertPairs pr{};
+    for (size_t j = 0; j < B.size(); ++j) in.b[j] = B[j];
+    for (size_t k = 0; k < pairs.size(); ++k) {
+      pr.x[k] = (int8_t)pairs[k].first;
+      pr.y[k] = (int8_t)pairs[k].second;
+    }
+    const size_t chunks = ((size_t)n * (d + 1) + kCertCols - 1) / kCertCols;
+    const int g = (int)std::max<size_t>(1, std::min<size_t>(kGramWg, chunks));
+    const int nb = (int)B.size(), np = (int)pairs.size();
+    DISPATCH(d, r, hipLaunchKernelGGL((k_cert_gram<D, R, kCertMaxBlocks>), dim3(g), dim3(kBlock), 0, p->stream, in, nb, pr,
+                                      np, part, n));
+    HIPC(hipGetLastError());
+    return reduce(g, np * r * r, G);
+  }
+  // out_k = sum_j M[k][j]^T B_j; M: [nout][nb][r][r] row-major
+  int combine(const std::vector<const double*>& B, const std::vector<double*>& out, const std::vector<double>& M) {
+    if (B.size() > (size_t)kCertMaxBlocks || out.size() > (size_t)kCertMaxOut ||
+        M.size() != out.size() * B.size() * r * r)
+      return fail(DPGO_ERR_INVALID, "certify: combination too large");
+    CertIn in{};
+    CertOut o{};
+    for (size_t j = 0; j < B.size(); ++j) in.b[j] = B[j];
+    for (size_t k = 0; k < out.size(); ++k) o.b[k] = out[k];
+    double* h = hcoef + (size_t)coef_slot * kCoefCap;
+    double* dv = coef + (size_t)coef_slot * kCoefCap;
+    coef_slot = (coef_slot + 1) % kCoefSlots;  // (the stream is synchronised by every Gram read-back, several per ring turn)
+    std::copy(M.begin(), M.end(), h);
+    HIPC(hipMemcpyAsync(dv, h, sizeof(double) * M.size(), hipMemcpyHostToDevice, p->stream));
+    const int nb = (int)B.size(), nout = (int)out.size();
+    DISPATCH(d, r, hipLaunchKernelGGL((k_cert_combine<D, R, kCertMaxBlocks>), dim3(flat_grid()), dim3(kBlock), 0,
+                                      p->stream, in, nb, o, nout, (const double*)dv, n));
+    HIPC(hipGetLastError());
+    return DPGO_OK;
+  }
+  // Z = M^-1 V without tangent projection
+  int precondition(const double* V, double* Z) {
+    if (precond == DPGO_PRECOND_BLOCK_JACOBI) {
+      DISPATCH(d, r, hipLaunchKernelGGL((k_cert_jacobi<D, R>), dim3(p->grid()), dim3(kBlock), 0, p->stream, V, p->dinv, Z, n));
+      HIPC(hipGetLastError());
+    } else if (precond == DPGO_PRECOND_MULTILEVEL) {
+      CHK(launch_ml_apply(p, zero, V, Z));
+    } else {
+      HIPC(hipMemcpyAsync(Z, V, vec_bytes(), hipMemcpyDeviceToDevice, p->stream));
+    }
+    return DPGO_OK;
+  }
+};
+
+// r x r identity / diagonal helpers of the coefficient matrices
+void put_block(std::vector<double>& M, int nb, int r, int k, int j, const std::vector<double>& blk) {
+  std::copy(blk.begin(), blk.end(), M.begin() + ((size_t)k * nb + j) * r * r);
+}
+std::vector<double> eye(int r, double s = 1.0) {
+  std::vector<double> I((size_t)r * r, 0.0);
+  for (int a = 0; a < r; ++a) I[a * r + a] = s;
+  return I;
+}
+
+// max_i max diag(Q_ii)
+int q_scale(dpgo_problem_s* p, TmpDev& tmp, double* out) {
+  const int g = (p->n + kBlock - 1) / kBlock;
+  double* dv = nullptr;
+  CHK(tmp.alloc(&dv, sizeof(double) * g));
+  if (p->d == 2)
+    hipLaunchKernelGGL(k_cert_scale<2>, dim3(g), dim3(kBlock), 0, p->stream, p->Q.dev(), dv, p->n);
+  else
+    hipLaunchKernelGGL(k_cert_scale<3>, dim3(g), dim3(kBlock), 0, p->stream, p->Q.dev(), dv, p->n);
+  HIPC(hipGetLastError());
+  std::vector<double> h(g);
+  HIPC(hipMemcpyAsync(h.data(), dv, sizeof(double) * g, hipMemcpyDeviceToHost, p->stream));
+  HIPC(hipStreamSynchronize(p->stream));
+  double m = 0.0;
+  for (double v : h) m = std::max(m, v);
+  *out = m;
+  return DPGO_OK;
+}
+
+int certify_impl(dpgo_problem_s* p, const double* X, const dpgo_certify_params* prm_in, dpgo_certify_result* res,
+                 double* witness, bool witness_on_host) {
+  const auto t0 = std::chrono::steady_clock::now();
+  CHK(check_ready(p));
+  if (!X || !res) return fail(DPGO_ERR_INVALID, "null pointer");
+  if (p->has_G || p->C.nnzb > 0)
+    return fail(DPGO_ERR_INVALID, "certification is defined for a problem without a linear term G (global / central problem)");
+  dpgo_certify_params prm;
+  if (prm_in)
+    prm = *prm_in;
+  else
+    dpgo_certify_params_default(&prm);
+  if (!(prm.eta >= 0.0) || !(prm.tol_rel > 0.0) || prm.max_iterations < 1 || !(prm.precond_shift >= 0.0))
+    return fail(DPGO_ERR_INVALID, "certify: bad parameters");
+  int precond = prm.precond;
+  if (precond == DPGO_PRECOND_AUTO) {
+    p->auto_decide();
+    precond = p->auto_ml ? DPGO_PRECOND_MULTILEVEL : DPGO_PRECOND_BLOCK_JACOBI;
+  }
+  if (precond == DPGO_PRECOND_ADDITIVE) precond = DPGO_PRECOND_MULTILEVEL;  // (the additive form lives inside the one-launch solve only)
+  if (precond < DPGO_PRECOND_NONE || precond > DPGO_PRECOND_MULTILEVEL) return fail(DPGO_ERR_INVALID, "unknown preconditioner");
+  *res = dpgo_certify_result{};
+  res->status = DPGO_CERT_NOT_CONVERGED;
+
+  Cert c;
+  c.p = p;
+  c.d = p->d;
+  c.r = p->r;
+  c.n = p->n;
+  c.precond = precond;
+  c.shift = prm.precond_shift;
+  CHK(c.init());
+  const int r = c.r;
+  if (p->sym_wanted() && p->split == 1) {
+    bool usable = false;
+    CHK(sym_ensure(p, &usable));
+    c.sym = usable;
+  }
+  // Lambda at X (and f, |rgrad| on the way)
+  CHK(launch_grad(p, X, nullptr, c.S, nullptr, nullptr, c.sym));
+  CHK(launch_rtr_begin(p, 0.0, 1.0, 1.0, 0, 0));
+  CHK(poll_state(p));
+  res->gradnorm = p->hstate->ngf;
+  double scale = 0.0;
+  CHK(q_scale(p, c.tmp, &scale));
+  if (!(scale > 0.0)) return fail(DPGO_ERR_INVALID, "certify: Q has no positive diagonal");
+  res->scale = scale;
+  const double eta = prm.eta * scale, tol = prm.tol_rel * scale;
+  const double null_tol = std::sqrt(prm.tol_rel) * scale;  // a candidate direction z is null when |C z| <= this
+  if (precond == DPGO_PRECOND_BLOCK_JACOBI) CHK(build_dinv(p, prm.precond_shift));
+  if (precond == DPGO_PRECOND_MULTILEVEL) {
+    CHK(ml_ensure(p, prm.precond_shift));
+    CHK(ml_ops32_ensure(p));
+    CHK(c.tmp.alloc(&c.zero, c.vec_bytes()));
+    HIPC(hipMemsetAsync(c.zero, 0, c.vec_bytes(), p->stream));
+  }
+
+  // ---- deflation space: rows of X and the translation indicator, kept where one product confirms them null
+  double *K1, *CK0, *CK1, *Z0, *Z1;
+  CHK(c.vec(&K1));
+  CHK(c.vec(&CK0));
+  CHK(c.vec(&CK1));
+  CHK(c.vec(&Z0));
+  CHK(c.vec(&Z1));
+  DISPATCH(c.d, r, hipLaunchKernelGGL((k_cert_indicator<D, R>), dim3(c.flat_grid()), dim3(kBlock), 0, p->stream, K1, c.n));
+  HIPC(hipGetLastError());
+  CHK(c.apply(X, CK0));
+  CHK(c.apply(K1, CK1));
+  const int m0 = 2 * r;
+  std::vector<double> Gk((size_t)m0 * m0), Gc((size_t)m0 * m0);
+  {
+    std::vector<double> G;
+    CHK(c.gram({X, K1, CK0, CK1}, {{0, 0}, {0, 1}, {1, 1}, {2, 2}, {2, 3}, {3, 3}}, G));
+    auto fill = [&](std::vector<double>& M, int base) {
+      const int blk[2][2] = {{0, 1}, {1, 2}};
+      for (int bx = 0; bx < 2; ++bx)
+        for (int by = 0; by < 2; ++by)
+          for (int a = 0; a < r; ++a)
+            for (int b = 0; b < r; ++b) {
+              const int k = base + blk[bx][by];
+              const double v = (bx <= by) ? G[(size_t)k * r * r + a * r + b] : G[(size_t)k * r * r + b * r + a];
+              M[(size_t)(bx * r + a) * m0 + by * r + b] = v;
+            }
+    };
+    fill(Gk, 0);
+    fill(Gc, 3);
+  }
+  std::vector<double> sk, Uk;
+  jacobi_eig(Gk, m0, sk, Uk);
+  const double smax = std::max(sk.back(), 0.0);
+  std::vector<int> keep;
+  for (int i = 0; i < m0; ++i)
+    if (sk[i] > 1e-10 * smax) keep.push_back(i);
+  const int m1 = (int)keep.size();
+  // orthonormal basis B^T K of span(K), B = U_keep diag(s^-1/2): m0 x m1
+  std::vector<double> Bm((size_t)m0 * m1);
+  for (int i = 0; i < m0; ++i)
+    for (int j = 0; j < m1; ++j) Bm[(size_t)i * m1 + j] = Uk[(size_t)i * m0 + keep[j]] / std::sqrt(sk[keep[j]]);
+  // |C z|^2 on that basis: B^T Gc B, and its near-null eigen-directions
+  std::vector<double> H((size_t)m1 * m1, 0.0);
+  for (int i = 0; i < m1; ++i)
+    for (int j = 0; j < m1; ++j) {
+      double s = 0.0;
+      for (int a = 0; a < m0; ++a)
+        for (int b = 0; b < m0; ++b) s += Bm[(size_t)a * m1 + i] * Gc[(size_t)a * m0 + b] * Bm[(size_t)b * m1 + j];
+      H[(size_t)i * m1 + j] = s;
+    }
+  std::vector<double> mu, Vh;
+  if (m1 > 0) jacobi_eig(H, m1, mu, Vh);
+  int mz = 0;
+  double cz = 0.0;
+  for (int i = 0; i < m1; ++i)
+    if (std::sqrt(std::max(mu[i], 0.0)) <= null_tol) {
+      ++mz;
+      cz = std::max(cz, std::sqrt(std::max(mu[i], 0.0)));
+    }
+  mz = std::min(mz, 2 * r);
+  res->deflated = mz;
+  res->deflation_residual = cz;
+  const int nzb = (mz + r - 1) / r;  // Z blocks (rows beyond mz are zero)
+  if (nzb > 0) {
+    // Z rows = (B V_keep)^T K: coefficient of K row a (block j = a / r) for Z row q (block k = q / r)
+    std::vector<double> M((size_t)2 * 2 * r * r, 0.0);
+    for (int q = 0; q < mz; ++q)
+      for (int a = 0; a < m0; ++a) {
+        double s = 0.0;
+        for (int j = 0; j < m1; ++j) s += Bm[(size_t)a * m1 + j] * Vh[(size_t)j * m1 + q];
+        const int k = q / r, bq = q % r, jb = a / r, ar = a % r;
+        M[((size_t)k * 2 + jb) * r * r + ar * r + bq] = s;
+      }
+    CHK(c.combine({X, K1}, {Z0, Z1}, M));
+  }
+  std::vector<const double*> Zb;
+  if (nzb >= 1) Zb.push_back(Z0);
+  if (nzb >= 2) Zb.push_back(Z1);
+
+  // ---- block LOBPCG on the complement of Z
+  double *W, *T, *P, *CW, *CT, *CP, *W2, *P2, *CW2, *CP2, *Rs;
+  for (double** v : {&W, &T, &P, &CW, &CT, &CP, &W2, &P2, &CW2, &CP2, &Rs}) CHK(c.vec(v));
+  DISPATCH(c.d, r, hipLaunchKernelGGL((k_cert_random<D, R>), dim3(c.flat_grid()), dim3(kBlock), 0, p->stream,
+                                      (unsigned long long)prm.seed, W, c.n));
+  HIPC(hipGetLastError());
+  // V <- V - (V Z^T) Z - (V U^T) U for orthonormal Z blocks and (optionally) an orthonormal block U; into `out`
+  auto project = [&](const double* V, const double* U, double* out) -> int {
+    std::vector<const double*> B{V};
+    std::vector<std::pair<int, int>> pairs;
+    for (const double* z : Zb) {
+      pairs.push_back({0, (int)B.size()});
+      B.push_back(z);
+    }
+    if (U) {
+      pairs.push_back({0, (int)B.size()});
+      B.push_back(U);
+    }
+    if (pairs.empty()) {
+      if (out != V) HIPC(hipMemcpyAsync(out, V, c.vec_bytes(), hipMemcpyDeviceToDevice, p->stream));
+      return DPGO_OK;
+    }
+    std::vector<double> G;
+    CHK(c.gram(B, pairs, G));
+    const int nb = (int)B.size();
+    std::vector<double> M((size_t)nb * r * r, 0.0);
+    put_block(M, nb, r, 0, 0, eye(r));
+    // out row b = v_b - sum_q G[b][q] z_q: coefficient of z_q (row a = q of block j) for output row b is -G[b][a]
+    for (int j = 1; j < nb; ++j)
+      for (int a = 0; a < r; ++a)
+        for (int b = 0; b < r; ++b) M[(size_t)j * r * r + a * r + b] = -G[(size_t)(j - 1) * r * r + b * r + a];
+    return c.combine(B, {out}, M);
+  };
+  // W <- Ritz vectors of W (orthonormalised against itself, rotated to diagonalise W C W^T); theta ascending
+  std::vector<double> theta(r, 0.0);
+  {
+    CHK(project(W, nullptr, W2));
+    std::vector<double> G;
+    CHK(c.gram({W2}, {{0, 0}}, G));
+    for (int a = 0; a < r; ++a) G[a * r + a] += 1e-300;
+    if (!cholesky(G, r)) return fail(DPGO_ERR_STATE, "certify: start block is rank deficient");
+    std::vector<double> Y = eye(r);
+    solve_lt(G, r, Y, r);  // W = L^-1 W2 -> coefficient (row b of W gets sum_a Linv[b][a] w2_a): M[a][b] = Y[a][b]
+    CHK(c.combine({W2}, {W}, Y));
+    CHK(c.apply(W, CW));
+    std::vector<double> H;
+    CHK(c.gram({W, CW}, {{0, 1}}, H));
+    for (int a = 0; a < r; ++a)
+      for (int b = 0; b < a; ++b) H[a * r + b] = H[b * r + a] = 0.5 * (H[a * r + b] + H[b * r + a]);
+    std::vector<double> w, V;
+    jacobi_eig(H, r, w, V);
+    CHK(c.combine({W, CW}, {W2, CW2}, [&] {
+      std::vector<double> M((size_t)2 * 2 * r * r, 0.0);
+      put_block(M, 2, r, 0, 0, V);
+      put_block(M, 2, r, 1, 1, V);
+      return M;
+    }()));
+    std::swap(W, W2);
+    std::swap(CW, CW2);
+    theta = w;
+  }
+  bool have_p = false, negative = false;
+  double resid0 = 0.0;
+  int it = 0;
+  for (; it < prm.max_iterations; ++it) {
+    // residual block Rs = CW - diag(theta) W and its row norms
+    {
+      std::vector<double> M((size_t)2 * r * r, 0.0);
+      put_block(M, 2, r, 0, 0, eye(r));
+      for (int a = 0; a < r; ++a) M[(size_t)r * r + a * r + a] = -theta[a];
+      CHK(c.combine({CW, W}, {Rs}, M));
+    }
+    std::vector<double> G;
+    CHK(c.gram({Rs}, {{0, 0}}, G));
+    resid0 = std::sqrt(std::max(G[0], 0.0));
+    if (theta[0] < -eta) negative = true;
+    if (resid0 <= tol) break;
+    // T = M^-1 Rs, orthogonal to Z and W
+    CHK(c.precondition(Rs, T));
+    CHK(project(T, W, T));
+    CHK(c.apply(T, CT));
+    // Rayleigh-Ritz on S = [W, T, P]
+    const int ns = have_p ? 3 : 2, m = ns * r;
+    std::vector<const double*> Sb{W, T, P}, CSb{CW, CT, CP};
+    std::vector<const double*> B;
+    std::vector<std::pair<int, int>> pairs;
+    for (int j = 0; j < ns; ++j) B.push_back(Sb[j]);
+    for (int j = 0; j < ns; ++j) B.push_back(CSb[j]);
+    for (int i = 0; i < ns; ++i)
+      for (int j = i; j < ns; ++j) pairs.push_back({i, j});
+    for (int i = 0; i < ns; ++i)
+      for (int j = i; j < ns; ++j) pairs.push_back({i, ns + j});
+    std::vector<double> Gr;
+    CHK(c.gram(B, pairs, Gr));
+    std::vector<double> Gs((size_t)m * m), Hs((size_t)m * m);
+    {
+      int k = 0;
+      for (int pass = 0; pass < 2; ++pass) {
+        std::vector<double>& M = pass == 0 ? Gs : Hs;
+        for (int i = 0; i < ns; ++i)
+          for (int j = i; j < ns; ++j, ++k)
+            for (int a = 0; a < r; ++a)
+              for (int b = 0; b < r; ++b) {
+                const double v = Gr[(size_t)k * r * r + a * r + b];
+                M[(size_t)(i * r + a) * m + j * r + b] = v;
+                M[(size_t)(j * r + b) * m + i * r + a] = v;
+              }
+      }
+      for (int i = 0; i < m; ++i)  // (C symmetric: average the two computed halves of the diagonal blocks)
+        for (int j = 0; j < i; ++j) Hs[(size_t)i * m + j] = Hs[(size_t)j * m + i] = 0.5 * (Hs[(size_t)i * m + j] + Hs[(size_t)j * m + i]);
+    }
+    // Jacobi scaling, Cholesky of the Gram matrix; a (near) dependent P is dropped and the step repeated without it
+    std::vector<double> dsc(m);
+    for (int i = 0; i < m; ++i) dsc[i] = Gs[(size_t)i * m + i] > 0 ? 1.0 / std::sqrt(Gs[(size_t)i * m + i]) : 0.0;
+    std::vector<double> Lm(Gs);
+    for (int i = 0; i < m; ++i)
+      for (int j = 0; j < m; ++j) Lm[(size_t)i * m + j] *= dsc[i] * dsc[j];
+    bool okc = cholesky(Lm, m);
+    if (okc) {
+      double dmin = INFINITY, dmax = 0.0;
+      for (int i = 0; i < m; ++i) dmin = std::min(dmin, Lm[(size_t)i * m + i]), dmax = std::max(dmax, Lm[(size_t)i * m + i]);
+      okc = dmin > 1e-7 * dmax;
+    }
+    if (!okc) {
+      if (have_p) {
+        have_p = false;
+        --it;
+        continue;
+      }
+      break;  // T depends on W: the iteration has stagnated
+    }
+    // A = L^-1 (D Hs D) L^-T; eigenvectors V; coefficients Y = D L^-T V[:, :r]
+    std::vector<double> A((size_t)m * m);
+    for (int i = 0; i < m; ++i)
+      for (int j = 0; j < m; ++j) A[(size_t)i * m + j] = Hs[(size_t)i * m + j] * dsc[i] * dsc[j];
+    // A <- L^-1 A (forward substitution on columns), then A <- A L^-T
+    for (int j = 0; j < m; ++j)
+      for (int i = 0; i < m; ++i) {
+        double s = A[(size_t)i * m + j];
+        for (int k = 0; k < i; ++k) s -= Lm[(size_t)i * m + k] * A[(size_t)k * m + j];
+        A[(size_t)i * m + j] = s / Lm[(size_t)i * m + i];
+      }
+    for (int i = 0; i < m; ++i)
+      for (int j = 0; j < m; ++j) {
+        double s = A[(size_t)i * m + j];
+        for (int k = 0; k < j; ++k) s -= A[(size_t)i * m + k] * Lm[(size_t)j * m + k];
+        A[(size_t)i * m + j] = s / Lm[(size_t)j * m + j];
+      }
+    for (int i = 0; i < m; ++i)
+      for (int j = 0; j < i; ++j) A[(size_t)i * m + j] = A[(size_t)j * m + i] = 0.5 * (A[(size_t)i * m + j] + A[(size_t)j * m + i]);
+    std::vector<double> w, V;
+    jacobi_eig(A, m, w, V);
+    std::vector<double> Y((size_t)m * r);
+    for (int i = 0; i < m; ++i)
+      for (int j = 0; j < r; ++j) Y[(size_t)i * r + j] = V[(size_t)i * m + j];
+    solve_lt(Lm, m, Y, r);
+    for (int i = 0; i < m; ++i)
+      for (int j = 0; j < r; ++j) Y[(size_t)i * r + j] *= dsc[i];
+    // W' = S Y, P' = [T P] Y_TP, CW' = CS Y, CP' = [CT CP] Y_TP   (inputs W T P CW CT CP)
+    {
+      const int nb = 2 * ns;
+      std::vector<double> M((size_t)4 * nb * r * r, 0.0);
+      for (int j = 0; j < ns; ++j)
+        for (int a = 0; a < r; ++a)
+          for (int b = 0; b < r; ++b) {
+            const double y = Y[(size_t)(j * r + a) * r + b];
+            M[((size_t)0 * nb + j) * r * r + a * r + b] = y;
+            M[((size_t)2 * nb + ns + j) * r * r + a * r + b] = y;
+            if (j > 0) {
+              M[((size_t)1 * nb + j) * r * r + a * r + b] = y;
+              M[((size_t)3 * nb + ns + j) * r * r + a * r + b] = y;
+            }
+          }
+      CHK(c.combine(B, {W2, P2, CW2, CP2}, M));
+    }
+    std::swap(W, W2);
+    std::swap(P, P2);
+    std::swap(CW, CW2);
+    std::swap(CP, CP2);
+    have_p = true;
+    for (int a = 0; a < r; ++a) theta[a] = w[a];
+  }
+  const bool converged = resid0 <= tol;
+  if (theta[0] < -eta) negative = true;
+  // the reported pair: the first Ritz vector, projected onto the complement of Z once more, normalised, and its exact
+  // Rayleigh quotient
+  CHK(project(W, nullptr, W2));
+  std::vector<double> G;
+  CHK(c.gram({W2}, {{0, 0}}, G));
+  {
+    std::vector<double> M((size_t)r * r, 0.0);
+    for (int a = 0; a < r; ++a) M[a * r + a] = G[a * r + a] > 0 ? 1.0 / std::sqrt(G[a * r + a]) : 0.0;
+    CHK(c.combine({W2}, {W}, M));
+  }
+  std::vector<double> wcw;
+  CHK(c.apply(W, CW, &wcw));
+  res->lambda_min = wcw[0];
+  res->residual = resid0;
+  res->iterations = it;
+  res->products = c.products;
+  if (res->lambda_min < -eta || negative)
+    res->status = DPGO_CERT_NOT_CERTIFIED;
+  else if (converged)
+    res->status = DPGO_CERT_CERTIFIED;
+  else
+    res->status = DPGO_CERT_NOT_CONVERGED;
+  if (witness) {
+    const size_t ncol = (size_t)c.n * (c.d + 1);
+    HIPC(hipMemcpy2DAsync(witness, sizeof(double), W, sizeof(double) * r, sizeof(double), ncol,
+                          witness_on_host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, p->stream));
+  }
+  HIPC(hipStreamSynchronize(p->stream));
+  res->elapsedMs = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  return DPGO_OK;
+}
+
+}  // namespace
+}  // namespace dpgo_host
+
+extern "C" {
+
+void dpgo_certify_params_default(dpgo_certify_params* p) {
+  if (!p) return;
+  p->eta = 1e-6;
+  p->tol_rel = 1e-6;
+  p->max_iterations = 1000;
+  p->precond = DPGO_PRECOND_AUTO;
+  p->precond_shift = 1e-1;
+  p->seed = 1;
+}
+
+
+int dpgo_problem_certify_device(dpgo_problem_t h, const double* X_dev, const dpgo_certify_params* params,
+                                dpgo_certify_result* result, double* witness_dev) {
+  return certify_impl(h, X_dev, params, result, witness_dev, false);
+}
+
+
+int dpgo_problem_certify(dpgo_problem_t h, const double* X_host, const dpgo_certify_params* params,
+                         dpgo_certify_result* result, double* witness_host) {
+  CHK(check_ready(h));
+  if (!X_host) return fail(DPGO_ERR_INVALID, "null X");
+  TmpDev tmp;
+  double* X = nullptr;
+  CHK(tmp.alloc(&X, h->vec_bytes()));
+  CHK(h2d(h, X, X_host));
+  return certify_impl(h, X, params, result, witness_host, true);
+}
+
+
+int dpgo_problem_certificate_apply(dpgo_problem_t h, const double* X_host, const double* V_host, double* CV_host) {
+  CHK(check_ready(h));
+  if (!X_host || !V_host || !CV_host) return fail(DPGO_ERR_INVALID, "null pointer");
+  if (h->has_G || h->C.nnzb > 0)
+    return fail(DPGO_ERR_INVALID, "the certificate matrix is defined for a problem without a linear term G");
+  TmpDev tmp;
+  double *X, *V, *CV, *S, *part;
+  CHK(tmp.alloc(&X, h->vec_bytes()));
+  CHK(tmp.alloc(&V, h->vec_bytes()));
+  CHK(tmp.alloc(&CV, h->vec_bytes()));
+  CHK(tmp.alloc(&S, sizeof(double) * (size_t)h->n * h->d * h->d));
+  CHK(tmp.alloc(&part, sizeof(double) * (size_t)kPartialCap * 36));
+  CHK(h2d(h, X, X_host));
+  CHK(h2d(h, V, V_host));
+  bool sym = false;
+  if (h->sym_wanted() && h->split == 1) CHK(sym_ensure(h, &sym));
+  CHK(launch_grad(h, X, nullptr, S, nullptr, nullptr, sym));
+  if (sym) {
+    DISPATCH(h->d, h->r, hipLaunchKernelGGL((k_cert_apply<D, R, 1, BsrSymDev>), dim3(h->grid_outer_sym()), dim3(kBlock), 0,
+                                            h->stream, h->sym.dev(), S, V, CV, part, h->n));
+  } else {
+    DISPATCH(h->d, h->r, LAUNCH_SPLIT(h, k_cert_apply, h->grid_s(), h->Q.dev(), S, V, CV, part, h->n));
+  }
+  HIPC(hipGetLastError());
+  return d2h(h, CV_host, CV);
+}
+
+
+int dpgo_certify_escape_device(dpgo_problem_t h_next, int r, const double* X_dev, const double* witness_dev,
+                               double grad_tol, double* X_next_dev, double* alpha) {
+  if (!h_next) return fail(DPGO_ERR_INVALID, "null handle");
+  if (!supported(h_next->d, r + 1)) return fail(DPGO_ERR_UNSUPPORTED, "certify: (d, r + 1) not compiled in");
+  if (h_next->r != r + 1) return fail(DPGO_ERR_INVALID, "certify: the escape handle must have rank r + 1");
+  if (!X_dev || !witness_dev || !X_next_dev) return fail(DPGO_ERR_INVALID, "null pointer");
+  if (!(grad_tol >= 0.0)) return fail(DPGO_ERR_INVALID, "certify: bad gradient tolerance");
+  CHK(check_ready(h_next));
+  dpgo_problem_s* p = h_next;
+  const int g = std::max(1, std::min(kMaxGrid, (int)(((size_t)p->n * (p->d + 1) + kBlock - 1) / kBlock)));
+  TmpDev tmp;
+  double* Xl = nullptr;
+  CHK(tmp.alloc(&Xl, p->vec_bytes()));
+  auto lift = [&](double a) -> int {
+    DISPATCH(p->d, r, hipLaunchKernelGGL((k_cert_lift<D, R>), dim3(g), dim3(kBlock), 0, p->stream, X_dev, witness_dev, a,
+                                         Xl, p->n));
+    HIPC(hipGetLastError());
+    return DPGO_OK;
+  };
+  double f0 = 0.0, gn0 = 0.0;
+  CHK(lift(0.0));
+  CHK(dpgo_problem_eval_device(p, Xl, &f0, &gn0));
+  // SE-Sync's rule: the first of alpha0, alpha0 / 2, ... whose retraction decreases f and leaves the gradient above the
+  // tolerance (the next solve must not stop at once); alpha0 moves each pose by ~0.1 for a witness spread over all poses
+  double a = 0.1 * std::sqrt((double)p->n);
+  for (int k = 0; k < 60; ++k, a *= 0.5) {
+    CHK(lift(a));
+    CHK(launch_retract(p, Xl, Xl, 0.0, X_next_dev, nullptr));
+    double f = 0.0, gn = 0.0;
+    CHK(dpgo_problem_eval_device(p, X_next_dev, &f, &gn));
+    if (f < f0 && gn > grad_tol) {
+      if (alpha) *alpha = a;
+      return DPGO_OK;
+    }
+  }
+  if (alpha) *alpha = 0.0;
+  return fail(DPGO_ERR_STATE, "certify: no step along the witness decreases f");
+}
+
+}  // extern "C"

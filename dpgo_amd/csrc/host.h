@@ -7,6 +7,7 @@
 //                   selection (DPGO_PRECOND_AUTO), concurrent / begin-end solves
 //   agents.hip      GNC re-weighting, initial guesses, manifold operations, public-pose exchange plans
 //   bench_probes.hip  kernel timing probes used by bench.py
+//   certify.hip     certificate of global optimality (LOBPCG on C(X) = Q - Lambda(X)) and the staircase escape
 #pragma once
 #include "kernels.h"
 

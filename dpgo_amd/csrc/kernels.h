@@ -31,5 +31,6 @@ namespace dpgo {
 #include "kernels/rtr.h"
 #include "kernels/agent.h"
 #include "kernels/init.h"
+#include "kernels/certify.h"
 
 }  // namespace dpgo

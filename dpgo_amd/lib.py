@@ -46,6 +46,21 @@ class RoptResultC(C.Structure):
                 ("precond_used", C.c_int)]
 
 
+class CertifyParamsC(C.Structure):
+    _fields_ = [("eta", C.c_double), ("tol_rel", C.c_double), ("max_iterations", C.c_int), ("precond", C.c_int),
+                ("precond_shift", C.c_double), ("seed", C.c_uint64)]
+
+
+class CertifyResultC(C.Structure):
+    _fields_ = [("status", C.c_int), ("lambda_min", C.c_double), ("residual", C.c_double), ("gradnorm", C.c_double),
+                ("scale", C.c_double), ("iterations", C.c_int), ("products", C.c_int), ("deflated", C.c_int),
+                ("deflation_residual", C.c_double), ("elapsedMs", C.c_double)]
+
+
+CERT_CERTIFIED, CERT_NOT_CERTIFIED, CERT_NOT_CONVERGED = 0, 1, 2
+CERT_STATUS = ["CERTIFIED", "NOT_CERTIFIED", "NOT_CONVERGED"]
+
+
 _P = C.c_void_p
 _I = C.c_int
 _D = C.c_double
@@ -160,6 +175,11 @@ SIGNATURES = {
     "dpgo_build_G_coupling": ([_I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P,
                                C.POINTER(_I), _P, _P, _P], _I),
     "dpgo_debug_reduction_primitives": ([_I, _I, _I, _P, _P, _P, _P, _P], _I),
+    "dpgo_certify_params_default": ([C.POINTER(CertifyParamsC)], None),
+    "dpgo_problem_certify": ([_P, _P, C.POINTER(CertifyParamsC), C.POINTER(CertifyResultC), _P], _I),
+    "dpgo_problem_certify_device": ([_P, _P, C.POINTER(CertifyParamsC), C.POINTER(CertifyResultC), _P], _I),
+    "dpgo_problem_certificate_apply": ([_P, _P, _P, _P], _I),
+    "dpgo_certify_escape_device": ([_P, _I, _P, _P, _D, _P, C.POINTER(_D)], _I),
 }
 
 _lib: Optional[C.CDLL] = None

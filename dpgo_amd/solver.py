@@ -464,6 +464,16 @@ class QuadraticProblem:
         L.check(self._lib.dpgo_problem_rie_grad_norm(self._h, L.ptr(Yc), C.byref(out)))
         return out.value
 
+    def certify(self, X, witness: bool = True, **params):
+        """Certificate of global optimality of X (dpgo_problem_certify; certificate.py): CertificateResult."""
+        from .certificate import certify
+        return certify(self, X, witness=witness, **params)
+
+    def certificateApply(self, X, V) -> np.ndarray:
+        """V C(X), C(X) = Q - Lambda(X) the certificate matrix (dpgo_problem_certificate_apply)."""
+        from .certificate import certificate_apply
+        return certificate_apply(self, X, V)
+
     # ---- device-resident flavour (torch tensors or raw device addresses) ----
     def setStream(self, hip_stream: Optional[int]) -> None:
         """Order this problem's device work with an external stream (torch's current stream);

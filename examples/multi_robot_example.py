@@ -21,6 +21,8 @@ def main():
     ap.add_argument("--iterations", type=int, default=1000)
     ap.add_argument("--no-acceleration", action="store_true")
     ap.add_argument("--out-dir", default=None)
+    ap.add_argument("--certify", action="store_true",
+                    help="certify the assembled global iterate on one central handle (QuadraticProblem.certify)")
     args = ap.parse_args()
     print("Multi-robot pose graph optimization example. ")
     if args.num_robots <= 0:
@@ -49,6 +51,14 @@ def main():
     out = cluster.run_greedy(max_iters=args.iterations, gradnorm_stop=0.1)
     for it, (rob, (cost, gn)) in enumerate(zip(out["selected"], out["trace"])):
         print("Iter = %d | robot = %d | cost = %.5g | gradnorm = %.5g" % (it, rob, cost, gn))
+    if args.certify:
+        X = np.concatenate([agents[a].X.cpu().numpy() for a in range(args.num_robots)])  # tiles [n, d+1, r]
+        pg = dpgo_amd.PoseGraph(0, r, d)
+        pg.setMeasurements(meas)
+        central = dpgo_amd.QuadraticProblem(pg)
+        c = central.certify(np.ascontiguousarray(X).reshape(-1, r).T)
+        print("Certificate of the global iterate: %s | lambda_min = %.6g | |rgrad| = %.3g | %d LOBPCG iterations" % (
+            c.status, c.lambda_min, c.gradnorm, c.iterations))
     if args.out_dir:
         os.makedirs(args.out_dir, exist_ok=True)
         for a, T in cluster.trajectories_in_global_frame().items():

@@ -18,6 +18,8 @@ def main():
     ap.add_argument("--iterations", type=int, default=100)
     ap.add_argument("--robust", action="store_true", help="GNC-TLS re-weighting (solveRobustPGO, rank d)")
     ap.add_argument("--out", default=None)
+    ap.add_argument("--certify", action="store_true",
+                    help="Riemannian staircase with a certificate of global optimality (solveCertifiedPGO)")
     args = ap.parse_args()
     import numpy as np
     import torch
@@ -29,6 +31,14 @@ def main():
     meas, n = dpgo_amd.read_g2o_file(args.g2o)
     d = meas.d
     print("Loaded %d poses, %d measurements from %s" % (n, len(meas), args.g2o))
+    if args.certify:
+        out = dpgo_amd.solveCertifiedPGO(meas)
+        c = out.certificate
+        print("Certificate: %s | lambda_min = %.6g | final rank = %d | escapes = %d | f = %.10g | gap = %.3g" % (
+            out.status, c.lambda_min, out.rank, len(out.escapes), out.f, out.gap))
+        if args.out and log_trajectory(d, n, out.trajectory, args.out):
+            print("wrote %s" % args.out)
+        return
     if args.robust:
         from dpgo_amd.robust import solveRobustPGO
         T, info = solveRobustPGO(meas, n)

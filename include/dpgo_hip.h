@@ -637,6 +637,68 @@ int dpgo_build_G_coupling(int my_id, int d, int n, int m, const int32_t* r1, con
                           const int32_t* slot_of_edge, int* nnzb_out, int32_t* rowptr, int32_t* colidx,
                           double* vals);
 
+/* ---- certificate of global optimality (SE-Sync / DC2-PGO verification) ----
+ * For an iterate X (r x (d+1)n, the tile layout above) of a handle WITHOUT a linear term G (the global or central problem):
+ * the certificate matrix C(X) = Q - Lambda(X), Lambda = blockdiag(Lambda_1 .. Lambda_n), Lambda_i (d+1) x (d+1) with top-left
+ * block sym(Y_i^T (XQ)_rot,i) and a zero last row and column.  C is symmetric; at a first-order critical point X C = 0.
+ * The smallest eigenvalue of C is sought by a preconditioned block LOBPCG (block = one r-row tile vector) on the complement
+ * of Z = span(rows of X, translation indicator t = (0_d, 1) per pose), where only the directions one product confirms to
+ * be null (|C z| <= sqrt(tol_rel) scale) are deflated.  scale = max_i max diag(Q_ii); eta and tol are relative to it.
+ *   NOT_CERTIFIED: a unit vector w orthogonal to Z has w^T C w < -eta scale.  A proof up to rounding: X is not a global
+ *                  minimiser of the rank-r relaxation (a saddle); w is the witness the staircase escapes along.  The solver
+ *                  goes on until that Ritz pair has converged (or the iteration budget ends) so that lambda_min and w are
+ *                  accurate.
+ *   CERTIFIED:     the smallest Ritz value on the complement is >= -eta scale and its residual is <= tol_rel scale.
+ *                  NUMERICAL, not a lower-bound proof: an eigen-solver can miss a smaller eigenvalue its start block and
+ *                  Krylov space never saw (a Cholesky-based proof of C + eta I >= 0 is out of scope).  With X of rank d
+ *                  a certified X rounds to the global optimum of the PGO problem (SE-Sync, Thm. 7).
+ *   NOT_CONVERGED: neither within max_iterations. */
+#define DPGO_CERT_CERTIFIED 0
+#define DPGO_CERT_NOT_CERTIFIED 1
+#define DPGO_CERT_NOT_CONVERGED 2
+
+/* defaults set by dpgo_certify_params_default() */
+typedef struct dpgo_certify_params {
+  double eta;          /* negativity threshold, relative to scale     default 1e-6 */
+  double tol_rel;      /* Ritz residual tolerance, relative to scale  default 1e-6 */
+  int max_iterations;  /* LOBPCG iterations                           default 1000 */
+  int precond;         /* DPGO_PRECOND_NONE / BLOCK_JACOBI / MULTILEVEL for Q + precond_shift I, applied WITHOUT tangent
+                          projection; AUTO = what the handle's solve resolves to; ADDITIVE runs MULTILEVEL.  default AUTO */
+  double precond_shift; /*                                            default 1e-1 */
+  uint64_t seed;       /* start block (deterministic hash of seed and element index)  default 1 */
+} dpgo_certify_params;
+
+typedef struct dpgo_certify_result {
+  int status;                 /* DPGO_CERT_* */
+  double lambda_min;          /* w^T C w of the returned witness (unit, orthogonal to Z) */
+  double residual;            /* |C w - theta w| of the smallest Ritz pair at the last iteration */
+  double gradnorm;            /* |rgrad f(X)| */
+  double scale;               /* max_i max diag(Q_ii) */
+  int iterations;             /* LOBPCG iterations */
+  int products;               /* r-row block products with C (deflation check included) */
+  int deflated;               /* dimension of Z */
+  double deflation_residual;  /* |C z| of the least null direction kept in Z */
+  double elapsedMs;
+} dpgo_certify_result;
+
+void dpgo_certify_params_default(dpgo_certify_params* p);
+/* Certify X (host matrix).  witness_host may be NULL; otherwise it receives (d+1)n doubles, pose-major like one row of X
+ * (one tile column per entry).  DPGO_ERR_INVALID for a handle with G set or bad parameters. */
+int dpgo_problem_certify(dpgo_problem_t h, const double* X_host, const dpgo_certify_params* params,
+                         dpgo_certify_result* result, double* witness_host);
+/* Device flavour: X_dev and witness_dev (may be NULL) are device buffers; only scalars and r x r blocks cross PCIe. */
+int dpgo_problem_certify_device(dpgo_problem_t h, const double* X_dev, const dpgo_certify_params* params,
+                                dpgo_certify_result* result, double* witness_dev);
+/* CV = V C(X) for host matrices X, V (r x (d+1)n); for tests. */
+int dpgo_problem_certificate_apply(dpgo_problem_t h, const double* X_host, const double* V_host, double* CV_host);
+/* Riemannian-staircase escape: X_next = retract([X; alpha w^T]) on h_next (rank r + 1, same Q) for the first alpha of
+ * alpha0, alpha0 / 2, ... (alpha0 = 0.1 sqrt(n)) that decreases f and leaves |rgrad| > grad_tol (SE-Sync's rule); X_dev:
+ * rank-r device matrix, witness_dev: (d+1)n doubles from dpgo_problem_certify_device.  DPGO_ERR_UNSUPPORTED when (d, r + 1)
+ * is not compiled (dpgo_supported), DPGO_ERR_INVALID when h_next does not have rank r + 1, DPGO_ERR_STATE when no step of
+ * 60 halvings decreases f. */
+int dpgo_certify_escape_device(dpgo_problem_t h_next, int r, const double* X_dev, const double* witness_dev,
+                               double grad_tol, double* X_next_dev, double* alpha);
+
 #ifdef __cplusplus
 }
 #endif

@@ -509,6 +509,29 @@ class QuadraticProblem {
     check(dpgo_problem_rie_grad(h_, Y.data(), out.data()));
     return out;
   }
+  // Certificate of global optimality of Y (dpgo_problem_certify): params NULL = the defaults;
+  // witness, if given, receives the (d+1)n entries of the witness (pose-major, one tile column per entry).
+  dpgo_certify_result certify(const Matrix& Y, const dpgo_certify_params* params = nullptr,
+                              std::vector<double>* witness = nullptr) const {
+    shape(Y);
+    dpgo_certify_params prm;
+    if (params)
+      prm = *params;
+    else
+      dpgo_certify_params_default(&prm);
+    dpgo_certify_result res{};
+    if (witness) witness->assign((size_t)num_poses() * (dimension() + 1), 0.0);
+    check(dpgo_problem_certify(h_, Y.data(), &prm, &res, witness ? witness->data() : nullptr));
+    return res;
+  }
+  // V C(Y), C(Y) = Q - Lambda(Y) the certificate matrix (dpgo_problem_certificate_apply)
+  Matrix certificateApply(const Matrix& Y, const Matrix& V) const {
+    shape(Y);
+    shape(V);
+    Matrix out(V.rows(), V.cols());
+    check(dpgo_problem_certificate_apply(h_, Y.data(), V.data(), out.data()));
+    return out;
+  }
   double RieGradNorm(const Matrix& Y) const {  // :81-83
     shape(Y);
     double out = 0;
