@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py -- RBCD iterations/sec of the MI355X-native local solver + Q*X roofline.
 
-    python bench.py --gpus N --steps K --warmup W [--workload grid100k|sphere2500|grid:NXxNYxNZ] [--dump-outputs DIR]
+    python bench.py --gpus N --steps K --warmup W [--workload grid100k|sphere2500|grid:NXxNYxNZ] [--dump-outputs DIR] [--full]
 
 One "step" = one RBCD iteration from a fixed, settled iterate (identical full work every step; see main()):
 every agent runs QuadraticOptimizer::optimize once (RTR, 3 outer
@@ -14,7 +14,10 @@ with the public-pose exchange over RCCL point-to-point.  Total work is fixed as 
 Workload at N = 1: the synthetic 100k-pose 3-D grid of BASELINE.json (configs[3], the configuration the
 HBM-roofline target is quoted on; it fits one GPU).  Inputs are resident in HBM before the timed region.
 
-Prints ONE JSON line (rank 0).  `roofline` describes the tCG-step kernel THE TIMED LOOP LAUNCHES (k_tcg_hess_span on the
+Prints ONE JSON line (rank 0).  A plain run does only what the headline needs: set-up, the settle phase, warm-up, the timed
+steps, --dump-outputs, the line.  `roofline`, `cpu_baseline`, `time_to_tolerance_*`, `hierarchy_*`, `also`, `kitti_gnc`
+and the settle phase's cost trajectory are measured with --full only (null otherwise); `products_per_step` and
+`us_per_product` come from the timed steps themselves.  `roofline` describes the tCG-step kernel THE TIMED LOOP LAUNCHES (k_tcg_hess_span on the
 plain block-CSR arrays for every BASELINE configuration; k_tcg_hess_sym where the size switch selects the symmetric
 storage): `frac` is its HBM-only figure (every operand cycling through > 256 MB of private copies), `warm`
 the back-to-back one the Infinity-Cache-resident loop sees; the other storage's figures stand beside it
@@ -56,10 +59,16 @@ def parse_args():
     ap.add_argument("--precond", default="auto", choices=["auto", "jacobi", "multilevel", "additive"],
                     help="tCG preconditioner: auto (library default, include/dpgo_hip.h DPGO_PRECOND_AUTO), or one of "
                          "the others all the time")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the sphere2500 side measurement (`also` field)")
-    ap.add_argument("--cpu-budget-s", type=float, default=25.0)
-    ap.add_argument("--spmm-reps", type=int, default=200)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure everything beside the headline: the settle phase's cost "
+                         "trajectory, the roofline probes, the CPU baselines, time to tolerance, the sphere2500 and kitti_00 "
+                         "side measurements.  Without it a run sets up, warms up, times the steps, dumps (--dump-outputs) and "
+                         "prints its line")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-secondary", action="store_true",
+                    help="with --full: skip the side measurements (time to tolerance, `also`, `kitti_gnc`)")
+    ap.add_argument("--cpu-budget-s", type=float, default=25.0, help="with --full: time budget of the 1-core port")
+    ap.add_argument("--spmm-reps", type=int, default=200, help="with --full: launches per roofline probe")
     ap.add_argument("--agents-per-gpu", type=int, default=0, help="0 = auto (1 if one GPU, else 2; 8 with --loopback)")
     ap.add_argument("--sequential", action="store_true",
                     help="diagnostic: the agents a process hosts are solved one after the other (DPGO_SEQUENTIAL_SWEEP=1) -- "
@@ -697,7 +706,7 @@ def compact_line(out):
             also[key] = {"it_per_s": v["it_per_s"], "us_per_product": v.get("us_per_product"), "precond_used": v.get("precond_used"),
                          "in_kernel_us_per_iteration": (v.get("in_kernel_us_per_iteration") or {}).get("total")}
     line = dict(head)
-    line.update(config=config, roofline=roof, cpu_baseline=cpu, kitti_gnc=kitti,
+    line.update(config=config, roofline=roof if rf else None, cpu_baseline=cpu, kitti_gnc=kitti,
                 to_tolerance_products_ms_reached=tt or None, also=also or None,
                 detail="full record: bench_detail.json and the stdout line prefixed 'DETAIL '")
     line = _rnd(line)
@@ -717,190 +726,12 @@ def compact_line(out):
     return text
 
 
-def main():
-    args = parse_args()
-    if args.sequential:
-        os.environ["DPGO_SEQUENTIAL_SWEEP"] = "1"
-    import torch
-    import torch.distributed as dist
+def roofline_probes(args, agent, ops_state, d, r, n_local, nnzb_local, world, elapsed, tcg_total):
+    """--full: the roofline of the kernels the timed loop launched, probed on `agent` (the largest block of this rank) after
+    the timed steps; `ops_state` = its multilevelOperatorBits() as the timed steps left them.  Returns (roofline, the
+    multilevel hierarchy's info or None)."""
     import dpgo_amd
-    from dpgo_amd.agent import DeviceAgent, ExchangePlan, RBCDCluster, build_pose_graphs
-
-    world = int(os.environ.get("WORLD_SIZE", "1"))
-    rank = int(os.environ.get("RANK", "0"))
-    local_rank = int(os.environ.get("LOCAL_RANK", "0"))
-    if args.gpus != world and world > 1:
-        raise SystemExit("--gpus %d but WORLD_SIZE=%d" % (args.gpus, world))
-    if args.gpus > 1 and world == 1:
-        raise SystemExit("launch with torch.distributed.run for --gpus > 1")
-    # the multi-GPU branch: N > 1 ranks, or forced at any world size (--dist / DPGO_BENCH_DIST=1) so that it can be
-    # executed -- and is tested -- on a single device
-    use_dist = world > 1 or args.dist or os.environ.get("DPGO_BENCH_DIST", "0") == "1"
-    if use_dist and "MASTER_ADDR" not in os.environ:  # (python bench.py --dist without a launcher)
-        os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
-        os.environ.setdefault("MASTER_PORT", "29531")
-        os.environ.setdefault("RANK", "0")
-        os.environ.setdefault("WORLD_SIZE", "1")
-    loopback = args.loopback or (use_dist and world == 1)
-    if dpgo_amd.device_count() < 1:
-        raise SystemExit("bench.py needs a HIP device: the product path has no CPU fallback")
-    dev_index = local_rank % torch.cuda.device_count()
-    torch.cuda.set_device(dev_index)
-    backend = None
-    comm = None
-    if use_dist:
-        # "nccl" IS RCCL on ROCm.  DPGO_DIST_BACKEND=gloo (host-staged exchange) lets the N > 1 path be exercised
-        # on a single-GPU box with all ranks sharing device 0; it is also the fallback if RCCL cannot initialise.
-        backend = "gloo" if args.transport == "ipc" else os.environ.get("DPGO_DIST_BACKEND", "nccl")
-        if args.transport == "ipc" and world == 1:
-            raise SystemExit("--transport ipc needs at least two processes (torch.distributed.run --nproc-per-node 2)")
-        if backend == "nccl":
-            # no silent degradation: if RCCL cannot initialise the run FAILS (non-zero exit) -- a host-staged number
-            # must never stand in for the xGMI one
-            dist.init_process_group("nccl", device_id=torch.device("cuda", dev_index))
-            t = torch.ones(1, device="cuda")
-            dist.all_reduce(t)  # create torch's communicator eagerly (barriers of the timing protocol)
-            torch.cuda.synchronize()
-            from dpgo_amd.comm import DeviceComm
-            comm = DeviceComm.from_torch_distributed(dev_index)  # the data path's own communicator (C ABI dpgo_comm_*)
-        else:
-            dist.init_process_group(backend)
-    elif loopback:
-        from dpgo_amd.comm import DeviceComm, unique_id
-        comm = DeviceComm(1, 0, unique_id(), dev_index)  # 1-rank RCCL communicator: self send / recv, all-reduce
-
-    r = args.rank
-    meas, n, X0, desc = make_workload(args.workload, r)
-    d = meas.d
-    # agents: 1 for a single GPU (one agent owns the whole graph, BASELINE configs[1] style);
-    # for N > 1 GPUs two agents per GPU by default -- consecutive blocks of a chain / ring partition
-    # alternate colours, so every GPU hosts one agent of each colour and works in BOTH colour phases
-    apg = args.agents_per_gpu if args.agents_per_gpu > 0 else (2 if use_dist else (8 if args.loopback else 1))
-    num_agents = world * apg
-    ranges, graphs = build_pose_graphs(meas, n, num_agents, r)
-    params = dpgo_amd.ROptParameters(precond=args.precond)  # reference defaults + block-Jacobi (or multilevel)
-    plan = ExchangePlan(graphs)
-    my_ids = list(range(rank * apg, (rank + 1) * apg))
-    agents = {a: DeviceAgent(graphs, plan, a, X0[ranges[a][0]:ranges[a][1]], params, device=dev_index)
-              for a in my_ids}
-    cluster = RBCDCluster(plan, agents, rank, world, agents_per_rank=apg, comm=comm, loopback=loopback)
-    if use_dist and args.transport == "ipc":
-        cluster.enable_peer_store()
-    big = max(my_ids, key=lambda a: graphs[a].n())  # the agent whose kernels are profiled below
-    agent = agents[big]
-    nnzb_local = len(graphs[big].quadraticMatrix()[1])
-    n_local = graphs[big].n()
-
-    def barrier():
-        torch.cuda.synchronize()
-        if use_dist:
-            dist.barrier()
-            torch.cuda.synchronize()
-
-    # Settle into the working regime (not timed), then make every step identical work: each warm-up / timed
-    # step restores the settled iterate and runs ONE full RBCD iteration from it.  (Consecutive iterations
-    # of a single agent converge within ~10 steps, after which optimize() is a no-op -- timing those would
-    # inflate the rate and make it depend on K.)
-    f0, g0 = cluster.central_cost_and_gradnorm()
-    trajectory = [(2 * f0, g0)]
-    # `settle` sweeps plus one probe sweep are run; the benchmark state is the iterate before the LAST sweep that
-    # still did at least half the Hessian-vector products of the first one.  Large problems: that is the state
-    # after all `settle` sweeps (the probe itself is heavy); small problems that converge during the settle
-    # phase: the last iterate from which a sweep is real work.
-    states, works = [], []
-    for k in range(args.settle + 1):
-        states.append({a: ag.X.clone() for a, ag in agents.items()})
-        cluster.sweep()
-        work = torch.tensor([float(sum(a.last_result.tcg_iterations for a in agents.values() if a.last_result))],
-                            dtype=torch.float64, device="cpu" if (use_dist and cluster.stage) else "cuda")
-        if use_dist:
-            dist.all_reduce(work)
-        works.append(float(work.item()))
-        if k < args.settle:
-            f, g = cluster.central_cost_and_gradnorm()
-            trajectory.append((2 * f, g))
-    settled = max(k for k in range(len(works)) if works[k] >= 0.5 * works[0])
-    for a, ag in agents.items():
-        ag.X.copy_(states[settled][a])
-    trajectory = trajectory[:settled + 1]
-    del states
-    for a in agents.values():
-        a.snapshot()
-    # Steady state of the preconditioner selection (untimed): `auto` decides per handle from the solves themselves (coupled
-    # blocks: the cost rule of dpgo_hip.h pays the hierarchy once the block-Jacobi solves have cost as much) -- sweeps from
-    # the benchmark's iterate until no agent's selection state changed in two consecutive sweeps, so that the timed steps
-    # run what a long RBCD run runs and contain no set-up.
-    selection_sweeps = 0
-    if args.precond == "auto" and num_agents > 1:
-        def undecided():
-            # an agent still on block-Jacobi that has never been through a trial (nor skipped a hopeless one) will switch
-            # once its block-Jacobi work has paid one set-up: not a steady state yet; blocks outside the cost rule
-            # (no coupling, or too large for the additive form: they follow the tCG-budget hysteresis) are steady at once
-            n_open = 0
-            for ag in agents.values():
-                info = ag.problem.autoInfo()
-                small = ag.n * (ag.d + 1) <= 65536 and ag.has_neighbours  # (256 aggregates of one 64-lane-group tile)
-                if small and (info["state"] == "trial" or (info["state"] == "jacobi" and info["backoff"] == 0)):
-                    n_open += 1
-            return n_open
-        while selection_sweeps < 40:
-            open_ = torch.tensor([float(undecided())], dtype=torch.float64,
-                                 device="cpu" if (use_dist and cluster.stage) else "cuda")
-            if use_dist:  # every rank runs the same number of sweeps (they contain the exchanges)
-                dist.all_reduce(open_, op=dist.ReduceOp.MAX)
-            if float(open_.item()) == 0.0:
-                break
-            for a in agents.values():
-                a.restore()
-            cluster.sweep()
-            selection_sweeps += 1
-
-    # device time of the public-pose exchanges, from event pairs on the stream they are enqueued on -- no host wait is
-    # added to the path being timed (pack kernel -> RCCL batch / device copies -> consumed by the coupling SpMM)
-    ex_events = []
-    _exchange = cluster.exchange
-
-    def timed_exchange(*a, **k):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        _exchange(*a, **k)
-        e1.record()
-        ex_events.append((e0, e1))
-
-    if num_agents > 1:
-        cluster.exchange = timed_exchange
-
-    def step():
-        for a in agents.values():
-            a.restore()
-        cluster.sweep()
-
-    for _ in range(args.warmup):
-        step()
-    barrier()
-    del ex_events[:]
-    t0 = time.perf_counter()
-    tcg_total = 0
-    used_precond = set()
-    for _ in range(args.steps):
-        step()
-        tcg_total += sum(a.last_result.tcg_iterations for a in agents.values() if a.last_result)
-        used_precond |= {a.last_result.precond_used for a in agents.values() if a.last_result}
-    barrier()
-    elapsed = time.perf_counter() - t0
-    if use_dist:
-        t = torch.tensor([elapsed], dtype=torch.float64, device="cpu" if cluster.stage else "cuda")
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        elapsed = float(t.item())
-    exchange_ms = sum(e0.elapsed_time(e1) for e0, e1 in ex_events)
-    cluster.exchange = _exchange
-    if args.dump_outputs:  # (before anything below touches the agents' state)
-        dump_outputs(args.dump_outputs, agents, world)
-    # (what the timed steps' cycles streamed: asked NOW -- the probes below set the hierarchy up again)
-    ops_state = agent.problem.multilevelOperatorBits()
     ops_active = bool(ops_state["active"])
-    f1, g1 = cluster.central_cost_and_gradnorm()
-
     # ---- dominant-kernel roofline, measured live with HIP events on the solver's stream ----
     lib = dpgo_amd.lib.load()
     import ctypes as C
@@ -1184,10 +1015,200 @@ def main():
                          "indices, factors, G, X in and out) over its time: latency-bound by its chip-wide reductions (2-3 "
                          "per product), not by HBM; effective_algorithmic_* = products x the tCG step's algorithmic bytes "
                          "(SURVEY 8d) over the same time, the figure comparable with multi_launch_kernel" % 20)
+    return roofline, ml_info
+
+
+def main():
+    args = parse_args()
+    if args.sequential:
+        os.environ["DPGO_SEQUENTIAL_SWEEP"] = "1"
+    import torch
+    import torch.distributed as dist
+    import dpgo_amd
+    from dpgo_amd.agent import DeviceAgent, ExchangePlan, RBCDCluster, build_pose_graphs
+
+    world = int(os.environ.get("WORLD_SIZE", "1"))
+    rank = int(os.environ.get("RANK", "0"))
+    local_rank = int(os.environ.get("LOCAL_RANK", "0"))
+    if args.gpus != world and world > 1:
+        raise SystemExit("--gpus %d but WORLD_SIZE=%d" % (args.gpus, world))
+    if args.gpus > 1 and world == 1:
+        raise SystemExit("launch with torch.distributed.run for --gpus > 1")
+    # the multi-GPU branch: N > 1 ranks, or forced at any world size (--dist / DPGO_BENCH_DIST=1) so that it can be
+    # executed -- and is tested -- on a single device
+    use_dist = world > 1 or args.dist or os.environ.get("DPGO_BENCH_DIST", "0") == "1"
+    if use_dist and "MASTER_ADDR" not in os.environ:  # (python bench.py --dist without a launcher)
+        os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
+        os.environ.setdefault("MASTER_PORT", "29531")
+        os.environ.setdefault("RANK", "0")
+        os.environ.setdefault("WORLD_SIZE", "1")
+    loopback = args.loopback or (use_dist and world == 1)
+    if dpgo_amd.device_count() < 1:
+        raise SystemExit("bench.py needs a HIP device: the product path has no CPU fallback")
+    dev_index = local_rank % torch.cuda.device_count()
+    torch.cuda.set_device(dev_index)
+    backend = None
+    comm = None
+    if use_dist:
+        # "nccl" IS RCCL on ROCm.  DPGO_DIST_BACKEND=gloo (host-staged exchange) lets the N > 1 path be exercised
+        # on a single-GPU box with all ranks sharing device 0; it is also the fallback if RCCL cannot initialise.
+        backend = "gloo" if args.transport == "ipc" else os.environ.get("DPGO_DIST_BACKEND", "nccl")
+        if args.transport == "ipc" and world == 1:
+            raise SystemExit("--transport ipc needs at least two processes (torch.distributed.run --nproc-per-node 2)")
+        if backend == "nccl":
+            # no silent degradation: if RCCL cannot initialise the run FAILS (non-zero exit) -- a host-staged number
+            # must never stand in for the xGMI one
+            dist.init_process_group("nccl", device_id=torch.device("cuda", dev_index))
+            t = torch.ones(1, device="cuda")
+            dist.all_reduce(t)  # create torch's communicator eagerly (barriers of the timing protocol)
+            torch.cuda.synchronize()
+            from dpgo_amd.comm import DeviceComm
+            comm = DeviceComm.from_torch_distributed(dev_index)  # the data path's own communicator (C ABI dpgo_comm_*)
+        else:
+            dist.init_process_group(backend)
+    elif loopback:
+        from dpgo_amd.comm import DeviceComm, unique_id
+        comm = DeviceComm(1, 0, unique_id(), dev_index)  # 1-rank RCCL communicator: self send / recv, all-reduce
+
+    r = args.rank
+    meas, n, X0, desc = make_workload(args.workload, r)
+    d = meas.d
+    # agents: 1 for a single GPU (one agent owns the whole graph, BASELINE configs[1] style);
+    # for N > 1 GPUs two agents per GPU by default -- consecutive blocks of a chain / ring partition
+    # alternate colours, so every GPU hosts one agent of each colour and works in BOTH colour phases
+    apg = args.agents_per_gpu if args.agents_per_gpu > 0 else (2 if use_dist else (8 if args.loopback else 1))
+    num_agents = world * apg
+    ranges, graphs = build_pose_graphs(meas, n, num_agents, r)
+    params = dpgo_amd.ROptParameters(precond=args.precond)  # reference defaults + block-Jacobi (or multilevel)
+    plan = ExchangePlan(graphs)
+    my_ids = list(range(rank * apg, (rank + 1) * apg))
+    agents = {a: DeviceAgent(graphs, plan, a, X0[ranges[a][0]:ranges[a][1]], params, device=dev_index)
+              for a in my_ids}
+    cluster = RBCDCluster(plan, agents, rank, world, agents_per_rank=apg, comm=comm, loopback=loopback)
+    if use_dist and args.transport == "ipc":
+        cluster.enable_peer_store()
+    big = max(my_ids, key=lambda a: graphs[a].n())  # the agent whose kernels are profiled below
+    agent = agents[big]
+    nnzb_local = len(graphs[big].quadraticMatrix()[1])
+    n_local = graphs[big].n()
+
+    def barrier():
+        torch.cuda.synchronize()
+        if use_dist:
+            dist.barrier()
+            torch.cuda.synchronize()
+
+    # Settle into the working regime (not timed), then make every step identical work: each warm-up / timed
+    # step restores the settled iterate and runs ONE full RBCD iteration from it.  (Consecutive iterations
+    # of a single agent converge within ~10 steps, after which optimize() is a no-op -- timing those would
+    # inflate the rate and make it depend on K.)
+    trajectory = []
+    if args.full:  # (the cost / gradient-norm trajectory of the settle phase; a plain run does not evaluate it)
+        f0, g0 = cluster.central_cost_and_gradnorm()
+        trajectory.append((2 * f0, g0))
+    # `settle` sweeps plus one probe sweep are run; the benchmark state is the iterate before the LAST sweep that
+    # still did at least half the Hessian-vector products of the first one.  Large problems: that is the state
+    # after all `settle` sweeps (the probe itself is heavy); small problems that converge during the settle
+    # phase: the last iterate from which a sweep is real work.
+    states, works = [], []
+    for k in range(args.settle + 1):
+        states.append({a: ag.X.clone() for a, ag in agents.items()})
+        cluster.sweep()
+        work = torch.tensor([float(sum(a.last_result.tcg_iterations for a in agents.values() if a.last_result))],
+                            dtype=torch.float64, device="cpu" if (use_dist and cluster.stage) else "cuda")
+        if use_dist:
+            dist.all_reduce(work)
+        works.append(float(work.item()))
+        if args.full and k < args.settle:
+            f, g = cluster.central_cost_and_gradnorm()
+            trajectory.append((2 * f, g))
+    settled = max(k for k in range(len(works)) if works[k] >= 0.5 * works[0])
+    for a, ag in agents.items():
+        ag.X.copy_(states[settled][a])
+    trajectory = trajectory[:settled + 1]
+    del states
+    for a in agents.values():
+        a.snapshot()
+    # Steady state of the preconditioner selection (untimed): `auto` decides per handle from the solves themselves (coupled
+    # blocks: the cost rule of dpgo_hip.h pays the hierarchy once the block-Jacobi solves have cost as much) -- sweeps from
+    # the benchmark's iterate until no agent's selection state changed in two consecutive sweeps, so that the timed steps
+    # run what a long RBCD run runs and contain no set-up.
+    selection_sweeps = 0
+    if args.precond == "auto" and num_agents > 1:
+        def undecided():
+            # an agent still on block-Jacobi that has never been through a trial (nor skipped a hopeless one) will switch
+            # once its block-Jacobi work has paid one set-up: not a steady state yet; blocks outside the cost rule
+            # (no coupling, or too large for the additive form: they follow the tCG-budget hysteresis) are steady at once
+            n_open = 0
+            for ag in agents.values():
+                info = ag.problem.autoInfo()
+                small = ag.n * (ag.d + 1) <= 65536 and ag.has_neighbours  # (256 aggregates of one 64-lane-group tile)
+                if small and (info["state"] == "trial" or (info["state"] == "jacobi" and info["backoff"] == 0)):
+                    n_open += 1
+            return n_open
+        while selection_sweeps < 40:
+            open_ = torch.tensor([float(undecided())], dtype=torch.float64,
+                                 device="cpu" if (use_dist and cluster.stage) else "cuda")
+            if use_dist:  # every rank runs the same number of sweeps (they contain the exchanges)
+                dist.all_reduce(open_, op=dist.ReduceOp.MAX)
+            if float(open_.item()) == 0.0:
+                break
+            for a in agents.values():
+                a.restore()
+            cluster.sweep()
+            selection_sweeps += 1
+
+    # device time of the public-pose exchanges, from event pairs on the stream they are enqueued on -- no host wait is
+    # added to the path being timed (pack kernel -> RCCL batch / device copies -> consumed by the coupling SpMM)
+    ex_events = []
+    _exchange = cluster.exchange
+
+    def timed_exchange(*a, **k):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        _exchange(*a, **k)
+        e1.record()
+        ex_events.append((e0, e1))
+
+    if num_agents > 1:
+        cluster.exchange = timed_exchange
+
+    def step():
+        for a in agents.values():
+            a.restore()
+        cluster.sweep()
+
+    for _ in range(args.warmup):
+        step()
+    barrier()
+    del ex_events[:]
+    t0 = time.perf_counter()
+    tcg_total = 0
+    used_precond = set()
+    for _ in range(args.steps):
+        step()
+        tcg_total += sum(a.last_result.tcg_iterations for a in agents.values() if a.last_result)
+        used_precond |= {a.last_result.precond_used for a in agents.values() if a.last_result}
+    barrier()
+    elapsed = time.perf_counter() - t0
+    if use_dist:
+        t = torch.tensor([elapsed], dtype=torch.float64, device="cpu" if cluster.stage else "cuda")
+        dist.all_reduce(t, op=dist.ReduceOp.MAX)
+        elapsed = float(t.item())
+    exchange_ms = sum(e0.elapsed_time(e1) for e0, e1 in ex_events)
+    cluster.exchange = _exchange
+    if args.dump_outputs:  # (before anything below touches the agents' state)
+        dump_outputs(args.dump_outputs, agents, world)
+    roofline = ml_info = ops_state = f1 = g1 = None
+    if args.full:
+        # (what the timed steps' cycles streamed: asked NOW -- the probes below set the hierarchy up again)
+        ops_state = agent.problem.multilevelOperatorBits()
+        f1, g1 = cluster.central_cost_and_gradnorm()
+        roofline, ml_info = roofline_probes(args, agent, ops_state, d, r, n_local, nnzb_local, world, elapsed, tcg_total)
 
     cpu = None
     jac_step = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         agent.restore()
         X_state = agent.iterate_in_caller_order().cpu().numpy()
         try:  # the device's block-Jacobi step from the same iterate: what the 1-core port below restates
@@ -1243,7 +1264,7 @@ def main():
 
     also = None
     to_tol = None
-    if rank == 0 and world == 1 and not args.no_secondary:
+    if rank == 0 and world == 1 and args.full and not args.no_secondary:
         # products-to-tolerance and time-to-gradnorm on this workload with both preconditioners, and the same for
         # sphere2500 (BASELINE configs[1]); then the fixed-work step rate of sphere2500
         to_tol = {}
@@ -1271,7 +1292,7 @@ def main():
                     also[key] = {"error": repr(exc)}
 
     kitti = None
-    if rank == 0 and world == 1 and not args.no_secondary and args.workload == "grid100k":
+    if rank == 0 and world == 1 and args.full and not args.no_secondary and args.workload == "grid100k":
         try:  # BASELINE configs[4]: the re-weighted rebuild of Q each GNC outer iteration, timed
             kitti = kitti_gnc_gpu(r, dev_index)
             if not args.no_cpu_baseline:
@@ -1373,7 +1394,7 @@ def main():
             "quality": {"settle_iterations": settled,
                         "cost_2f_trajectory": [c for c, _ in trajectory],
                         "gradnorm_trajectory": [g for _, g in trajectory],
-                        "cost_2f_after_step": 2 * f1, "gradnorm_after_step": g1,
+                        "cost_2f_after_step": 2 * f1 if f1 is not None else None, "gradnorm_after_step": g1,
                         "tcg_iterations_per_step_rank0": tcg_total / max(args.steps, 1),
                         "us_per_tcg_iteration_rank0": 1e6 * elapsed / max(tcg_total, 1),
                         "exchange_ms_per_step_rank0": exchange_ms / max(args.steps, 1),

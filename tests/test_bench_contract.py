@@ -113,7 +113,7 @@ def test_dump_outputs_writes_the_agents_results_within_the_size_limit(tmp_path, 
 def test_bench_prints_one_valid_json_line(tmp_path):
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "grid:12x10x6", "--steps", "2",
                         "--warmup", "1", "--settle", "2", "--cpu-budget-s", "3", "--spmm-reps", "20",
-                        "--dump-outputs", str(tmp_path)],
+                        "--dump-outputs", str(tmp_path), "--full"],
                        capture_output=True, text=True, cwd=ROOT, timeout=600)
     assert p.returncode == 0, p.stderr[-2000:]
     line, j = records(p.stdout)
@@ -212,13 +212,44 @@ def test_bench_prints_one_valid_json_line(tmp_path):
 
 
 @pytest.mark.gpu
+def test_bench_plain_run_measures_the_headline_only(tmp_path):
+    """Without --full a run sets up, settles, warms up, times its steps, dumps and prints: no roofline probe, CPU baseline or
+    side measurement, and the steps compute bit for bit what a --full run's steps compute."""
+    args = [sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "grid:12x10x6", "--steps", "2", "--warmup", "1",
+            "--settle", "2"]
+    plain = subprocess.run(args + ["--dump-outputs", str(tmp_path / "plain")], capture_output=True, text=True, cwd=ROOT,
+                           timeout=600)
+    assert plain.returncode == 0, plain.stderr[-2000:]
+    line, j = records(plain.stdout)
+    assert line["metric"] == "rbcd_iterations_per_sec" and line["unit"] == "it/s" and line["higher_is_better"] is True
+    assert line["dtype"] == "f64" and j["value"] > 0 and abs(j["value"] - 1e3 / j["ms_per_step"]) < 1e-6 * j["value"]
+    assert j["products_per_step"] > 0 and line["us_per_product"] > 0 and j["config"]["precond_used_in_timed_steps"]
+    for k in ("roofline", "cpu_baseline", "also", "kitti_gnc", "time_to_tolerance_ms", "hierarchy_setup_ms",
+              "gradnorm_before_step", "gradnorm_after_step"):
+        assert j[k] is None and line.get(k) is None, k
+    assert j["quality"]["to_tolerance"] is None and j["quality"]["cost_2f_trajectory"] == []
+    full = subprocess.run(args + ["--dump-outputs", str(tmp_path / "full"), "--full", "--no-cpu-baseline",
+                                  "--no-secondary", "--spmm-reps", "10"],
+                          capture_output=True, text=True, cwd=ROOT, timeout=600)
+    assert full.returncode == 0, full.stderr[-2000:]
+    _, jf = records(full.stdout)
+    assert jf["roofline"] is not None and jf["gradnorm_after_step"] > 0
+    assert jf["products_per_step"] == j["products_per_step"]
+    names = sorted(os.listdir(str(tmp_path / "plain")))
+    assert names == sorted(os.listdir(str(tmp_path / "full"))) and "agent0_X.npy" in names
+    for f in names:
+        assert np.array_equal(np.load(str(tmp_path / "plain" / f)), np.load(str(tmp_path / "full" / f))), f
+
+
+@pytest.mark.gpu
 def test_bench_default_invocation_fits_the_drivers_record():
-    """The driver's own command (python bench.py --gpus 1 --steps 20 --warmup 5: the 100k-pose grid): the LAST stdout line
+    """The driver's own command with --full (python bench.py --gpus 1 --steps 20 --warmup 5 --full: the 100k-pose grid, every
+    side measurement): the LAST stdout line
     is one JSON object below 6 KB carrying `roofline` (headline kernel, PMC traffic, streamed-byte fractions of every kernel
     of the iteration, the whole iteration) and `cpu_baseline`; BASELINE configs[4] (kitti_00 GNC) has its numbers; the
     default (fp32 cycle storage) and the fp64-cycle run need the same number of products to the tolerance."""
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5"],
-                       capture_output=True, text=True, cwd=ROOT, timeout=1200)
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5",
+                        "--full"], capture_output=True, text=True, cwd=ROOT, timeout=1200)
     assert p.returncode == 0, p.stderr[-3000:]
     line, full = records(p.stdout)
     assert "100000 poses" in line["config"]["workload"] and line["config"]["agents"] == 1
@@ -274,7 +305,7 @@ def test_bench_loopback_runs_the_multi_agent_path_through_rccl():
     communicator (the N > 1 data path), same-colour agents solved concurrently, exchange time from device events."""
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "grid:12x10x8", "--steps", "2",
                         "--warmup", "1", "--settle", "1", "--loopback", "--agents-per-gpu", "4", "--no-cpu-baseline",
-                        "--no-secondary", "--spmm-reps", "10"],
+                        "--no-secondary", "--spmm-reps", "10", "--full"],
                        capture_output=True, text=True, cwd=ROOT, timeout=600)
     assert p.returncode == 0, p.stderr[-2000:]
     line, j = records(p.stdout)
@@ -301,6 +332,30 @@ def test_bench_default_steps_time_more_than_a_second():
     assert a.steps >= 200 and a.gpus == 1 and a.warmup >= 1
 
 
+def test_bench_side_measurements_are_opt_in():
+    """--full is off by default; the line of a run without it carries the headline keys and null in place of the side
+    measurements."""
+    sys.path.insert(0, ROOT)
+    import bench
+    old = sys.argv
+    try:
+        sys.argv = ["bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1"]
+        assert bench.parse_args().full is False
+        sys.argv += ["--full"]
+        assert bench.parse_args().full is True
+    finally:
+        sys.argv = old
+    out = {"metric": "rbcd_iterations_per_sec", "value": 250.0, "unit": "it/s", "n_gpus": 1, "steps": 3, "warmup": 1,
+           "ms_per_step": 4.0, "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f64",
+           "data": "synthetic", "products_per_step": 30.0, "gradnorm_before_step": None, "gradnorm_after_step": None,
+           "config": {"workload": "w", "agents": 1, "precond": "auto", "precond_used_in_timed_steps": ["additive"]},
+           "roofline": None, "cpu_baseline": None, "also": None, "kitti_gnc": None,
+           "quality": {"us_per_tcg_iteration_rank0": 133.3, "cost_2f_trajectory": [], "to_tolerance": None}}
+    line = json.loads(bench.compact_line(out))
+    assert REQUIRED <= set(line) and line["roofline"] is None and line["cpu_baseline"] is None
+    assert line["value"] == 250.0 and line["ms_per_step"] == 4.0 and line["us_per_product"] == 133.3
+
+
 @pytest.mark.gpu
 def test_bench_multi_gpu_branch_runs_at_world_size_one():
     """The N > 1 branch of bench.py executed on ONE device exactly as the driver launches it for N > 1 (python -m
@@ -311,7 +366,7 @@ def test_bench_multi_gpu_branch_runs_at_world_size_one():
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr",
            "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "1", "--dist", "--workload",
            "grid:12x10x8", "--steps", "3", "--warmup", "1", "--settle", "1", "--no-cpu-baseline", "--no-secondary",
-           "--spmm-reps", "10"]
+           "--spmm-reps", "10", "--full"]
     p = subprocess.run(cmd, capture_output=True, text=True, cwd=ROOT, timeout=900)
     assert p.returncode == 0, p.stderr[-3000:]
     line, j = records(p.stdout)
@@ -332,7 +387,7 @@ def test_bench_two_ranks_on_one_gpu_through_the_peer_store():
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
            "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--transport", "ipc",
            "--workload", "grid:12x10x8", "--steps", "3", "--warmup", "1", "--settle", "1", "--no-cpu-baseline",
-           "--no-secondary", "--spmm-reps", "10"]
+           "--no-secondary", "--spmm-reps", "10", "--full"]
     p = subprocess.run(cmd, capture_output=True, text=True, cwd=ROOT, timeout=900,
                        env=dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0"))
     assert p.returncode == 0, p.stderr[-3000:]

@@ -3,7 +3,7 @@
 # (variant builds: make -C dpgo_amd/csrc OUT=../libdpgo_hip_X.so OBJDIR=build_X EXTRA=-DDPGO_...=...)
 W=$1; shift
 for rep in 1 2 3; do for L in "$@"; do
-DPGO_LIB=$PWD/$L timeout 300 python bench.py --workload $W --steps 10 --warmup 2 --no-cpu-baseline --no-secondary 2>/dev/null | grep '^DETAIL {' | tail -1 | cut -c8- > /tmp/b.json
+DPGO_LIB=$PWD/$L timeout 300 python bench.py --workload $W --steps 10 --warmup 2 --full --no-cpu-baseline --no-secondary 2>/dev/null | grep '^DETAIL {' | tail -1 | cut -c8- > /tmp/b.json
 python - <<PY
 import json
 j=json.load(open("/tmp/b.json")); t=j["quality"]["tcg_iterations_per_step_rank0"]; rf=j["roofline"]

@@ -54,7 +54,7 @@ PY
       env "${envs[@]}" timeout 900 python tools/ml_probe.py "$@" > "$OUT/$name.log" 2>&1
       grep -v "^dpgo_hip" "$OUT/$name.log" | cut -c1-400 | tail -40 ;;
     profile)
-      bash tools/profile_round.sh "$1" > "$OUT/profile_round.log" 2>&1
+      PROFILE_OUT=$PWD/$OUT bash tools/profile_round.sh "$1" > "$OUT/profile_round.log" 2>&1
       bash tools/profile_extra.sh "$1" > "$OUT/profile_extra.log" 2>&1
       tail -5 "$OUT/profile_round.log" | cut -c1-300 ;;
     py)

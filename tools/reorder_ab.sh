@@ -5,7 +5,7 @@ OUT=gpurun_out/${GPU_OUT:-run}; mkdir -p $OUT
 modes=$1; shift
 for m in $modes; do
   if [ "$m" == "off" ]; then export DPGO_REORDER=0; else export DPGO_REORDER=1 DPGO_REORDER_RUN=$m; fi
-  timeout 900 python bench.py --no-cpu-baseline --no-secondary --steps 50 "$@" 2> $OUT/ab_$m.err | grep '^{' | tail -1 > $OUT/ab_$m.json
+  timeout 900 python bench.py --full --no-cpu-baseline --no-secondary --steps 50 "$@" 2> $OUT/ab_$m.err | grep '^{' | tail -1 > $OUT/ab_$m.json
   python - $OUT/ab_$m.json $m <<'PY'
 import json, sys
 j = json.load(open(sys.argv[1])); rf = j["roofline"]
