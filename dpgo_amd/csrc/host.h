@@ -94,6 +94,11 @@ inline bool supported(int d, int r) {
       hipLaunchKernelGGL((KERNEL<D, R, 1>), dim3(GRID), dim3(kBlock), 0, (p)->stream, __VA_ARGS__);   \
   } while (0)
 
+// Caller pointers (include/dpgo_hip.h, "Alignment"): any 8-byte-aligned address is valid; the kernels that move own-tile
+// spans in 16-byte pieces (span_to_lds / span_from_lds, dbl2) run on 16-byte-aligned buffers only
+inline bool aligned8(const void* q) { return ((uintptr_t)q & 7) == 0; }
+inline bool aligned16(const void* q) { return ((uintptr_t)q & 15) == 0; }
+
 struct Bsr {
   int nrows = 0, ncols = 0, nnzb = 0;
   int32_t* rowptr = nullptr;
@@ -387,6 +392,7 @@ struct dpgo_problem_s {
     bool is_auto = false;
     const double* dinv = nullptr;
     double* own_x1 = nullptr;
+    double* staged_x = nullptr;  // the caller's iterate when it is not 16-byte aligned (the solve runs on own_x1)
     std::chrono::steady_clock::time_point t0;
     dpgo_ropt_result result{};
   } pending;
@@ -667,7 +673,8 @@ void sym_free(dpgo_problem_s* p);
 int sym_symbolic_setup(dpgo_problem_s* p);
 int sym_ensure(dpgo_problem_s* p, bool* usable);
 int launch_spmm_sym(dpgo_problem_s* p, const BsrSymDev& M, const double* V, const double* Gadd, double* OUT);
-int launch_spmm(dpgo_problem_s* p, const Bsr& M, const double* V, const double* Gadd, double* OUT, int nrows = -1);
+int launch_spmm(dpgo_problem_s* p, const Bsr& M, const double* V, const double* Gadd, double* OUT, int nrows = -1,
+                bool plain_only = false);
 bool outer_sym_enabled();
 int launch_grad(dpgo_problem_s* p, const double* X, double* RG, double* S, double* EG,
                 const DevState* st = nullptr, bool sym = false);

@@ -226,8 +226,8 @@ int launch_spmm_sym(dpgo_problem_s* p, const BsrSymDev& M, const double* V, cons
   return DPGO_OK;
 }
 
-int launch_spmm(dpgo_problem_s* p, const Bsr& M, const double* V, const double* Gadd, double* OUT, int nrows) {
-  if (&M == &p->Q && nrows < 0 && p->sym_wanted()) {
+int launch_spmm(dpgo_problem_s* p, const Bsr& M, const double* V, const double* Gadd, double* OUT, int nrows, bool plain_only) {
+  if (&M == &p->Q && nrows < 0 && !plain_only && p->sym_wanted()) {
     bool usable = false;
     CHK(sym_ensure(p, &usable));
     if (usable) return launch_spmm_sym(p, p->sym.dev(), V, Gadd, OUT);
@@ -794,7 +794,11 @@ int dpgo_problem_precondition(dpgo_problem_t p, int precond, double shift, const
 int dpgo_spmm_device(dpgo_problem_t p, const double* V_dev, double* OUT_dev, int add_G) {
   CHK(check_ready(p));
   if (!V_dev || !OUT_dev) return fail(DPGO_ERR_INVALID, "null pointer");
-  return launch_spmm(p, p->Q, V_dev, (add_G && p->has_G) ? p->G : nullptr, OUT_dev);
+  if (!aligned8(V_dev) || !aligned8(OUT_dev)) return fail(DPGO_ERR_INVALID, "V_dev / OUT_dev not 8-byte aligned");
+  // k_spmm_sym stores OUT in 16-byte pieces: a caller's buffer at an odd element offset takes the plain kernel (8-byte
+  // stores, same product to rounding)
+  const bool plain_only = !aligned16(V_dev) || !aligned16(OUT_dev);
+  return launch_spmm(p, p->Q, V_dev, (add_G && p->has_G) ? p->G : nullptr, OUT_dev, -1, plain_only);
 }
 
 

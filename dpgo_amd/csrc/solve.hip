@@ -1006,13 +1006,18 @@ int dpgo_optimize(dpgo_problem_t p, const dpgo_ropt_params* params, const double
 int dpgo_optimize_device(dpgo_problem_t p, const dpgo_ropt_params* params, double* X_dev, dpgo_ropt_result* result) {
   CHK(check_ready(p));
   if (!params || !X_dev || !result) return fail(DPGO_ERR_INVALID, "null pointer");
+  if (!aligned8(X_dev)) return fail(DPGO_ERR_INVALID, "X_dev not 8-byte aligned");
   // the caller's buffer IS the iterate for the duration of the call (no copies in or out): accepted steps are written
-  // into it by k_rtr_update, rejected ones leave it untouched
+  // into it by k_rtr_update, rejected ones leave it untouched -- unless it is not 16-byte aligned (the tCG and cycle
+  // kernels read the iterate in 16-byte pieces): then the solve runs on the handle's own x1, copied in and out
   double* own = p->x1;
-  p->x1 = X_dev;
+  const bool staged = !aligned16(X_dev);
+  if (staged) HIPC(hipMemcpyAsync(own, X_dev, p->vec_bytes(), hipMemcpyDeviceToDevice, p->stream));
+  else p->x1 = X_dev;
   const int rc = run_optimize(p, params, result);
   p->x1 = own;
   if (rc != DPGO_OK) return rc;
+  if (staged) HIPC(hipMemcpyAsync(X_dev, own, p->vec_bytes(), hipMemcpyDeviceToDevice, p->stream));
   HIPC(hipStreamSynchronize(p->stream));
   return DPGO_OK;
 }
@@ -1024,6 +1029,7 @@ int dpgo_optimize_device_begin(dpgo_problem_t p, const dpgo_ropt_params* params,
                                const double* nbr_tiles_dev) {
   CHK(check_ready(p));
   if (!params || !X_dev) return fail(DPGO_ERR_INVALID, "null pointer");
+  if (!aligned8(X_dev)) return fail(DPGO_ERR_INVALID, "X_dev not 8-byte aligned");
   if (p->pending.active) return fail(DPGO_ERR_STATE, "a solve of this handle is already in flight (dpgo_optimize_device_end)");
   if (nbr_tiles_dev) {  // PGOAgent::updateX: G from the neighbours' public poses first (same stream)
     if (!p->C.rowptr) return fail(DPGO_ERR_STATE, "G coupling not set");
@@ -1033,7 +1039,14 @@ int dpgo_optimize_device_begin(dpgo_problem_t p, const dpgo_ropt_params* params,
   auto& pd = p->pending;
   pd = dpgo_problem_s::Pending();
   pd.own_x1 = p->x1;
-  p->x1 = X_dev;
+  // (a caller's iterate that is not 16-byte aligned: the solve runs on the handle's own x1, copied in here and out when
+  // the solve has ended -- stream-ordered, as the solve itself)
+  if (!aligned16(X_dev)) {
+    pd.staged_x = X_dev;
+    HIPC(hipMemcpyAsync(p->x1, X_dev, p->vec_bytes(), hipMemcpyDeviceToDevice, p->stream));
+  } else {
+    p->x1 = X_dev;
+  }
   p->persist_stream_ordered = true;
   dpgo_ropt_result tmp;
   const int rc = run_optimize(p, params, &tmp, RUN_BEGIN);
@@ -1041,6 +1054,10 @@ int dpgo_optimize_device_begin(dpgo_problem_t p, const dpgo_ropt_params* params,
   if (rc != DPGO_OK || !pd.launched) {  // failed, or the solve is not a one-launch solve and has run to completion
     p->x1 = pd.own_x1;
     if (rc != DPGO_OK) return rc;
+    if (pd.staged_x) {
+      HIPC(hipMemcpyAsync(pd.staged_x, p->x1, p->vec_bytes(), hipMemcpyDeviceToDevice, p->stream));
+      HIPC(hipStreamSynchronize(p->stream));
+    }
     pd.result = tmp;
   }
   pd.active = true;
@@ -1062,6 +1079,7 @@ int dpgo_optimize_device_end(dpgo_problem_t p, dpgo_ropt_result* result) {
   const int rc = run_optimize(p, &pd.resolved, result, RUN_END);
   p->x1 = pd.own_x1;
   if (rc != DPGO_OK) return rc;
+  if (pd.staged_x) HIPC(hipMemcpyAsync(pd.staged_x, p->x1, p->vec_bytes(), hipMemcpyDeviceToDevice, p->stream));
   HIPC(hipStreamSynchronize(p->stream));
   return DPGO_OK;
 }
@@ -1188,8 +1206,10 @@ int dpgo_optimize_device_many(int count, const dpgo_problem_t* handles, const dp
                               dpgo_ropt_result* results) {
   if (count <= 0) return DPGO_OK;
   if (!params || !X_dev || !results) return fail(DPGO_ERR_INVALID, "null pointer");
-  for (int k = 0; k < count; ++k)
+  for (int k = 0; k < count; ++k) {
     if (!X_dev[k]) return fail(DPGO_ERR_INVALID, "null iterate");
+    if (!aligned8(X_dev[k])) return fail(DPGO_ERR_INVALID, "iterate not 8-byte aligned");
+  }
   return run_many(count, handles, after_stream, [&](int k) -> int {
     dpgo_problem_s* p = handles[k];
     if (nbr_tiles_dev && nbr_tiles_dev[k]) {  // PGOAgent::updateX: G from the neighbours' public poses first
@@ -1198,9 +1218,12 @@ int dpgo_optimize_device_many(int count, const dpgo_problem_t* handles, const dp
       p->has_G = true;
     }
     double* own = p->x1;
-    p->x1 = X_dev[k];
+    const bool staged = !aligned16(X_dev[k]);  // (as dpgo_optimize_device)
+    if (staged) HIPC(hipMemcpyAsync(own, X_dev[k], p->vec_bytes(), hipMemcpyDeviceToDevice, p->stream));
+    else p->x1 = X_dev[k];
     const int rc = run_optimize(p, params, &results[k]);
     p->x1 = own;
+    if (rc == DPGO_OK && staged) HIPC(hipMemcpyAsync(X_dev[k], own, p->vec_bytes(), hipMemcpyDeviceToDevice, p->stream));
     return rc;
   });
 }

@@ -354,6 +354,17 @@ int dpgo_problem_rie_hess(dpgo_problem_t h, const double* X, const double* V, do
 int dpgo_problem_precondition(dpgo_problem_t h, int precond, double shift, const double* X,
                               const double* V, double* Z);
 
+/* ---- Alignment of caller device pointers ----
+ * Every device pointer a caller passes (iterates, products, neighbour tiles, witnesses, G) needs the alignment of a double:
+ * 8 bytes, so that a float64 view at any element offset of a larger buffer is a valid argument (dpgo_spmm_device and the
+ * dpgo_optimize_device entries return DPGO_ERR_INVALID before any launch for a pointer that is not).  Entries whose kernels
+ * would move the caller's buffer in 16-byte pieces take another route when it is not 16-byte aligned:
+ *   dpgo_spmm_device                        the plain-storage product (8-byte stores) instead of the symmetric storage's;
+ *   dpgo_optimize_device[_begin | _many]    the solve runs on the handle's own iterate buffer, copied in before it and
+ *                                           out after it (device to device, on the handle's stream);
+ * the results equal those of a 16-byte-aligned call (the product to rounding of the other storage; bitwise on the plain
+ * storage).  The other device entries read caller buffers in 8-byte elements only and need nothing. */
+
 /* ---- QuadraticOptimizer::optimize (src/QuadraticOptimizer.cpp:26-48) ----
  * host flavour: X0 -> Xopt are host matrices (H2D + solve + D2H);
  * device flavour: X is a device matrix updated in place (nothing but scalars crosses PCIe). */

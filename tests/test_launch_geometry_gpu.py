@@ -1,0 +1,505 @@
+"""Launch geometry of the SpMM-family kernels against fp64 references: every (d, r) at 1, 2 and 4 lane groups per pose
+(DPGO_SPLIT) on pose counts around the workgroup tile, forced launch caps (DPGO_GRID_*) on both tile-walk branches of
+tile_iter (kernels/common.h), and caller pointers at an 8-byte offset (include/dpgo_hip.h, "Alignment").
+
+Every output leaves through a buffer with a guard region of at least one workgroup tile before and after it: the result
+region is prefilled with NaN, the guards with a sentinel bit pattern; a kernel that skips a tile leaves NaN, one that
+stores past pose n - 1 changes a guard.  Inputs that stay on the device sit between NaN guards, so that a read past the
+last pose poisons the result.  Tolerances are the parity suite's: element-wise 1e-11, scalars 1e-12, Q*V 1e-13 against
+scipy's CSR product.
+"""
+import contextlib
+import ctypes as C
+import os
+
+import numpy as np
+import pytest
+
+import certificate_reference as ref
+from conftest import DATA, tiles_to_matrix, to_product_measurements
+from test_parity_gpu import RTOL_ELEM, _random_graph, relerr
+
+pytestmark = pytest.mark.gpu
+
+DR = [(2, 2), (2, 3), (2, 4), (2, 5), (3, 3), (3, 4), (3, 5), (3, 6)]  # DPGO_FOR_DR (csrc/host.h)
+SPLITS = (1, 2, 4)
+SENTINEL = 0x7FF4DEADBEEF0BAD  # a signalling-NaN bit pattern no kernel writes
+GEOMETRY_VARS = ("DPGO_SPLIT", "DPGO_SPMM_SYMMETRIC", "DPGO_GRID_UPDATE", "DPGO_GRID_HESS", "DPGO_GRID_HESS_SYM",
+                 "DPGO_GRID_RETRACT", "DPGO_GRID_OUTER_SYM", "DPGO_GRID_SPMM_SYM", "DPGO_GRID_ML", "DPGO_COARSE_GRID",
+                 "DPGO_DENSE_CHUNK", "DPGO_PERSIST")
+
+
+def tile_poses(d, split):
+    """Poses per workgroup tile of a <D, R, SPLIT> kernel (Geo::P, kernels/common.h)."""
+    return 4 * (64 // ((d + 1) * split))
+
+
+def pose_counts(d, split):
+    P = tile_poses(d, split)
+    return sorted({1, 2, P - 1, P, P + 1, 17 * P + 3})  # (17 P + 3: 18 tiles, uneven XCD eighths)
+
+
+@contextlib.contextmanager
+def library_options(env):
+    """The library's switches set to `env` (every geometry switch not in it unset), read again by dpgo_options_reload;
+    handles created inside see them.  Restored whatever happens."""
+    import dpgo_amd
+    lib = dpgo_amd.lib.load()
+    names = set(GEOMETRY_VARS) | set(env)
+    saved = {k: os.environ.get(k) for k in names}
+    try:
+        for k in names:
+            os.environ.pop(k, None)
+        os.environ.update(env)
+        dpgo_amd.lib.check(lib.dpgo_options_reload())
+        text = dpgo_amd.lib.describe_options()
+        assert all(("%s=%s [set]" % kv) in text for kv in env.items()), (env, text)
+        yield lib
+    finally:
+        for k, v in saved.items():
+            if v is None:
+                os.environ.pop(k, None)
+            else:
+                os.environ[k] = v
+        lib.dpgo_options_reload()
+
+
+class Handle:
+    """A problem handle on the C ABI with Q set from an oracle BSR (any symmetric block pattern with diagonal blocks)."""
+
+    def __init__(self, lib, Qb, r, d):
+        import dpgo_amd.lib as L
+        self.lib, self.L, self.r, self.d, self.n = lib, L, r, d, Qb.n
+        self.T = (d + 1) * r
+        self.h = L._P()
+        L.check(lib.dpgo_problem_create(C.byref(self.h), r, d, Qb.n, 0))
+        L.check(lib.dpgo_problem_set_Q_bsr(self.h, Qb.nnzb, L.ptr(Qb.rowptr), L.ptr(Qb.colidx), L.ptr(Qb.vals)))
+
+    def close(self):
+        if self.h:
+            self.lib.dpgo_problem_destroy(self.h)
+            self.h = None
+
+    def describe(self):
+        buf = C.create_string_buffer(32768)
+        self.L.check(self.lib.dpgo_problem_describe(self.h, buf, len(buf)))
+        return buf.value.decode()
+
+    def out(self, guard):
+        return Guarded(self.n * self.T, guard, device=False)
+
+    # host-pointer entries: X, V as [n, d+1, r] tiles (the bytes of the r x (d+1)n column-major matrix)
+    def f(self, X):
+        v = C.c_double()
+        self.L.check(self.lib.dpgo_problem_f(self.h, self.L.ptr(np.ascontiguousarray(X)), C.byref(v)))
+        return v.value
+
+    def rie_grad_norm(self, X):
+        v = C.c_double()
+        self.L.check(self.lib.dpgo_problem_rie_grad_norm(self.h, self.L.ptr(np.ascontiguousarray(X)), C.byref(v)))
+        return v.value
+
+    def vec(self, entry, guard, *args):
+        o = self.out(guard)
+        self.L.check(getattr(self.lib, entry)(self.h, *[self.L.ptr(np.ascontiguousarray(a)) for a in args], o.ptr()))
+        return o.result((self.n, self.d + 1, self.r))
+
+    def jacobi(self, X, V, guard):
+        o = self.out(guard)
+        self.L.check(self.lib.dpgo_problem_precondition(self.h, self.L.PRECOND_BLOCK_JACOBI, 0.1,
+                                                        self.L.ptr(np.ascontiguousarray(X)),
+                                                        self.L.ptr(np.ascontiguousarray(V)), o.ptr()))
+        return o.result((self.n, self.d + 1, self.r))
+
+    def certificate_apply(self, X, V, guard):
+        return self.vec("dpgo_problem_certificate_apply", guard, X, V)
+
+    def set_G(self, G):
+        self.L.check(self.lib.dpgo_problem_set_G(self.h, self.L.ptr(None if G is None else np.ascontiguousarray(G))))
+
+    # device-pointer entries
+    def spmm_device(self, Vd, guard, add_G=False):
+        o = Guarded(self.n * self.T, guard, device=True)
+        self.L.check(self.lib.dpgo_spmm_device(self.h, self.L.ptr(Vd), o.ptr(), int(add_G)))
+        return o.result((self.n, self.d + 1, self.r))
+
+    def eval_device(self, Xd):
+        f, g = C.c_double(), C.c_double()
+        self.L.check(self.lib.dpgo_problem_eval_device(self.h, self.L.ptr(Xd), C.byref(f), C.byref(g)))
+        return f.value, g.value
+
+    def eval_terms_device(self, Xd):
+        a, b, c = C.c_double(), C.c_double(), C.c_double()
+        self.L.check(self.lib.dpgo_problem_eval_terms_device(self.h, self.L.ptr(Xd), C.byref(a), C.byref(b), C.byref(c)))
+        return a.value, b.value, c.value
+
+
+class Guarded:
+    """`size` doubles between two guards of `guard` doubles (host numpy or device torch): the body prefilled with NaN, the
+    guards with SENTINEL.  result() checks both and returns the body."""
+
+    def __init__(self, size, guard, device, body=None, guard_nan=False):
+        self.size, self.guard = size, guard
+        host = np.empty(size + 2 * guard, dtype=np.float64)
+        bits = host.view(np.uint64)
+        bits[:] = np.uint64(SENTINEL)
+        host[guard:guard + size] = np.nan if body is None else np.asarray(body, dtype=np.float64).reshape(-1)
+        if guard_nan:
+            host[:guard] = np.nan
+            host[guard + size:] = np.nan
+        if device:
+            import torch
+            self.buf = torch.from_numpy(host).to("cuda")
+            self.body = self.buf[guard:guard + size]
+            torch.cuda.synchronize()  # (the library's launches run on the handle's own stream)
+        else:
+            self.buf = host
+            self.body = host[guard:guard + size]
+
+    def ptr(self):
+        import dpgo_amd.lib as L
+        return L.ptr(self.body)
+
+    def result(self, shape):
+        if not isinstance(self.buf, np.ndarray):
+            import torch
+            torch.cuda.synchronize()
+            host = self.buf.cpu().numpy()
+        else:
+            host = self.buf
+        bits = host.view(np.uint64)
+        g = self.guard
+        assert np.all(bits[:g] == np.uint64(SENTINEL)), "store in front of the output"
+        assert np.all(bits[g + self.size:] == np.uint64(SENTINEL)), "store behind the output"
+        body = host[g:g + self.size]
+        assert not np.isnan(body).any(), "output entries not written: %d" % int(np.isnan(body).sum())
+        return body.reshape(shape).copy()
+
+
+def device_input(a, guard):
+    """A device copy of `a` between NaN guards (a read past the last pose poisons the result)."""
+    return Guarded(a.size, guard, device=True, body=a, guard_nan=True).body
+
+
+def guard_of(d, r):
+    g = tile_poses(d, 1) * (d + 1) * r + 2
+    return g + (g & 1)  # (even: the body keeps the buffer's 16-byte alignment)
+
+
+_GRAPHS = {}
+
+
+def graph_Q(oracle, d, n):
+    """(Q, T): the block matrix of a random pose graph (_random_graph: odometry chain, loop closures, one hub row longer
+    than the gather core's preloaded index window from 64 poses on) and its ground truth; n = 1: the first diagonal block
+    of the two-pose graph."""
+    key = (d, n)
+    if key not in _GRAPHS:
+        if n == 1:
+            Q2, T2 = graph_Q(oracle, d, 2)
+            b = d + 1
+            Qb = oracle.BSR(1, b, np.array([0, 1]), np.array([0]), Q2.vals[:1].copy())
+            _GRAPHS[key] = (Qb, T2[:1].copy())
+        else:
+            hub = 40 if n >= 64 else max(0, n - 4) // 2
+            n_lc = n // 2 if n >= 8 else 0  # (_random_graph needs room for loop closures j > i + 1)
+            om, T, _ = _random_graph(oracle, d, n, n_lc, hub, seed=700 + 10 * n + d)
+            _GRAPHS[key] = (oracle.construct_Q(n, d, om), T)
+    return _GRAPHS[key]
+
+
+def point(oracle, T, d, r, seed):
+    n = T.shape[0]
+    rng = np.random.default_rng(seed)
+    X = oracle.polar_project(oracle.lift(T, r) + 0.1 * rng.standard_normal((n, d + 1, r)), d)
+    V = rng.standard_normal((n, d + 1, r))
+    G = 0.1 * rng.standard_normal((n, d + 1, r))
+    return X, V, G
+
+
+def check_against_references(oracle, h, Qb, X, V, G, guard):
+    """Every evaluation of the handle against the oracle / scipy in fp64; returns the element-wise outputs."""
+    import torch
+    d, r, n = h.d, h.r, h.n
+    N = n * (d + 1)
+    Qs = ref.sparse_Q(Qb)
+    op = oracle.QuadraticProblem(Qb, None, r, d, precond="jacobi")
+    QV = (Qs @ V.reshape(N, r)).reshape(V.shape)
+    out = {}
+    Vd = device_input(V, guard)
+    Xd = device_input(X, guard)
+    out["QV"] = h.spmm_device(Vd, guard)
+    assert relerr(out["QV"], QV) < 1e-13
+    assert abs(h.f(X) - op.f(X)) <= 1e-12 * abs(op.f(X))
+    out["EucGrad"] = h.vec("dpgo_problem_euc_grad", guard, X)
+    assert relerr(out["EucGrad"], op.euc_grad(X)) < RTOL_ELEM
+    out["EucHess"] = h.vec("dpgo_problem_euc_hess", guard, V)
+    assert relerr(out["EucHess"], QV) < 1e-13
+    out["RieGrad"] = h.vec("dpgo_problem_rie_grad", guard, X)
+    assert relerr(out["RieGrad"], op.rie_grad(X)) < RTOL_ELEM
+    gn = op.rie_grad_norm(X)
+    assert abs(h.rie_grad_norm(X) - gn) <= 1e-12 * gn
+    S = op.sym_ytg(X, op.euc_grad(X))
+    Vt = oracle.tangent_project(X, V, d)
+    out["RieHess"] = h.vec("dpgo_problem_rie_hess", guard, X, Vt)
+    assert relerr(out["RieHess"], op.rie_hess(X, S, Vt)) < RTOL_ELEM
+    out["Jacobi"] = h.jacobi(X, V, guard)
+    assert relerr(out["Jacobi"], op.precondition(X, V)) < RTOL_ELEM
+    f, g = h.eval_device(Xd)
+    assert abs(f - op.f(X)) <= 1e-12 * abs(op.f(X)) and abs(g - gn) <= 1e-12 * gn
+    xqx, xg, g2 = h.eval_terms_device(Xd)
+    assert abs(xqx - 2 * op.f(X)) <= 1e-12 * abs(2 * op.f(X)) and xg == 0.0 and abs(g2 - gn * gn) <= 1e-12 * gn * gn
+    Xm, Vm = tiles_to_matrix(X), tiles_to_matrix(V)
+    out["CertApply"] = h.certificate_apply(X, V, guard)
+    want = ref.certificate_apply(Qs, Xm, Vm, d)
+    assert np.linalg.norm(tiles_to_matrix(out["CertApply"]) - want) <= 1e-12 * np.linalg.norm(want)
+    # with a linear term G (dpgo_problem_set_G): f(X) = 0.5 <XQ, X> + <X, G>
+    h.set_G(G)
+    opG = oracle.QuadraticProblem(Qb, G, r, d, precond="jacobi")
+    out["QV+G"] = h.spmm_device(Vd, guard, add_G=True)
+    assert relerr(out["QV+G"], QV + G) < 1e-13
+    assert abs(h.f(X) - opG.f(X)) <= 1e-12 * abs(opG.f(X))
+    out["EucGradG"] = h.vec("dpgo_problem_euc_grad", guard, X)
+    assert relerr(out["EucGradG"], opG.euc_grad(X)) < RTOL_ELEM
+    out["RieGradG"] = h.vec("dpgo_problem_rie_grad", guard, X)
+    assert relerr(out["RieGradG"], opG.rie_grad(X)) < RTOL_ELEM
+    gnG = opG.rie_grad_norm(X)
+    f, g = h.eval_device(Xd)
+    assert abs(f - opG.f(X)) <= 1e-12 * abs(opG.f(X)) and abs(g - gnG) <= 1e-12 * gnG
+    xqx, xg, g2 = h.eval_terms_device(Xd)
+    want_xg = float(np.sum(X * G))
+    assert abs(xqx - 2 * op.f(X)) <= 1e-12 * abs(2 * op.f(X)) and abs(xg - want_xg) <= 1e-12 * np.sum(np.abs(X * G))
+    assert abs(g2 - gnG * gnG) <= 1e-12 * gnG * gnG
+    h.set_G(None)
+    torch.cuda.synchronize()
+    return out
+
+
+# ---------------------------------------------------------------- A. every (d, r) x split x pose count
+# launch caps of the matrix: none (grid = tiles up to the resident count), small ones (the plain-stride walk takes several
+# trips on every pose count above the cap) and 16 / 17 (the XCD-eighths walk with uneven eighths on 17 P + 3 poses)
+MATRIX_CAPS = [{}, {"DPGO_GRID_UPDATE": "3", "DPGO_GRID_HESS": "2"}, {"DPGO_GRID_UPDATE": "17", "DPGO_GRID_HESS": "16"}]
+@pytest.mark.parametrize("d,r", DR)
+def test_every_split_and_ragged_size_matches_fp64_references(oracle, d, r):
+    """DPGO_SPLIT = 1, 2, 4 (a fresh handle per split and cap set, MATRIX_CAPS) on n = 1, 2, P - 1, P, P + 1, 17 P + 3
+    poses, P the split's workgroup tile: k_spmm, k_grad, k_hess, k_precond and k_cert_apply through every evaluation entry, with and without G,
+    against the oracle and scipy; guarded outputs.  In 2-D, r = 3 and r = 5 give odd tile sizes (generic stores), the
+    other pairs the span path."""
+    guard = guard_of(d, r)
+    for split, caps in [(s, c) for s in SPLITS for c in MATRIX_CAPS]:
+        with library_options(dict(caps, DPGO_SPLIT=str(split))) as lib:
+            for n in pose_counts(d, split):
+                Qb, T = graph_Q(oracle, d, n)
+                X, V, G = point(oracle, T, d, r, seed=n + 31 * r)
+                h = Handle(lib, Qb, r, d)
+                try:
+                    assert "lane groups per pose %d;" % split in h.describe()
+                    check_against_references(oracle, h, Qb, X, V, G, guard)
+                except AssertionError as e:
+                    raise AssertionError("d=%d r=%d split=%d n=%d caps=%s: %s" % (d, r, split, n, caps, e)) from e
+                finally:
+                    h.close()
+
+
+# ---------------------------------------------------------------- B. forced launch caps
+CAP_SETS = [{k: str(c) for k in ("DPGO_GRID_UPDATE", "DPGO_GRID_HESS", "DPGO_GRID_HESS_SYM", "DPGO_GRID_OUTER_SYM",
+                                  "DPGO_GRID_SPMM_SYM", "DPGO_GRID_ML", "DPGO_GRID_RETRACT")} for c in (1, 7, 15, 16, 17, 100)]
+MIXED_CAPS = {"DPGO_GRID_UPDATE": "13", "DPGO_GRID_HESS": "5", "DPGO_GRID_HESS_SYM": "23", "DPGO_GRID_OUTER_SYM": "9",
+              "DPGO_GRID_SPMM_SYM": "31", "DPGO_GRID_ML": "19", "DPGO_GRID_RETRACT": "3"}
+CAP_SETS.append(MIXED_CAPS)
+
+
+def _workload(oracle, name):
+    if name.startswith("grid:"):
+        om, n, _ = oracle.synthetic_grid(*[int(v) for v in name[5:].split("x")], seed=0)
+    else:
+        om, n = oracle.read_g2o(os.path.join(DATA, name + ".g2o"))
+    return om, n
+
+
+@pytest.mark.parametrize("name,split,storage", [("smallGrid3D", 4, "plain"), ("grid:40x40x25", 1, "plain"),
+                                                ("grid:40x40x25", 1, "symmetric")])
+def test_forced_launch_caps_keep_elementwise_outputs_bitwise(oracle, name, split, storage):
+    """At a fixed split and storage every pose's output is computed by the same lanes whatever workgroup runs it: Q V,
+    EucHessianEta, RieGrad, RieHessianEta, block-Jacobi and V C(X) are BIT-identical under every cap set -- 1, 7, 15
+    (plain stride), 16, 17, 100 (XCD eighths, uneven) and a mixed set whose kernels write and reduce their partial sums on
+    different grids -- to the uncapped run; f and |rgrad| (summation order changes with the grid) match the oracle."""
+    om, n = _workload(oracle, name)
+    d, r = om.d, 5
+    Qb = oracle.construct_Q(n, d, om)
+    Ttrue = np.zeros((n, d + 1, d))
+    Ttrue[:, :d, :] = np.eye(d)
+    X, V, _ = point(oracle, Ttrue, d, r, seed=5)
+    Vt = oracle.tangent_project(X, V, d)
+    op = oracle.QuadraticProblem(Qb, None, r, d, precond="jacobi")
+    fo, gno = op.f(X), op.rie_grad_norm(X)
+    guard = guard_of(d, r)
+    base_env = {"DPGO_SPLIT": str(split), "DPGO_SPMM_SYMMETRIC": "1" if storage == "symmetric" else "0",
+                "DPGO_PERSIST": "0"}
+    Vd = device_input(V, guard)
+    base = None
+    for caps in [{}] + CAP_SETS:
+        with library_options(dict(base_env, **caps)) as lib:
+            h = Handle(lib, Qb, r, d)
+            try:
+                text = h.describe()
+                assert "lane groups per pose %d;" % split in text
+                in_use = C.c_int(-1)
+                h.L.check(lib.dpgo_problem_set_spmm_variant(h.h, 0, C.byref(in_use)))  # DPGO_SPMM_AUTO
+                assert in_use.value == (2 if storage == "symmetric" else 1), (storage, in_use.value)
+                out = {"QV": h.spmm_device(Vd, guard), "EucHess": h.vec("dpgo_problem_euc_hess", guard, V),
+                       "RieGrad": h.vec("dpgo_problem_rie_grad", guard, X),
+                       "RieHess": h.vec("dpgo_problem_rie_hess", guard, X, Vt), "Jacobi": h.jacobi(X, V, guard),
+                       "CertApply": h.certificate_apply(X, V, guard)}
+                assert abs(h.f(X) - fo) <= 1e-12 * abs(fo), caps
+                assert abs(h.rie_grad_norm(X) - gno) <= 1e-12 * gno, caps
+            finally:
+                h.close()
+        if base is None:
+            base = out
+            assert relerr(out["QV"], op.euc_hess(V)) < 1e-13
+            assert relerr(out["RieGrad"], op.rie_grad(X)) < RTOL_ELEM
+            assert relerr(out["Jacobi"], op.precondition(X, V)) < RTOL_ELEM
+        else:
+            for k, v in out.items():
+                assert np.array_equal(v.view(np.uint64), base[k].view(np.uint64)), (caps, k)
+
+
+def test_certificate_under_split_2_and_caps_matches_default(oracle):
+    """dpgo_problem_certify on solved smallGrid3D at 2 lane groups per pose and under the mixed cap set (multi-launch
+    solve): the default run's status, lambda_min to 1e-10."""
+    import dpgo_amd
+    om, n = oracle.read_g2o(os.path.join(DATA, "smallGrid3D.g2o"))
+    d, r = om.d, 5
+    params = dict(eta=1e-6, tol_rel=1e-9, max_iterations=2000, precond="jacobi", seed=3)
+
+    def problem():
+        pg = dpgo_amd.PoseGraph(0, r, d)
+        pg.setMeasurements(to_product_measurements(om))
+        prob = dpgo_amd.QuadraticProblem(pg)
+        prob.setPersistent(False)
+        return prob
+
+    with library_options({}):
+        prob = problem()
+        X = tiles_to_matrix(oracle.lift(oracle.chordal_initialization(om, n), r))
+        opt = dpgo_amd.QuadraticOptimizer(prob, dpgo_amd.ROptParameters(precond="jacobi", gradnorm_tol=1e-8,
+                                                                         RTR_iterations=200))
+        for _ in range(5):
+            X = opt.optimize(X)
+            if opt.getOptResult().gradNormOpt <= 1e-8:
+                break
+        want = prob.certify(X, **params)
+        del opt, prob
+    for env in ({"DPGO_SPLIT": "2"}, dict(MIXED_CAPS, DPGO_SPLIT="2")):
+        with library_options(env):
+            prob = problem()
+            assert "lane groups per pose 2;" in prob.describe()
+            got = prob.certify(X, **params)
+            assert got.status == want.status, (env, got.status, want.status)
+            assert abs(got.lambda_min - want.lambda_min) <= 1e-10, (env, got.lambda_min, want.lambda_min)
+            del prob
+
+
+# ---------------------------------------------------------------- C. caller pointers at an 8-byte offset
+@pytest.mark.parametrize("name,storage", [("smallGrid3D", "auto"), ("grid:40x40x25", "symmetric")])
+def test_spmm_device_at_an_odd_element_offset(oracle, name, storage):
+    """dpgo_spmm_device on float64 views at element offset 1 (8-byte, not 16-byte aligned): on the symmetric storage the
+    product takes the plain kernel (the symmetric one stores 16-byte pieces), so it is BITWISE the aligned plain product;
+    pointers that are not 8-byte aligned are refused."""
+    import torch
+    import dpgo_amd.lib as L
+    om, n = _workload(oracle, name)
+    d, r = om.d, 5
+    Qb = oracle.construct_Q(n, d, om)
+    T = (d + 1) * r
+    V = np.random.default_rng(3).standard_normal((n, d + 1, r))
+    Qs = ref.sparse_Q(Qb)
+    want = (Qs @ V.reshape(-1, r)).reshape(V.shape)
+    env = {"DPGO_SPMM_SYMMETRIC": "1"} if storage == "symmetric" else {}
+    with library_options(env) as lib:
+        h = Handle(lib, Qb, r, d)
+        try:
+            if storage == "symmetric":
+                in_use = C.c_int(-1)
+                L.check(lib.dpgo_problem_set_spmm_variant(h.h, 0, C.byref(in_use)))
+                assert in_use.value == 2
+            big_v = torch.zeros(n * T + 2, dtype=torch.float64, device="cuda")
+            big_o = torch.full((n * T + 2,), float("nan"), dtype=torch.float64, device="cuda")
+            big_v[1:1 + n * T] = torch.from_numpy(V.reshape(-1))
+            assert big_v[1:].data_ptr() % 16 == 8 and big_o[1:].data_ptr() % 16 == 8
+            aligned_v = torch.from_numpy(V.reshape(-1)).to("cuda")
+            aligned_o = torch.empty_like(aligned_v)
+            torch.cuda.synchronize()
+            L.check(lib.dpgo_spmm_device(h.h, L.ptr(aligned_v), L.ptr(aligned_o), 0))
+            L.check(lib.dpgo_spmm_device(h.h, L.ptr(big_v[1:]), L.ptr(big_o[1:]), 0))
+            torch.cuda.synchronize()
+            odd = big_o[1:1 + n * T].cpu().numpy()
+            assert np.isnan(big_o[0].item()) and np.isnan(big_o[-1].item())
+            assert relerr(odd.reshape(V.shape), want) < 1e-13
+            if storage == "symmetric":  # the plain product, bit for bit
+                L.check(lib.dpgo_problem_set_spmm_variant(h.h, 1, C.byref(in_use)))  # DPGO_SPMM_PLAIN
+                L.check(lib.dpgo_spmm_device(h.h, L.ptr(aligned_v), L.ptr(aligned_o), 0))
+                torch.cuda.synchronize()
+            assert np.array_equal(odd.view(np.uint64), aligned_o.cpu().numpy().view(np.uint64))
+            bad = big_v.data_ptr() + 4  # (never dereferenced: refused on the host)
+            assert lib.dpgo_spmm_device(h.h, bad, L.ptr(aligned_o), 0) == L.ERR_INVALID
+            assert lib.dpgo_spmm_device(h.h, L.ptr(aligned_v), bad, 0) == L.ERR_INVALID
+        finally:
+            h.close()
+
+
+def test_device_solves_at_an_odd_element_offset(oracle):
+    """dpgo_optimize_device, _begin / _end and _many on an iterate at element offset 1 (d = 3, r = 5: even tile size, the
+    16-byte span kernels of tCG and the V-cycle): the solve runs on the handle's own buffer, copied in and out, and gives
+    the aligned call's result; the entries that read the caller's buffer in 8-byte elements (eval, certify) agree
+    bitwise.  A pointer that is not 8-byte aligned is refused."""
+    import torch
+    import dpgo_amd
+    import dpgo_amd.lib as L
+    om, n = oracle.read_g2o(os.path.join(DATA, "smallGrid3D.g2o"))
+    d, r = om.d, 5
+    T = (d + 1) * r
+    X0 = np.ascontiguousarray(oracle.lift(oracle.chordal_initialization(om, n), r))
+    pg = dpgo_amd.PoseGraph(0, r, d)
+    pg.setMeasurements(to_product_measurements(om))
+    results = {}
+    for precond in ("multilevel", "jacobi"):
+        for persistent in (False, True):
+            prob = dpgo_amd.QuadraticProblem(pg)
+            prob.setPersistent(persistent)
+            opt = dpgo_amd.QuadraticOptimizer(prob, dpgo_amd.ROptParameters(precond=precond))
+            aligned = torch.from_numpy(X0.reshape(-1)).to("cuda")
+            torch.cuda.synchronize()
+            ra = opt.optimizeDevice(aligned)
+            big = torch.full((n * T + 2,), float("nan"), dtype=torch.float64, device="cuda")
+            odd = big[1:1 + n * T]
+            assert odd.data_ptr() % 16 == 8
+            for entry in ("device", "begin_end", "many"):
+                odd.copy_(torch.from_numpy(X0.reshape(-1)))
+                torch.cuda.synchronize()
+                if entry == "device":
+                    ro = opt.optimizeDevice(odd)
+                elif entry == "begin_end":
+                    opt.optimizeDeviceBegin(odd)
+                    ro = opt.optimizeDeviceEnd()
+                else:
+                    ro = dpgo_amd.solver.optimize_device_many([opt], [odd])[0]
+                torch.cuda.synchronize()
+                assert np.isnan(big[0].item()) and np.isnan(big[-1].item()), entry
+                xo, xa = odd.cpu().numpy(), aligned.cpu().numpy()
+                assert (ro.tcg_iterations, ro.rtr_iterations) == (ra.tcg_iterations, ra.rtr_iterations), (precond, entry)
+                assert abs(ro.fOpt - ra.fOpt) <= 1e-9 * abs(ra.fOpt), (precond, entry)
+                assert relerr(xo, xa) < 1e-6, (precond, entry)
+                results[(precond, persistent, entry)] = ro.fOpt
+            # eval and certify read X in 8-byte elements: bitwise the aligned call
+            copy = odd.clone()
+            torch.cuda.synchronize()
+            assert prob.evalDevice(odd) == prob.evalDevice(copy)
+            assert prob.evalTermsDevice(odd) == prob.evalTermsDevice(copy)
+            bad = big.data_ptr() + 4  # (never dereferenced: refused on the host)
+            cp, cr = L.RoptParamsC(), L.RoptResultC()
+            prob._lib.dpgo_ropt_params_default(C.byref(cp))
+            assert prob._lib.dpgo_optimize_device(prob.handle, C.byref(cp), bad, C.byref(cr)) == L.ERR_INVALID
+            assert prob._lib.dpgo_optimize_device_begin(prob.handle, C.byref(cp), bad, None) == L.ERR_INVALID
+            del opt, prob

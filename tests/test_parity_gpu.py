@@ -2536,6 +2536,17 @@ SWITCH_SETS = [
     ({"DPGO_ML_SETUP_SERIAL": "1", "DPGO_GJ_MFMA": "0"}, "oracle"),  # round-3 set-up kernels, FMA rank-64 updates
     ({"DPGO_ML_DENSE_SYM": "1"}, "oracle"),        # dense level from the packed lower triangle on the matrix cores
     ({"DPGO_COARSE_NODES": "1", "DPGO_COARSE_NT": "1"}, "oracle"),  # one node per workgroup, non-temporal inverse
+    ({"DPGO_SPLIT": "1"}, "oracle"),               # lane groups per pose of the SpMM-family kernels, whatever the size
+    ({"DPGO_SPLIT": "2"}, "oracle"),
+    ({"DPGO_SPLIT": "4"}, "oracle"),
+    # forced launch caps, every kernel on its own grid (partials written and reduced on different grids): plain-stride tile
+    # walk on small caps, the packed dense level in one-tile chunks, the coarse prolongation in several rounds
+    ({"DPGO_GRID_UPDATE": "7", "DPGO_GRID_HESS": "3", "DPGO_GRID_RETRACT": "5", "DPGO_GRID_ML": "11",
+      "DPGO_COARSE_GRID": "2", "DPGO_ML_DENSE_SYM": "1", "DPGO_DENSE_CHUNK": "1"}, "oracle"),
+    # ... XCD-eighths tile walk with uneven eighths, on the symmetric storage where the block can run it
+    ({"DPGO_SPMM_SYMMETRIC": "1", "DPGO_GRID_UPDATE": "17", "DPGO_GRID_HESS": "100", "DPGO_GRID_HESS_SYM": "16",
+      "DPGO_GRID_OUTER_SYM": "23", "DPGO_GRID_SPMM_SYM": "33", "DPGO_GRID_RETRACT": "19", "DPGO_GRID_ML": "16",
+      "DPGO_COARSE_GRID": "9", "DPGO_DENSE_CHUNK": "3"}, "oracle"),
 ]
 
 
@@ -2549,7 +2560,9 @@ def test_kernel_selecting_switches_match_oracle(oracle, workload):
     iterate 1e-6.  Switches that must not change a single bit (where the residual test sits, how the launches are
     enqueued) are also compared bitwise with the default run.  The library reads its switches once; the test reloads
     them (dpgo_options_reload) and builds a fresh handle per set.  DPGO_ASYNC_SWEEP lives in the Python agent layer:
-    test_stream_ordered_sweep_matches_phase_by_phase."""
+    test_stream_ordered_sweep_matches_phase_by_phase.  The launch geometry -- lane groups per pose (DPGO_SPLIT) and the
+    launch caps (DPGO_GRID_*, DPGO_COARSE_GRID, DPGO_DENSE_CHUNK) -- is flipped here too; kernel by kernel it is tested in
+    tests/test_launch_geometry_gpu.py."""
     import hashlib
     import torch
     import dpgo_amd
