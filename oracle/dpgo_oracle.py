@@ -989,7 +989,9 @@ def tcg(problem: QuadraticProblem, X, g, S, Delta, max_inner, theta=1.0, kappa=0
             eta = eta + tau * delta
             status = TCG_NEGCURV if d_Hd < 0 else TCG_EXCREGION
             if trace is not None:
-                trace.append(dict(j=j, d_Hd=d_Hd, alpha=alpha, tau=tau, status=status))
+                # (norm_d, norm_Hd: the scale against which a negative d_Hd is "beyond round-off")
+                trace.append(dict(j=j, d_Hd=d_Hd, alpha=alpha, tau=tau, status=status,
+                                  norm_d=math.sqrt(dot(delta, delta)), norm_Hd=math.sqrt(dot(Hd, Hd))))
             break
         e_Pe = e_Pe_new
         eta = eta + alpha * delta
@@ -1058,6 +1060,7 @@ class QuadraticOptimizer:
         isstop = ngf < prm.gradnorm_tol
         while not isstop and it < max_iter:
             tr = [] if prm.verbose else None
+            Delta_in = Delta
             eta, status, inner, n_hess = tcg(p, x1, g1, S, Delta, prm.RTR_tCG_iterations, trace=tr,
                                              hess_recurrence=self.hess_recurrence)
             self.result.tcg_iters += n_hess
@@ -1076,6 +1079,8 @@ class QuadraticOptimizer:
                                    abs(f1 - f2) / (abs(f1) + 1) < sqeps and f2 < f1)
             self.result.trace.append(dict(it=it, f1=f1, f2=f2, rho=rho, Delta=Delta, inner=inner,
                                           status=status, accept=accept, ngf=ngf))
+            if tr is not None:  # verbose: the iterate and radius this iteration started from, and its tCG rows
+                self.result.trace[-1].update(x=x1, Delta_in=Delta_in, tcg=tr)
             if accept:
                 EG = p.euc_grad(x2)
                 S = p.sym_ytg(x2, EG)

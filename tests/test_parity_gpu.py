@@ -360,7 +360,9 @@ def test_final_cost_of_the_multi_agent_configuration_matches_reference(oracle):
 
 def test_feed_modes_and_single_iteration_radius_shrink(oracle):
     """The just-in-time kernel feed (default) and the polling feed run the same device arithmetic;
-    RTR_iterations == 1 takes the radius-shrinking branch of trustRegion (src/QuadraticOptimizer.cpp:80-99)."""
+    RTR_iterations == 1 enters the single-iteration mode of trustRegion (src/QuadraticOptimizer.cpp:80-99) with a radius that
+    is accepted at once; the loop that shrinks the radius over several tries, and its give-up branch, are tested in
+    tests/test_trust_region_branches_gpu.py."""
     import dpgo_amd
     om, n, d, Q, pg, prob = build_single_agent(oracle, "sphere2500", 5)
     X0 = tiles_to_matrix(oracle.lift(oracle.chordal_initialization(om, n), 5))
