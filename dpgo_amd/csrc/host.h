@@ -95,7 +95,7 @@ inline bool supported(int d, int r) {
   } while (0)
 
 // Caller pointers (include/dpgo_hip.h, "Alignment"): any 8-byte-aligned address is valid; the kernels that move own-tile
-// spans in 16-byte pieces (span_to_lds / span_from_lds, dbl2) run on 16-byte-aligned buffers only
+// spans in 16-byte pieces (dbl2, span_from_lds) run on 16-byte-aligned buffers only
 inline bool aligned8(const void* q) { return ((uintptr_t)q & 7) == 0; }
 inline bool aligned16(const void* q) { return ((uintptr_t)q & 15) == 0; }
 
@@ -127,7 +127,6 @@ inline int free_bsr(Bsr& m) {
   X(stream_nt,         "DPGO_STREAM_NT",         -1,  "non-temporal single-use operands in the tCG-step kernels: 0 / 1")             \
   X(outer_sym,         "DPGO_OUTER_SYM",          1,  "outer RTR iteration (k_grad / k_hess) reads the symmetric copy when tCG does") \
   X(tile_walk,         "DPGO_TILE_WALK",          1,  "symmetric-storage kernels walk each XCD's tiles breadth-first over the tile graph (0: index order)") \
-  X(iter_graph,        "DPGO_ITER_GRAPH",         0,  "steady tCG iterations replayed from an instantiated hipGraph (measured slower)") \
   X(tcg_ahead,         "DPGO_TCG_AHEAD",          0,  "iterations the just-in-time feed stays ahead (0: 2 multilevel / 4 otherwise)") \
   X(grid_update,       "DPGO_GRID_UPDATE",        0,  "launch cap of k_tcg_update (0: resident count)")                              \
   X(grid_hess,         "DPGO_GRID_HESS",          0,  "launch cap of k_tcg_hess (0: resident count)")                                \
@@ -145,7 +144,6 @@ inline int free_bsr(Bsr& m) {
   X(poll_sleep,        "DPGO_POLL_SLEEP",        -1,  "s_sleep units between sweeps of the in-kernel all-reduce")                    \
   X(poll_first_pay,    "DPGO_POLL_FIRST_PAY",    -1,  "the same before the first sweep of a reduction that carries a payload")       \
   X(persist_verbose,   "DPGO_PERSIST_VERBOSE",    0,  "per-solve phase report of the one-launch solve on stderr")                    \
-  X(hess_dma,          "DPGO_HESS_DMA",           0,  "k_tcg_hess_sym's own tiles by LDS-DMA: 1 = double-buffered, 2 waves / SIMD, 4 blocks in flight; 2 = 3 waves, 2 blocks") \
   X(setup_timing,      "DPGO_SETUP_TIMING",       0,  "section times of the hierarchy's symbolic set-up on stderr")                  \
   X(setup_threads,     "DPGO_SETUP_THREADS",      0,  "host threads of the hierarchy's symbolic set-up (0: min(8, cores); 1: serial)") \
   X(setup_pin,         "DPGO_SETUP_PIN",          1,  "set-up worker threads placed in the CPU group of the thread that first used them") \
@@ -159,7 +157,6 @@ inline int free_bsr(Bsr& m) {
   X(ml_operator_bits,  "DPGO_ML_OPERATOR_BITS",   0,  "level-0 operator copies of the cycle on HBM-bound blocks: 32 / 64 (0: 32)")   \
   X(ml_vector_bits,    "DPGO_ML_VECTOR_BITS",     0,  "cycle-internal vectors (pre-smoothed iterate, kept residual) beside fp32 operator copies: 32 / 64 (0: 32)") \
   X(ml_dense_bits,     "DPGO_ML_DENSE_BITS",      0,  "dense level beside fp32 cycle vectors: 32 / 64 (0: 64 -- fp32 measured neutral)") \
-  X(ml_setup_serial,   "DPGO_ML_SETUP_SERIAL",    0,  "one-thread-per-aggregate set-up kernels of round 3")                          \
   X(gj_mfma,           "DPGO_GJ_MFMA",            1,  "rank-64 updates of the dense inverse on the fp64 matrix cores")               \
   X(dense_chunk,       "DPGO_DENSE_CHUNK",        0,  "tiles per workgroup of k_dense_sym_apply (0: default)")                       \
   X(coarse_nodes,      "DPGO_COARSE_NODES",       0,  "nodes per workgroup of k_ml_coarse_prolong: 1-4 (0: by size)")                \
@@ -407,18 +404,6 @@ struct dpgo_problem_s {
   unsigned long long* hflag = nullptr;  // pinned, host-coherent: device-published tCG progress word
   unsigned gen = 0;
   bool saw_rtr_stop = false;  // set from the progress word in just-in-time mode
-  // One STEADY tCG iteration (j >= 1: Hessian step, update, and the V-cycle's launches when that is the preconditioner)
-  // of the multi-launch scheme as an instantiated hipGraph, replayed by the just-in-time feed instead of 2-6 stream
-  // launches (tools/launch_lab.hip: the boundary between two dependent kernels is 3.4 us on a stream, 1.6 us inside a
-  // graph).  One per parity of the state slot the iteration starts from; `key` = hash of everything the launches read
-  // from the handle (iter_graph_key, solve.hip): a graph is re-captured when it no longer matches.
-  struct IterGraph {
-    hipGraphExec_t exec = nullptr;
-    unsigned long long key = 0;
-  } iter_graph[2];
-  bool capturing = false;          // launches are being recorded: they pass generation 0 (kernels/common.h, state_gen)
-  bool iter_graph_failed = false;  // capture / instantiation / launch failed once: this handle keeps plain launches
-  unsigned launch_gen() const { return capturing ? 0u : gen; }
   // re-weightable edges (GNC)
   int em = 0;
   int32_t *e_p1 = nullptr, *e_p2 = nullptr, *c_ptr = nullptr, *c_edge = nullptr;

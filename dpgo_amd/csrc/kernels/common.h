@@ -41,10 +41,9 @@ __device__ __forceinline__ void publish_progress(unsigned long long* hflag, unsi
   }
 }
 
-// The generation a tCG run's progress words carry.  Launches that are replayed from an instantiated hipGraph (one steady
-// tCG iteration, solve.hip) cannot take it as a kernel argument -- it changes with every outer iteration -- so the record
-// carries it: a launch with gen != 0 (every direct launch; the first launches of a tCG run always are) writes it into
-// the record, a launch with gen == 0 reads it from there.
+// The generation a tCG run's progress words carry.  The record carries it beside the kernel argument: a launch with
+// gen != 0 (every launch of a solve) writes it into the record, a launch with gen == 0 and no progress word (the kernel
+// probes of bench_probes.hip) reads it from there.
 __device__ __forceinline__ unsigned state_gen(DevState& st, unsigned gen) {
   if (gen) st.pad0 = (int)gen;
   return (unsigned)st.pad0;
@@ -139,15 +138,6 @@ __device__ __forceinline__ TileIter tile_iter(int ntiles) {
 #endif
 #ifndef DPGO_GATHER_BATCH
 #define DPGO_GATHER_BATCH 1  // the same for the other kernels on the symmetric storage (q_gather: restriction, one-launch solve)
-#endif
-#ifndef DPGO_CYCLE_SPAN
-// own-tile rows of the cycle's level-0 kernels (restriction, post-smoothing) as lane-linear span pieces through the wave's LDS
-// tiles, like the tCG kernels (1) or per-lane column loads / stores (0).  Built, parity-green and measured in round 6
-// (profiles/r06_ab_results.txt, three interleaved pairs at 100k poses): restriction 23.9 -> 28.8 us, post-smoothing
-// 22.8 -> 32.9 us, 132.8 -> 155.5 us per product -- the extra LDS round trip and wave barrier per tile sit on the tile's
-// dependent chain behind the gather, and the post-smoothing kernel spills 19 instead of 10 VGPRs at its 4 waves per SIMD.
-// Negative: off.
-#define DPGO_CYCLE_SPAN 0
 #endif
 #ifndef DPGO_SYM_WAVES
 #define DPGO_SYM_WAVES 2  // waves per SIMD k_tcg_hess_sym is compiled for (<= 256 VGPRs; 3 with DPGO_HESS_BATCH=1)
@@ -244,29 +234,9 @@ struct Span {
   static constexpr int NIT = (NPC + 63) / 64; // pieces per lane
 };
 
-// Own-tile span moves between global memory and a wave's LDS tile (layout [pose][column][R] = the memory layout): pieces of
-// two entries, lane-linear (16-byte accesses for fp64, 8-byte for the fp32 storage of the cycle's vectors -- converted on the
-// way, the LDS tile is always fp64).  `valid` = entries of the span that exist (ragged last tile).  Wave-cooperative.
-template <int D, int R, int NTS = 0, class XT>
-__device__ __forceinline__ void span_to_lds(const XT* __restrict__ src, double* __restrict__ lds, int valid) {
-  using SPN = Span<D, R, 1>;
-  const int lane = threadIdx.x & 63;
-#pragma unroll
-  for (int it = 0; it < SPN::NIT; ++it) {
-    const int pc = lane + 64 * it;
-    if (2 * pc < valid) {
-      dbl2 v;
-      if constexpr (sizeof(XT) == 8) {
-        v = ld_stream<NTS>(reinterpret_cast<const dbl2*>(src) + pc);
-      } else {
-        const float2 f = ld_stream<NTS>(reinterpret_cast<const float2*>(src) + pc);
-        v.x = (double)f.x;
-        v.y = (double)f.y;
-      }
-      reinterpret_cast<dbl2*>(lds)[pc] = v;
-    }
-  }
-}
+// Own-tile span move from a wave's LDS tile (layout [pose][column][R] = the memory layout) to global memory: pieces of
+// two entries, lane-linear (16-byte accesses for fp64, 8-byte for an fp32 destination -- converted on the way, the LDS tile
+// is always fp64).  `valid` = entries of the span that exist (ragged last tile).  Wave-cooperative.
 template <int D, int R, int NTS = 0, class XT>
 __device__ __forceinline__ void span_from_lds(XT* __restrict__ dst, const double* __restrict__ lds, int valid) {
   using SPN = Span<D, R, 1>;

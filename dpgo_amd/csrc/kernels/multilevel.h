@@ -116,7 +116,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(Restrict
         stop.state->tcg_status = (kappa < pw) ? TCG_LCON : TCG_SCON;
         stop.state->tcg_done = 1;
         if (stop.hflag) {
-          const unsigned g_ = stop.gen ? stop.gen : (unsigned)st->pad0;  // (0: a replayed launch, see state_gen)
+          const unsigned g_ = stop.gen ? stop.gen : (unsigned)st->pad0;  // (0: the one in the record, see state_gen)
           const unsigned long long w = ((unsigned long long)g_ << 32) |
                                        ((unsigned long long)((unsigned)j & 0xFFFFFFu) << 8) | 1ull;
           __hip_atomic_store(stop.hflag, w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
@@ -142,41 +142,18 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(Restrict
     q_gather<D, R, SPLIT>(A, x1, i, L.s, L.c, okp, h);
     DPGO_TL_USE(h[0]);
     DPGO_STAMP_TILE_IN(g_tl_restrict, 1);
-    if constexpr (SPLIT == 1 && Span<D, R, 1>::kOk && DPGO_CYCLE_SPAN) {
-      // (opt-in, measured slower: see DPGO_CYCLE_SPAN in common.h) the own rows of r and x1 and the kept residual move as
-      // lane-linear pieces of the wave's span: r is staged in the wave's residual tile, x1 in its rows of t_s (free until
-      // the P^T products below); same arithmetic
-      const int p0 = tile * GEO::P + L.wave * GEO::G;
-      const int npose = (n - p0) < GEO::G ? (n - p0) : GEO::G;
-      const int valid = npose > 0 ? npose * GEO::T : 0;
-      const size_t base = (size_t)p0 * GEO::T;
-      double* rw = &res_s[L.wave][0][0];
-      span_to_lds<D, R>(r + base, rw, valid);
-      span_to_lds<D, R>(x1 + base, &t_s[L.wave * GEO::G][0], valid);
-      wave_sync();
-      if (ok) {
-        const double* rr = &res_s[L.wave][L.g][L.c * R];
-        const double* xr = &t_s[lp][L.c * R];
+    if (ok) {
+      XT xr[R];  // (kept in its storage type until used: five registers instead of ten for the fp32 cycle vectors)
+      double rr[R];
 #pragma unroll
-        for (int a = 0; a < R; ++a) h[a] = rr[a] - h[a] - shift * xr[a];
-        store_col<R>(&res_s[L.wave][L.g][L.c * R], h);  // (a lane reads and writes its own column only)
-      }
-      wave_sync();
-      if (res_out) span_from_lds<D, R>(res_out + base, rw, valid);  // kept for k_ml_post_ap, in its storage type
-    } else {
-      if (ok) {
-        XT xr[R];  // (kept in its storage type until used: five registers instead of ten for the fp32 cycle vectors)
-        double rr[R];
+      for (int a = 0; a < R; ++a) xr[a] = x1[off + a];
+      load_col<R>(r + off, rr);
 #pragma unroll
-        for (int a = 0; a < R; ++a) xr[a] = x1[off + a];
-        load_col<R>(r + off, rr);
-#pragma unroll
-        for (int a = 0; a < R; ++a) h[a] = rr[a] - h[a] - shift * (double)xr[a];
-        store_col<R>(&res_s[L.wave][L.g][L.c * R], h);
-        if (res_out) store_col_t<R>(res_out + off, h);  // kept for k_ml_post_ap (in its storage type; P^T res uses h itself)
-      }
-      wave_sync();
+      for (int a = 0; a < R; ++a) h[a] = rr[a] - h[a] - shift * (double)xr[a];
+      store_col<R>(&res_s[L.wave][L.g][L.c * R], h);
+      if (res_out) store_col_t<R>(res_out + off, h);  // kept for k_ml_post_ap (in its storage type; P^T res uses h itself)
     }
+    wave_sync();
     DPGO_STAMP_TILE_IN(g_tl_restrict, 2);
     if (L.s == 0 && L.g < GEO::G) {
       double t[R];
@@ -625,34 +602,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(SPLIT ==
     spmm_col<D, R, SPLIT>(AP.rowptr, AP.colidx, AP.vals, xc, i, L.s, L.c, okp, h);
     DPGO_TL_USE(h[0]);
     DPGO_STAMP_TILE_IN(g_tl_post, 1);
-    constexpr bool kSpan = (SPLIT == 1) && Span<D, R, 1>::kOk && DPGO_CYCLE_SPAN;
-    [[maybe_unused]] int valid = 0;
-    [[maybe_unused]] size_t base = 0;
-    if constexpr (kSpan) {
-      // (opt-in, measured slower: see DPGO_CYCLE_SPAN in common.h) own rows of X, r and the kept residual as lane-linear
-      // pieces of the wave's span, staged in the three tiles; the output leaves the same way (below); same arithmetic
-      const int p0 = tile * GEO::P + L.wave * GEO::G;
-      const int npose = (n - p0) < GEO::G ? (n - p0) : GEO::G;
-      valid = npose > 0 ? npose * GEO::T : 0;
-      base = (size_t)p0 * GEO::T;
-      span_to_lds<D, R>(X + base, &sm[L.wave][0][0][0], valid);
-      span_to_lds<D, R>(r + base, &sm[L.wave][1][0][0], valid);
-      span_to_lds<D, R>(res1 + base, &sm[L.wave][2][0][0], valid);
-      if (ok) {
-#pragma unroll
-        for (int q = 0; q < GEO::B; ++q) dr[q] = dinv[(size_t)i * GEO::BB + L.c * GEO::B + q];
-      }
-      wave_sync();
-      if (ok) {
-#pragma unroll
-        for (int a = 0; a < R; ++a) {
-          rr[a] = vs[L.c * R + a];
-          h[a] = zs[L.c * R + a] - h[a];  // r - A x
-          part[0] = fma(rr[a], rr[a], part[0]);
-        }
-        store_col<R>(zs + L.c * R, h);  // (a lane reads and writes its own column only)
-      }
-    } else if (ok) {
+    if (ok) {
       double x[R], rs[R];
       load_col<R>(X + off, x);
       load_col<R>(r + off, rr);
@@ -705,16 +655,9 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(SPLIT ==
 #pragma unroll
         for (int a = 0; a < R; ++a) part[1] = fma(out[a], rr[a], part[1]);
       }
-      if constexpr (kSpan)
-        store_col<R>(vs + L.c * R, out);  // (the r tile is free: its last readers were the smoothing steps above)
-      else
-        store_col<R>(Z + off, out);
+      store_col<R>(Z + off, out);
     }
     wave_sync();
-    if constexpr (kSpan) {
-      span_from_lds<D, R>(Z + base, &sm[L.wave][1][0][0], valid);
-      wave_sync();
-    }
     DPGO_STAMP_TILE_IN(g_tl_post, 5);
     DPGO_TILE_NEXT;
   }
@@ -803,87 +746,15 @@ __global__ __launch_bounds__(kBlock) void k_ml_build_P(BsrDev Q, int n_fine, int
 
 // Prolongation blocks for GRAPH aggregates.  Every aggregate carries a spanning tree (the breadth-first tree the host's
 // aggregation grew it along): parent[i] = the node that discovered i (-1: the aggregate's root), pslot[i] = the slot of
-// block (parent, i) in Q.  One thread per aggregate walks its members in discovery order (a parent precedes its children)
-// and composes G(root -> i) = G(root -> parent) T(parent -> i);  Pb[i] = G^T.  T is read off the block as in k_ml_build_P;
-// the block of an edge measured the other way round (i -> parent) is the transpose -(T' Om)^T: T = T'^-1.  A block that
-// is neither (zero weight, several measurements summed) restarts the chain at the identity.
-template <int D>
-__global__ __launch_bounds__(kBlock) void k_ml_build_P_tree(BsrDev Q, const int32_t* __restrict__ agg_ptr,
-                                                            const int32_t* __restrict__ agg_mem,
-                                                            const int32_t* __restrict__ parent,
-                                                            const int32_t* __restrict__ pslot, double* Pb, int na) {
-  constexpr int B = D + 1, BB = B * B;
-  for (int a = blockIdx.x * kBlock + threadIdx.x; a < na; a += gridDim.x * kBlock) {
-    for (int m = agg_ptr[a]; m < agg_ptr[a + 1]; ++m) {
-      const int i = agg_mem[m];
-      const int par = parent[i];
-      double G[B][B];
-#pragma unroll
-      for (int p = 0; p < B; ++p)
-#pragma unroll
-        for (int q = 0; q < B; ++q) G[p][q] = (p == q) ? 1.0 : 0.0;
-      if (par >= 0) {
-        const double* blk = Q.vals + (size_t)pslot[i] * BB;
-        const double wt = -blk[D * B + D];
-        double wk = 0.0;
-#pragma unroll
-        for (int p = 0; p < D; ++p) wk = fma(blk[p * B], blk[p * B], wk);
-        wk = sqrt(wk);
-        bool fwd = true, bwd = true;
-#pragma unroll
-        for (int q = 0; q < D; ++q) {
-          fwd = fwd && (blk[D * B + q] == 0.0);
-          bwd = bwd && (blk[q * B + D] == 0.0);
-        }
-        if ((wt > 0.0) && (wk > 0.0) && (fwd || bwd)) {
-          double Tm[B][B];
-#pragma unroll
-          for (int p = 0; p < B; ++p)
-#pragma unroll
-            for (int q = 0; q < B; ++q) Tm[p][q] = (p == q) ? 1.0 : 0.0;
-#pragma unroll
-          for (int p = 0; p < D; ++p)
-#pragma unroll
-            for (int q = 0; q < D; ++q) Tm[p][q] = -blk[p * B + q] / wk;
-          if (fwd) {
-#pragma unroll
-            for (int p = 0; p < D; ++p) Tm[p][D] = -blk[p * B + D] / wt;
-          } else {  // T'^-1 = [R'^T, -R'^T t'; 0 1],  R'^T = Tm's rotation part,  t' = -blk[D][:] / wt
-#pragma unroll
-            for (int p = 0; p < D; ++p) {
-              double sv = 0.0;
-#pragma unroll
-              for (int q = 0; q < D; ++q) sv = fma(Tm[p][q], blk[D * B + q] / wt, sv);
-              Tm[p][D] = sv;
-            }
-          }
-          const double* __restrict__ Pp = Pb + (size_t)par * BB;  // G(root -> parent)^T, written earlier by this thread
-#pragma unroll
-          for (int p = 0; p < B; ++p)
-#pragma unroll
-            for (int q = 0; q < B; ++q) {
-              double sv = 0.0;
-#pragma unroll
-              for (int mm = 0; mm < B; ++mm) sv = fma(Pp[mm * B + p], Tm[mm][q], sv);
-              G[p][q] = sv;
-            }
-        }
-      }
-      double* out = Pb + (size_t)i * BB;
-#pragma unroll
-      for (int p = 0; p < B; ++p)
-#pragma unroll
-        for (int q = 0; q < B; ++q) out[p * B + q] = G[q][p];
-    }
-  }
-}
-
-// The same, one WAVE per aggregate (graph aggregates of dozens to hundreds of poses: one thread walking 250 members one
-// dependent load after the other took 1.24 ms at 100k poses, 0.37 ms on a 12 500-pose block of 230 aggregates).  The members
-// are in breadth-first discovery order, so a parent precedes its children; the wave takes them in chunks of 64 and, inside a
+// block (parent, i) in Q.  G(root -> i) = G(root -> parent) T(parent -> i);  Pb[i] = G^T.  T is read off the block as in
+// k_ml_build_P; the block of an edge measured the other way round (i -> parent) is the transpose -(T' Om)^T: T = T'^-1
+// = [R'^T, -R'^T t'; 0 1].  A block that is neither (zero weight, several measurements summed) restarts the chain at the
+// identity.
+// One WAVE per aggregate (graph aggregates of dozens to hundreds of poses: one thread walking 250 members one dependent
+// load after the other took 1.24 ms at 100k poses, 0.37 ms on a 12 500-pose block of 230 aggregates).  The members are in
+// breadth-first discovery order, so a parent precedes its children; the wave takes them in chunks of 64 and, inside a
 // chunk, in passes: a lane computes once its parent's block is there (parent in an earlier chunk, or done in an earlier
-// pass -- ballot mask).  Every block is computed by the same arithmetic as in the one-thread kernel: identical bits.
-// mem_pos[i] = position of pose i in agg_mem.
+// pass -- ballot mask).  mem_pos[i] = position of pose i in agg_mem.
 template <int D>
 __device__ __forceinline__ void ml_tree_block(const BsrDev& Q, const double* Pb, int i, int par, int slot, double* out) {
   constexpr int B = D + 1, BB = B * B;

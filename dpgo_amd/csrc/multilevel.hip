@@ -723,16 +723,11 @@ int ml_numeric_setup_d(dpgo_problem_s* p) {
     auto& L = p->ml[l];
     auto& C = p->ml[l + 1];
     const long long span = stride * L.k;
-    // (wave-parallel forms of the two setup kernels that walked an aggregate's members with ONE thread; DPGO_ML_SETUP_SERIAL=1
-    // restores them)
-    const bool serial = options().ml_setup_serial != 0;
+    // (the wave-parallel set-up kernels: one wave per aggregate / per coarse slot)
     auto wave_grid = [](int items) { return std::max(1, std::min(kMaxGrid, (items + kWaves - 1) / kWaves)); };
-    if (L.graph && !serial)
+    if (L.graph)
       hipLaunchKernelGGL(k_ml_build_P_tree_wave<D>, dim3(wave_grid(C.n)), dim3(kBlock), 0, p->stream, p->Q.dev(), L.agg_ptr,
                          L.agg_mem, L.parent, L.pslot, L.mem_pos, L.Pb, C.n);
-    else if (L.graph)
-      hipLaunchKernelGGL(k_ml_build_P_tree<D>, dim3(flat_grid(C.n)), dim3(kBlock), 0, p->stream, p->Q.dev(), L.agg_ptr,
-                         L.agg_mem, L.parent, L.pslot, L.Pb, C.n);
     else
       hipLaunchKernelGGL(k_ml_build_P<D>, dim3(flat_grid(C.n)), dim3(kBlock), 0, p->stream, p->Q.dev(), p->n, (int)stride,
                          (int)span, L.Pb, C.n);
@@ -741,7 +736,7 @@ int ml_numeric_setup_d(dpgo_problem_s* p) {
     if (have_ap)  // A P first: the Galerkin operator of a two-level hierarchy is its restriction
       hipLaunchKernelGGL(k_ml_build_AP<D>, dim3(flat_grid(L.n)), dim3(kBlock), 0, p->stream, p->Q.dev(), p->ml_shift, L.Pb,
                          L.agg(), L.n, L.AP.dev(), L.AP.vals);
-    if (have_ap && !serial)
+    if (have_ap)
       hipLaunchKernelGGL(k_ml_galerkin_ap<D>, dim3(wave_grid(C.A.nnzb)), dim3(kBlock), 0, p->stream, L.AP.dev(), L.Pb,
                          L.agg(), L.agg_ptr, L.agg_mem, L.n, C.slot_row, C.A.colidx, C.A.vals, C.A.nnzb);
     else
@@ -1040,7 +1035,7 @@ int launch_ml_restrict0(dpgo_problem_s* p, const double* r, const DevState* gate
     stop.pin = p->pB();
     stop.nb = p->grid_u(true);  // (k_tcg_update_span's multilevel-mode instance wrote them)
     stop.hflag = p->hflag;
-    stop.gen = p->launch_gen();
+    stop.gen = p->gen;
   }
   float* rc32 = (C.k == 0 && p->coarse32_active()) ? reinterpret_cast<float*>(C.r) : (float*)nullptr;
   double* res_out = p->ml_use_ap() ? L.res1 : nullptr;

@@ -476,7 +476,6 @@ int dpgo_problem_describe(dpgo_problem_t p, char* out, int capacity) {
   s += std::string(p->ml_ready ? " built" : " not built") + ", dense level fp" + std::to_string(p->coarse32_active() ? 32 : 64) +
        (p->ml_additive_layout ? ", additive layout" : "") + ", level-0 operator copies of the cycle fp" +
        std::to_string(p->ml_operator_bits) + (p->ml_ops32_active() ? " (in use)" : "") + "\n";
-  s += std::string("  iteration graphs: ") + (p->iter_graph_failed ? "unavailable" : (p->iter_graph[0].exec || p->iter_graph[1].exec ? "captured" : "none yet")) + "\n";
   s += "options:\n" + options_describe();
   return copy_text(s, out, capacity);
 }
@@ -500,8 +499,6 @@ int dpgo_problem_destroy(dpgo_problem_t p) {
   if (p->pctrl) (void)hipFree(p->pctrl);
   if (p->pgran) (void)hipFree(p->pgran);
   if (p->hctrl) (void)hipHostFree(p->hctrl);
-  for (auto& g : p->iter_graph)
-    if (g.exec) (void)hipGraphExecDestroy(g.exec);
   if (p->own_stream) (void)hipStreamDestroy(p->own_stream);
   delete p;
   return DPGO_OK;

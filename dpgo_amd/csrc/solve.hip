@@ -15,18 +15,18 @@ int launch_tcg_update(dpgo_problem_s* p, const double* dinv, int first, double* 
       if (ml_mode)  // (the instance compiled for the multilevel mode: 3 waves per SIMD)
         hipLaunchKernelGGL((k_tcg_update_span<D, R, 1>), dim3(g), dim3(kBlock), 0, p->stream, p->x1, p->g1, dinv, p->delta,
                            p->Hd, p->eta, p->rr, zt, p->pA(), p->grid_s(), p->pB(), p->dstate + p->cur,
-                           p->dstate + (p->cur ^ 1), first, p->n, p->hflag, p->launch_gen(), ml_omega, z32);
+                           p->dstate + (p->cur ^ 1), first, p->n, p->hflag, p->gen, ml_omega, z32);
       else
         hipLaunchKernelGGL((k_tcg_update_span<D, R, 0>), dim3(g), dim3(kBlock), 0, p->stream, p->x1, p->g1, dinv, p->delta,
                            p->Hd, p->eta, p->rr, zt, p->pA(), p->grid_s(), p->pB(), p->dstate + p->cur,
-                           p->dstate + (p->cur ^ 1), first, p->n, p->hflag, p->launch_gen(), ml_omega, z32);
+                           p->dstate + (p->cur ^ 1), first, p->n, p->hflag, p->gen, ml_omega, z32);
     } else {
       // (odd tile size: the generic kernel has no fp32 output -- resolve_tcg_storage keeps such blocks off the symmetric
       // storage, hence off the cycle's fp32 vectors; a state that says otherwise is refused instead of dropping z32)
       if (z32) return fail(DPGO_ERR_STATE, "fp32 cycle vectors need the span kernels (even pose tile size)");
       hipLaunchKernelGGL((k_tcg_update<D, R>), dim3(g), dim3(kBlock), 0, p->stream, p->x1, p->g1, dinv, p->delta,
                          p->Hd, p->eta, p->rr, zt, p->pA(), p->grid_s(), p->pB(), p->dstate + p->cur,
-                         p->dstate + (p->cur ^ 1), first, p->n, p->hflag, p->launch_gen(), ml_omega);
+                         p->dstate + (p->cur ^ 1), first, p->n, p->hflag, p->gen, ml_omega);
     }
   });
   HIPC(hipGetLastError());
@@ -39,15 +39,7 @@ int launch_tcg_update(dpgo_problem_s* p, const double* dinv, int first, double* 
 #define LAUNCH_TCG_HESS(p, SIN, SOUT, FIRST, HFLAG, GEN)                                                          \
   do {                                                                                                            \
     if constexpr (Span<D, R, 1>::kOk) {                                                                           \
-      if ((p)->tcg_sym && options().hess_dma == 1)                                                                \
-        hipLaunchKernelGGL((k_tcg_hess_sym_dma<D, R, 1, 2, 4, 1>), dim3((p)->grid_s()), dim3(kBlock), 0,          \
-                           (p)->stream, (p)->sym.dev(), (p)->x1, (p)->S1, (p)->z, (p)->delta, (p)->Hd, (p)->pB(), \
-                           (p)->nb_zr(), (p)->pA(), SIN, SOUT, FIRST, (p)->n, HFLAG, GEN);                         \
-      else if ((p)->tcg_sym && options().hess_dma == 2)                                                           \
-        hipLaunchKernelGGL((k_tcg_hess_sym_dma<D, R, 1, 3, 2, 0>), dim3((p)->grid_s()), dim3(kBlock), 0,          \
-                           (p)->stream, (p)->sym.dev(), (p)->x1, (p)->S1, (p)->z, (p)->delta, (p)->Hd, (p)->pB(), \
-                           (p)->nb_zr(), (p)->pA(), SIN, SOUT, FIRST, (p)->n, HFLAG, GEN);                         \
-      else if ((p)->tcg_sym && (p)->stream_nt)                                                                    \
+      if ((p)->tcg_sym && (p)->stream_nt)                                                                         \
         hipLaunchKernelGGL((k_tcg_hess_sym<D, R, 1>), dim3((p)->grid_s()), dim3(kBlock), 0, (p)->stream,          \
                            (p)->sym.dev(), (p)->x1, (p)->S1, (p)->z, (p)->delta, (p)->Hd, (p)->pB(), (p)->nb_zr(), \
                            (p)->pA(), SIN, SOUT, FIRST, (p)->n, HFLAG, GEN);                                      \
@@ -74,7 +66,7 @@ int launch_tcg_hess_with(dpgo_problem_s* p, const DevState* sin, DevState* sout,
   return DPGO_OK;
 }
 int launch_tcg_hess(dpgo_problem_s* p, int first) {
-  CHK(launch_tcg_hess_with(p, p->dstate + p->cur, p->dstate + (p->cur ^ 1), first, p->hflag, p->launch_gen()));
+  CHK(launch_tcg_hess_with(p, p->dstate + p->cur, p->dstate + (p->cur ^ 1), first, p->hflag, p->gen));
   p->cur ^= 1;
   return DPGO_OK;
 }
@@ -334,57 +326,6 @@ void persist_report(dpgo_problem_s* p) {  // (hctrl has been read back with the 
                0.01 * (double)p->hctrl->ticks[5], 0.01 * (double)p->hctrl->ticks[6], 0.01 * (double)p->hctrl->ticks[7]);
 }
 
-// ---- one steady tCG iteration as an instantiated hipGraph (dpgo_problem_s::IterGraph) ----
-// Everything the launches of an iteration read from the handle, hashed: a captured graph is valid exactly while this
-// value is unchanged (a buffer that was freed and came back at the same address with the same sizes is the same launch).
-struct KeyHash {
-  unsigned long long h = 1469598103934665603ull;
-  void add(const void* ptr) { mix((unsigned long long)(uintptr_t)ptr); }
-  void add(long long v) { mix((unsigned long long)v); }
-  void add(double v) {
-    unsigned long long u;
-    std::memcpy(&u, &v, sizeof(u));
-    mix(u);
-  }
-  void mix(unsigned long long v) {
-    for (int k = 0; k < 8; ++k) {
-      h ^= (v >> (8 * k)) & 0xffull;
-      h *= 1099511628211ull;
-    }
-  }
-};
-void key_bsr(KeyHash& k, const Bsr& m) {
-  k.add((long long)m.nrows), k.add((long long)m.ncols), k.add((long long)m.nnzb);
-  k.add(m.rowptr), k.add(m.colidx), k.add(m.vals);
-}
-unsigned long long iter_graph_key(const dpgo_problem_s* p, const double* dinv, bool ml, bool early_stop) {
-  KeyHash k;
-  k.add((long long)p->d), k.add((long long)p->r), k.add((long long)p->n), k.add((long long)p->split), k.add((long long)p->cur);
-  k.add((long long)p->tcg_sym), k.add((long long)p->stream_nt), k.add((long long)ml), k.add((long long)early_stop);
-  k.add((long long)p->grid()), k.add((long long)p->grid_u(true)), k.add((long long)p->grid_s()), k.add((long long)p->grid_restrict()), k.add((long long)p->grid_post());
-  k.add((long long)p->zr_from_post), k.add((long long)p->nb_zr()), k.add((long long)p->device);
-  key_bsr(k, p->Q);
-  const auto& y = p->sym;
-  k.add(y.urow), k.add(y.ucol), k.add(y.uvalsT), k.add(y.lrow), k.add(y.lcol), k.add(y.lslot), k.add(y.tord);
-  const void* vecs[] = {p->x1, p->g1, p->S1, p->z, p->delta, p->Hd, p->eta, p->rr, dinv, p->dinv, p->partials, p->dstate, p->hflag};
-  for (auto v : vecs) k.add(v);
-  if (!ml) return k.h;
-  k.add(p->ml_omega), k.add(p->ml_shift), k.add((long long)p->ml_coarse_bits), k.add((long long)p->ml_lda);
-  k.add((long long)p->ml_use_ap()), k.add((long long)p->ml_use_dense_sym()), k.add((long long)p->beyond_cache());
-  k.add(p->ml_dense), k.add(p->ml_dense32), k.add(p->ml_packed), k.add(p->ml_pd), k.add(p->ml_pt), k.add(p->ml_chunks);
-  k.add(p->ml_chunk_first), k.add((long long)p->ml_nchunks), k.add((long long)p->ml.size());
-  k.add((long long)p->ml_ops32_active()), k.add((long long)p->ml_vec32_active()), k.add((long long)p->coarse32_active());
-  k.add(p->sym.uvalsT32);
-  for (const auto& L : p->ml) {
-    k.add((long long)L.n), k.add((long long)L.k), k.add((long long)L.split), k.add((long long)L.graph), k.add((long long)L.nseg);
-    key_bsr(k, L.A), key_bsr(k, L.AP);
-    const void* ptrs[] = {L.slot_row, L.dinv, L.Pb, L.r, L.x1, L.x, L.res1, L.lab, L.agg_ptr, L.agg_mem, L.parent, L.pslot,
-                          L.mem_pos, L.seg_info, L.seg_ptr, L.tile_perm, L.tbuf, L.Pb32, L.AP32, L.x1f, L.res1f};
-    for (auto v : ptrs) k.add(v);
-  }
-  return k.h;
-}
-
 // One ROPTLIB SolversTR::Run outer iteration: tCG + retraction + rho test.  State stays on the device; the host
 // feeds tCG-step kernels just-in-time (or polls the state every `tcg_poll_interval` inner iterations).
 int rtr_outer_iteration(dpgo_problem_s* p, const dpgo_ropt_params* prm, const double* dinv, Counters& cnt,
@@ -408,62 +349,7 @@ int rtr_outer_iteration(dpgo_problem_s* p, const dpgo_ropt_params* prm, const do
   };
   CHK(update(1));
   const int max_inner = prm->RTR_tCG_iterations;
-  // Steady iterations (j >= 1) of the just-in-time feed are replayed from an instantiated hipGraph: the launches of one
-  // iteration recorded once (stream capture on the handle's private stream -- the caller's may be the legacy default
-  // stream, which cannot be captured --, generation 0 = "the one in the state record") and launched into the handle's
-  // stream.  Same kernels, same arguments, same order: bit-identical iterates.  OPT-IN (DPGO_ITER_GRAPH=1): measured on the
-  // 100k-pose grid (round 5, two interleaved repetitions) a replayed iteration is SLOWER than its six stream launches --
-  // 158.2 / 157.1 against 150.6 / 152.0 us per product -- although the boundary between two kernels INSIDE one graph is half
-  // a stream boundary (tools/launch_lab.hip: 1.6 against 3.4 us): every hipGraphLaunch of this six-node graph costs more
-  // than the five boundaries it shortens.
-  const bool graph_wanted = options().iter_graph != 0, early_stop_ = options().ml_early_stop != 0;
-  const bool use_graph = graph_wanted && !p->iter_graph_failed && prm->tcg_poll_interval <= 0 && max_inner > 1 && p->own_stream;
-  auto replay = [&]() -> int {  // one steady iteration; DPGO_OK with *launched = false: the caller launches directly
-    auto& g = p->iter_graph[p->cur & 1];
-    const unsigned long long key = iter_graph_key(p, dinv, ml, early_stop_);
-    if (!g.exec || g.key != key) {
-      if (g.exec) (void)hipGraphExecDestroy(g.exec);
-      g.exec = nullptr;
-      hipStream_t own = p->own_stream, keep = p->stream;
-      const int cur0 = p->cur;
-      if (keep == own) HIPC(hipStreamSynchronize(own));  // (recording starts on an idle stream)
-      if (hipStreamBeginCapture(own, hipStreamCaptureModeThreadLocal) != hipSuccess) {
-        (void)hipGetLastError();
-        p->iter_graph_failed = true;
-        return DPGO_ERR_UNSUPPORTED;
-      }
-      p->stream = own;
-      p->capturing = true;
-      int rc = launch_tcg_hess(p, 0);
-      if (rc == DPGO_OK) rc = update(0);
-      p->capturing = false;
-      p->stream = keep;
-      p->cur = cur0;
-      hipGraph_t graph = nullptr;
-      const hipError_t e1 = hipStreamEndCapture(own, &graph);
-      hipError_t e2 = hipSuccess;
-      if (rc == DPGO_OK && e1 == hipSuccess && graph) e2 = hipGraphInstantiate(&g.exec, graph, nullptr, nullptr, 0);
-      if (graph) (void)hipGraphDestroy(graph);
-      if (rc != DPGO_OK || e1 != hipSuccess || e2 != hipSuccess || !g.exec) {
-        (void)hipGetLastError();
-        g.exec = nullptr;
-        p->iter_graph_failed = true;
-        return DPGO_ERR_UNSUPPORTED;
-      }
-      g.key = key;
-    }
-    if (hipGraphLaunch(g.exec, p->stream) != hipSuccess) {
-      (void)hipGetLastError();
-      p->iter_graph_failed = true;
-      return DPGO_ERR_UNSUPPORTED;
-    }
-    return DPGO_OK;
-  };
   auto step = [&](int j) -> int {
-    if (j >= 1 && use_graph && !p->iter_graph_failed) {
-      if (replay() == DPGO_OK) return DPGO_OK;  // (otherwise: nothing of this iteration has been enqueued)
-      if (options().persist_verbose) std::fprintf(stderr, "dpgo_hip: hipGraph replay of a tCG iteration unavailable; plain launches\n");
-    }
     CHK(launch_tcg_hess(p, j == 0 ? 1 : 0));
     return update(0);
   };
@@ -874,12 +760,7 @@ int tune_launch_caps(dpgo_problem_s* p) {
         CHK(resident_blocks(k_tcg_hess_span<D, R, 2>, &p->cap_h));
       else
         CHK(resident_blocks(k_tcg_hess_span<D, R, 1>, &p->cap_h));
-      if (options().hess_dma == 1)
-        CHK(resident_blocks((k_tcg_hess_sym_dma<D, R, 1, 2, 4, 1>), &p->cap_hs));
-      else if (options().hess_dma == 2)
-        CHK(resident_blocks((k_tcg_hess_sym_dma<D, R, 1, 3, 2, 0>), &p->cap_hs));
-      else
-        CHK(resident_blocks(k_tcg_hess_sym<D, R, 1>, &p->cap_hs));
+      CHK(resident_blocks(k_tcg_hess_sym<D, R, 1>, &p->cap_hs));
     } else {
       CHK(resident_blocks(k_tcg_update<D, R>, &p->cap_u));
       p->cap_u_ml = p->cap_u;  // (one kernel for both modes)

@@ -592,7 +592,7 @@ def amg_merge_small_aggregates(Q: "BSR", S: int, lab, ptr, mem, cap: Optional[in
 
 
 def amg_tree_prolongation(Q: "BSR", d: int, mem, parent, pslot):
-    """Mirrors k_ml_build_P_tree: Pb[i] = G(root of i's aggregate -> i)^T, composed along the aggregate's breadth-first
+    """Mirrors k_ml_build_P_tree_wave: Pb[i] = G(root of i's aggregate -> i)^T, composed along the aggregate's breadth-first
     tree.  The relative pose of a tree edge parent -> i is read off the block Q[parent, i]: a measurement parent -> i
     leaves -T Om = -[w kappa R, w tau t; 0, w tau] there (last row zero but for -w tau), a measurement i -> parent its
     transpose -(T' Om)^T (last column zero but for -w tau; T = T'^-1).  Anything else (zero weight, several measurements

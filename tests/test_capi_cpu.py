@@ -387,7 +387,7 @@ def test_multilevel_hierarchy_rules(name, ks):
         assert np.all(lab_o[par_o[par_o >= 0]] == lab_o[par_o >= 0])
     if len(ks) == 1 and ks[0] < 0:
         # graph aggregates (the default two-level hierarchy): the prolongation composed along each aggregate's
-        # breadth-first tree (k_ml_build_P_tree) reproduces the rigid-body modes -- on the odometry chain, and on a spanning
+        # breadth-first tree (k_ml_build_P_tree_wave) reproduces the rigid-body modes -- on the odometry chain, and on a spanning
         # tree of the whole graph whose edges are measured in either direction
         lab, ptr, mem, parent, pslot = O.amg_graph_aggregates(Qo, -ks[0])
         assert sorted(mem.tolist()) == list(range(n)) and np.all(np.diff(ptr) <= -ks[0]) and np.all(np.diff(ptr) >= 1)
@@ -623,9 +623,11 @@ def test_switches_are_one_table_read_once_and_the_auto_rule_is_restated(oracle):
     lib = L.load()
     text = L.describe_options()
     rows = dict(ln.split("  # ")[0].split("=", 1) for ln in text.strip().splitlines())
-    for name in ("DPGO_SPLIT", "DPGO_SPMM_SYMMETRIC", "DPGO_ITER_GRAPH", "DPGO_ML_OPERATOR_BITS", "DPGO_TILE_WALK",
+    for name in ("DPGO_SPLIT", "DPGO_SPMM_SYMMETRIC", "DPGO_ML_OPERATOR_BITS", "DPGO_TILE_WALK",
                  "DPGO_AUTO_COST_RULE", "DPGO_ML_EARLY_STOP", "DPGO_OUTER_SYM", "DPGO_ML_GRAPH", "DPGO_PERSIST"):
         assert name in rows, name
+    for name in ("DPGO_ITER_GRAPH", "DPGO_HESS_DMA", "DPGO_ML_SETUP_SERIAL"):  # removed with the paths they selected
+        assert name not in text, name
     assert len(rows) >= 30 and all("[set]" not in v for k, v in rows.items() if k not in os.environ)
     old = os.environ.get("DPGO_TCG_AHEAD")
     try:

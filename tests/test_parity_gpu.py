@@ -2520,14 +2520,11 @@ def test_multilevel_on_random_graphs_with_broken_chains(oracle, d, r, n, hub_edg
 SWITCH_SETS = [
     ({}, "baseline"),
     ({"DPGO_ML_EARLY_STOP": "0"}, "bitwise"),      # tCG's residual test back in the Hessian-step kernel's prologue
-    ({"DPGO_ITER_GRAPH": "1"}, "bitwise"),         # steady tCG iterations replayed from an instantiated hipGraph
     ({"DPGO_SPMM_SYMMETRIC": "1", "DPGO_ML_OPERATOR_BITS": "64"}, "oracle"),  # the cycle streams the fp64 operators (sym. storage)
     ({"DPGO_SPMM_SYMMETRIC": "1", "DPGO_ML_VECTOR_BITS": "64"}, "oracle"),    # fp32 operator copies, fp64 vectors inside the cycle
     ({"DPGO_SPMM_SYMMETRIC": "1", "DPGO_ML_DENSE_BITS": "32"}, "oracle"),     # ... and the dense level in fp32 as well
     ({"DPGO_SPMM_SYMMETRIC": "1"}, "oracle"),      # symmetric storage of Q: k_tcg_hess_sym, level-0 restriction / post-smoothing
     ({"DPGO_SPMM_SYMMETRIC": "1", "DPGO_OUTER_SYM": "0", "DPGO_STREAM_NT": "1"}, "oracle"),  # outer iteration on the plain copy
-    ({"DPGO_SPMM_SYMMETRIC": "1", "DPGO_STREAM_NT": "1", "DPGO_HESS_DMA": "1"}, "oracle"),  # k_tcg_hess_sym_dma: own tiles by LDS-DMA, double-buffered
-    ({"DPGO_SPMM_SYMMETRIC": "1", "DPGO_STREAM_NT": "1", "DPGO_HESS_DMA": "2"}, "oracle"),  # ... single-buffered, 3 waves per SIMD, 2 blocks in flight
     ({"DPGO_SPMM_SYMMETRIC": "1", "DPGO_TILE_WALK": "0"}, "oracle"),  # symmetric-storage kernels walk their tiles in index order
     ({"DPGO_SPMM_SYMMETRIC": "0", "DPGO_STREAM_NT": "1"}, "oracle"),  # plain storage with non-temporal single-use operands
     ({"DPGO_SETUP_THREADS": "1"}, "bitwise"),      # the hierarchy's symbolic set-up on the calling thread alone
@@ -2535,7 +2532,7 @@ SWITCH_SETS = [
     ({"DPGO_ML_GROWTH_CHUNKS": "4"}, "oracle"),    # aggregates grown and merged inside 4 index ranges (the oracle reads the same variable)
     ({"DPGO_ML_GRAPH": "0"}, "oracle"),            # index-run hierarchy (k_ml_post_ap on runs, in-workgroup restriction sums)
     ({"DPGO_ML_GRAPH": "0", "DPGO_ML_AP": "0"}, "oracle"),  # ... post-smoothing gathers through Q (k_ml_post)
-    ({"DPGO_ML_SETUP_SERIAL": "1", "DPGO_GJ_MFMA": "0"}, "oracle"),  # round-3 set-up kernels, FMA rank-64 updates
+    ({"DPGO_GJ_MFMA": "0"}, "oracle"),             # FMA rank-64 updates of the dense inverse
     ({"DPGO_ML_DENSE_SYM": "1"}, "oracle"),        # dense level from the packed lower triangle on the matrix cores
     ({"DPGO_COARSE_NODES": "1", "DPGO_COARSE_NT": "1"}, "oracle"),  # one node per workgroup, non-temporal inverse
     ({"DPGO_SPLIT": "1"}, "oracle"),               # lane groups per pose of the SpMM-family kernels, whatever the size
@@ -2559,8 +2556,8 @@ def test_kernel_selecting_switches_match_oracle(oracle, workload):
     smallGrid3D and on a 40 000-pose grid (the smallest block that can run the symmetric storage): two
     QuadraticOptimizer::optimize calls with the multilevel preconditioner against the oracle told the device's
     hierarchy, each call from the oracle's iterate -- same tCG / RTR counts, cost 1e-9 (+ 1e-4 of the call's decrease),
-    iterate 1e-6.  Switches that must not change a single bit (where the residual test sits, how the launches are
-    enqueued) are also compared bitwise with the default run.  The library reads its switches once; the test reloads
+    iterate 1e-6.  Switches that must not change a single bit (where the residual test sits, how many host
+    threads build the hierarchy) are also compared bitwise with the default run.  The library reads its switches once; the test reloads
     them (dpgo_options_reload) and builds a fresh handle per set.  DPGO_ASYNC_SWEEP lives in the Python agent layer:
     test_stream_ordered_sweep_matches_phase_by_phase.  The launch geometry -- lane groups per pose (DPGO_SPLIT) and the
     launch caps (DPGO_GRID_*, DPGO_COARSE_GRID, DPGO_DENSE_CHUNK) -- is flipped here too; kernel by kernel it is tested in
