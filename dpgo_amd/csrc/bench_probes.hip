@@ -464,12 +464,12 @@ extern "C" int dpgo_debug_reduction_primitives(int workgroups, int pay, int step
     hipLaunchKernelGGL((k_probe_allreduce<P>), dim3(workgroups), dim3(kBlock), 0, nullptr, gran, salt, steps, in_dev,   \
                        pay_in_dev, sums_dev, pay_out_dev, rows_out_dev, error, poll);                                    \
     break;
-    CASE_(6) CASE_(9) CASE_(15) CASE_(20) CASE_(24)
+    CASE_(6) CASE_(9) CASE_(12) CASE_(15) CASE_(16) CASE_(20) CASE_(24)
 #undef CASE_
     default:
       (void)hipFree(gran);
       (void)hipFree(error);
-      return fail(DPGO_ERR_UNSUPPORTED, "payload size: one of 6, 9, 15, 20, 24");
+      return fail(DPGO_ERR_UNSUPPORTED, "payload size: one of 6, 9, 12, 15, 16, 20, 24");
   }
   HIPC(hipGetLastError());
   HIPC(hipDeviceSynchronize());

@@ -461,7 +461,7 @@ int dpgo_bench_iteration_kernels(dpgo_problem_t h, int reps, int warmup, double 
 /* Test probe (no reference counterpart): the communication primitives of the one-launch solve alone.  `workgroups`
  * (<= the device's CUs, <= 256) run `steps` chip-wide reductions of two partial sums per thread -- in_dev
  * [workgroups][256][2]: step s reduces in[..][0] * (s + 1) and in[..][1] - s -- each carrying a payload of `pay`
- * (6, 9, 15, 20 or 24) doubles per workgroup, the per-wave parts pay_in_dev [workgroups][4][pay] (+ s) added in wave
+ * (6, 9, 12, 15, 16, 20 or 24: every (d+1) r) doubles per workgroup, the per-wave parts pay_in_dev [workgroups][4][pay] (+ s) added in wave
  * order.  sums_dev [workgroups][steps][2]: what every workgroup's thread 0 holds afterwards (identical bits in all of
  * them); pay_out_dev [workgroups][steps][workgroups][pay]: participant t's payload as thread t of every workgroup
  * received it; rows_out_dev [workgroups][4][pay]: the wavefront sums of value e = in[t][0] (e + 1) + in[t][1] over the 64

@@ -990,7 +990,8 @@ def tcg(problem: QuadraticProblem, X, g, S, Delta, max_inner, theta=1.0, kappa=0
             status = TCG_NEGCURV if d_Hd < 0 else TCG_EXCREGION
             if trace is not None:
                 # (norm_d, norm_Hd: the scale against which a negative d_Hd is "beyond round-off")
-                trace.append(dict(j=j, d_Hd=d_Hd, alpha=alpha, tau=tau, status=status,
+                # (e_Pe: the squared preconditioner-norm length the full step would have had, against Delta^2)
+                trace.append(dict(j=j, d_Hd=d_Hd, alpha=alpha, tau=tau, status=status, e_Pe=e_Pe_new,
                                   norm_d=math.sqrt(dot(delta, delta)), norm_Hd=math.sqrt(dot(Hd, Hd))))
             break
         e_Pe = e_Pe_new
@@ -999,7 +1000,8 @@ def tcg(problem: QuadraticProblem, X, g, S, Delta, max_inner, theta=1.0, kappa=0
         r_r = dot(r, r)
         norm_r = math.sqrt(r_r)
         if trace is not None:
-            trace.append(dict(j=j, d_Hd=d_Hd, alpha=alpha, norm_r=norm_r))
+            trace.append(dict(j=j, d_Hd=d_Hd, alpha=alpha, norm_r=norm_r, e_Pe=e_Pe, norm_r0=norm_r0,
+                              norm_d=math.sqrt(dot(delta, delta)), norm_Hd=math.sqrt(dot(Hd, Hd))))
         if j >= min_inner and norm_r <= norm_r0 * min(norm_r0 ** theta, kappa):
             status = TCG_LCON if kappa < norm_r0 ** theta else TCG_SCON
             break

@@ -139,7 +139,8 @@ def test_manifold_ops_match_oracle(oracle, d, r, n):
     assert np.abs(Yr @ np.swapaxes(Yr, 1, 2) - np.eye(d)).max() <= 1e-12
 
 
-@pytest.mark.parametrize("workgroups,pay", [(196, 20), (157, 20), (64, 9), (256, 24), (40, 15), (7, 6)])
+@pytest.mark.parametrize("workgroups,pay", [(196, 20), (157, 20), (64, 9), (256, 24), (40, 15), (7, 6),
+                                            (5, 12), (255, 12), (3, 16), (253, 16)])  # (12: (2,4), (3,3); 16: (3,4))
 def test_in_kernel_reduction_primitives(workgroups, pay):
     """The communication primitives of the one-launch solve on their own (dpgo_debug_reduction_primitives; no reference
     counterpart: they stand in for ROPTLIB's serial dot products inside tCG_TR).  chip_allreduce<2, PAY>: three chip-wide
