@@ -3,46 +3,29 @@
 
 namespace dpgo_host {
 
-int free_edges(dpgo_problem_s* p) {
-  void* ptrs[] = {p->e_p1,  p->e_p2,    p->c_ptr,  p->c_edge,   p->e_R,    p->e_t,    p->e_kappa,
-                  p->e_tau, p->e_w,     p->e_rsq,  p->q_base,   p->e_fixed, p->c_kind, p->e_counts,
-                  p->e_role, p->e_slot, p->g_ptr,  p->g_edge,   p->g_kind, p->c_base};
-  for (void* q : ptrs)
-    if (q) (void)hipFree(q);
-  p->e_role = p->g_kind = nullptr;
-  p->e_slot = p->g_ptr = p->g_edge = nullptr;
-  p->c_base = nullptr;
-  p->n_shared_edges = 0;
-  p->e_p1 = p->e_p2 = p->c_ptr = p->c_edge = nullptr;
-  p->e_R = p->e_t = p->e_kappa = p->e_tau = p->e_w = p->e_rsq = p->q_base = nullptr;
-  p->e_fixed = p->c_kind = nullptr;
-  p->e_counts = nullptr;
-  p->em = 0;
-  return DPGO_OK;
-}
 int rebuild_vals(dpgo_problem_s* p, int nnzb, const int32_t* cptr, const int32_t* cedge, const uint8_t* ckind,
                  const double* base, double sign, double* out) {
   if (nnzb <= 0) return DPGO_OK;
   const int g = std::max(1, std::min(kMaxGrid, (nnzb + kBlock - 1) / kBlock));
   if (p->d == 2)
-    hipLaunchKernelGGL(k_rebuild_Q<2>, dim3(g), dim3(kBlock), 0, p->stream, p->edges(), cptr, cedge, ckind, base,
+    hipLaunchKernelGGL(k_rebuild_Q<2>, dim3(g), dim3(kBlock), 0, p->stream, p->gnc.dev(), cptr, cedge, ckind, base,
                        sign, out, nnzb);
   else
-    hipLaunchKernelGGL(k_rebuild_Q<3>, dim3(g), dim3(kBlock), 0, p->stream, p->edges(), cptr, cedge, ckind, base,
+    hipLaunchKernelGGL(k_rebuild_Q<3>, dim3(g), dim3(kBlock), 0, p->stream, p->gnc.dev(), cptr, cedge, ckind, base,
                        sign, out, nnzb);
   HIPC(hipGetLastError());
   return DPGO_OK;
 }
 int rebuild_Q_from_weights(dpgo_problem_s* p, const double* base, double sign, double* out) {
-  return rebuild_vals(p, p->Q.nnzb, p->c_ptr, p->c_edge, p->c_kind, base, sign, out);
+  return rebuild_vals(p, p->Q.nnzb, p->gnc.c_ptr, p->gnc.c_edge, p->gnc.c_kind, base, sign, out);
 }
 int rebuild_C_from_weights(dpgo_problem_s* p, const double* base, double sign, double* out) {
-  if (!p->g_ptr) return DPGO_OK;
-  return rebuild_vals(p, p->C.nnzb, p->g_ptr, p->g_edge, p->g_kind, base, sign, out);
+  if (!p->gnc.g_ptr) return DPGO_OK;
+  return rebuild_vals(p, p->C.nnzb, p->gnc.g_ptr, p->gnc.g_edge, p->gnc.g_kind, base, sign, out);
 }
 int refresh_after_weights(dpgo_problem_s* p) {
-  CHK(rebuild_Q_from_weights(p, p->q_base, 1.0, p->Q.vals));
-  CHK(rebuild_C_from_weights(p, p->c_base, 1.0, p->C.vals));  // G itself is refreshed by the next update_G call
+  CHK(rebuild_Q_from_weights(p, p->gnc.q_base, 1.0, p->Q.vals));
+  CHK(rebuild_C_from_weights(p, p->gnc.c_base, 1.0, p->C.vals));  // G itself is refreshed by the next update_G call
   p->ml_ready = false;
   p->auto_decided = false;
   p->sym.ready = p->tcg_sym = false;
@@ -133,34 +116,34 @@ int dpgo_problem_set_reweightable_edges_ex(dpgo_problem_t p, int m, const int32_
   std::vector<int32_t> cptr, cedge, gptr, gedge;
   std::vector<uint8_t> ckind, gkind;
   flatten(lists, cptr, cedge, ckind);
-  CHK(free_edges(p));
-  p->em = m;
-  p->n_shared_edges = n_shared;
-  CHK(upload(&p->e_p1, p1, (size_t)m, p->stream));
-  CHK(upload(&p->e_p2, p2, (size_t)m, p->stream));
-  CHK(upload(&p->e_role, role_v.data(), (size_t)m, p->stream));
-  CHK(upload(&p->e_slot, slot_v.data(), (size_t)m, p->stream));
-  CHK(upload(&p->e_R, R, (size_t)m * d * d, p->stream));
-  CHK(upload(&p->e_t, t, (size_t)m * d, p->stream));
-  CHK(upload(&p->e_kappa, kappa, (size_t)m, p->stream));
-  CHK(upload(&p->e_tau, tau, (size_t)m, p->stream));
-  CHK(upload(&p->e_w, weight, (size_t)m, p->stream));
-  CHK(upload(&p->e_fixed, fixed_weight, (size_t)m, p->stream));
-  CHK(upload(&p->c_ptr, cptr.data(), cptr.size(), p->stream));
-  CHK(upload(&p->c_edge, cedge.data(), cedge.size(), p->stream));
-  CHK(upload(&p->c_kind, ckind.data(), ckind.size(), p->stream));
-  HIPC(hipMalloc(&p->e_rsq, sizeof(double) * (m > 0 ? m : 1)));
-  HIPC(hipMalloc(&p->e_counts, sizeof(int) * 4));
-  HIPC(hipMalloc(&p->q_base, sizeof(double) * (size_t)nnzb * p->b * p->b));
+  p->gnc = dpgo_problem_s::GncEdges();
+  p->gnc.em = m;
+  p->gnc.n_shared_edges = n_shared;
+  CHK(upload(p->gnc.e_p1, p1, (size_t)m, p->stream));
+  CHK(upload(p->gnc.e_p2, p2, (size_t)m, p->stream));
+  CHK(upload(p->gnc.e_role, role_v.data(), (size_t)m, p->stream));
+  CHK(upload(p->gnc.e_slot, slot_v.data(), (size_t)m, p->stream));
+  CHK(upload(p->gnc.e_R, R, (size_t)m * d * d, p->stream));
+  CHK(upload(p->gnc.e_t, t, (size_t)m * d, p->stream));
+  CHK(upload(p->gnc.e_kappa, kappa, (size_t)m, p->stream));
+  CHK(upload(p->gnc.e_tau, tau, (size_t)m, p->stream));
+  CHK(upload(p->gnc.e_w, weight, (size_t)m, p->stream));
+  CHK(upload(p->gnc.e_fixed, fixed_weight, (size_t)m, p->stream));
+  CHK(upload(p->gnc.c_ptr, cptr.data(), cptr.size(), p->stream));
+  CHK(upload(p->gnc.c_edge, cedge.data(), cedge.size(), p->stream));
+  CHK(upload(p->gnc.c_kind, ckind.data(), ckind.size(), p->stream));
+  CHK(p->gnc.e_rsq.alloc(m > 0 ? m : 1));
+  CHK(p->gnc.e_counts.alloc(4));
+  CHK(p->gnc.q_base.alloc((size_t)nnzb * p->b * p->b));
   // base = Q(current weights) - sum of the listed edges' contributions at those weights
-  CHK(rebuild_Q_from_weights(p, p->Q.vals, -1.0, p->q_base));
+  CHK(rebuild_Q_from_weights(p, p->Q.vals, -1.0, p->gnc.q_base));
   if (n_shared > 0 && cnnz > 0) {
     flatten(glists, gptr, gedge, gkind);
-    CHK(upload(&p->g_ptr, gptr.data(), gptr.size(), p->stream));
-    CHK(upload(&p->g_edge, gedge.data(), gedge.size(), p->stream));
-    CHK(upload(&p->g_kind, gkind.data(), gkind.size(), p->stream));
-    HIPC(hipMalloc(&p->c_base, sizeof(double) * (size_t)cnnz * p->b * p->b));
-    CHK(rebuild_C_from_weights(p, p->C.vals, -1.0, p->c_base));
+    CHK(upload(p->gnc.g_ptr, gptr.data(), gptr.size(), p->stream));
+    CHK(upload(p->gnc.g_edge, gedge.data(), gedge.size(), p->stream));
+    CHK(upload(p->gnc.g_kind, gkind.data(), gkind.size(), p->stream));
+    CHK(p->gnc.c_base.alloc((size_t)cnnz * p->b * p->b));
+    CHK(rebuild_C_from_weights(p, p->C.vals, -1.0, p->gnc.c_base));
   }
   HIPC(hipStreamSynchronize(p->stream));
   return DPGO_OK;
@@ -178,23 +161,23 @@ int dpgo_problem_set_reweightable_edges(dpgo_problem_t p, int m, const int32_t* 
 int dpgo_problem_gnc_reweight_device(dpgo_problem_t p, const double* X_dev, const double* nbr_tiles_dev, double mu,
                                      double barc, double w_tol, int update, int counts[3], double* max_rsq) {
   CHK(check_ready(p));
-  if (!p->e_w) return fail(DPGO_ERR_STATE, "re-weightable edges not set");
+  if (!p->gnc.e_w) return fail(DPGO_ERR_STATE, "re-weightable edges not set");
   if (!X_dev) return fail(DPGO_ERR_INVALID, "null X");
-  if (p->n_shared_edges > 0 && !nbr_tiles_dev) return fail(DPGO_ERR_INVALID, "shared edges need the neighbour tiles");
+  if (p->gnc.n_shared_edges > 0 && !nbr_tiles_dev) return fail(DPGO_ERR_INVALID, "shared edges need the neighbour tiles");
   if (update && !(mu > 0.0)) return fail(DPGO_ERR_INVALID, "GNC mu must be positive");
-  HIPC(hipMemsetAsync(p->e_counts, 0, sizeof(int) * 4, p->stream));
-  const int g = std::max(1, std::min(kMaxGrid, (p->em + kBlock - 1) / kBlock));
-  DISPATCH(p->d, p->r, hipLaunchKernelGGL((k_edge_weights<D, R>), dim3(g), dim3(kBlock), 0, p->stream, p->edges(), X_dev,
-                                          nbr_tiles_dev, mu, barc, w_tol, update, p->e_counts));
+  HIPC(hipMemsetAsync(p->gnc.e_counts, 0, sizeof(int) * 4, p->stream));
+  const int g = std::max(1, std::min(kMaxGrid, (p->gnc.em + kBlock - 1) / kBlock));
+  DISPATCH(p->d, p->r, hipLaunchKernelGGL((k_edge_weights<D, R>), dim3(g), dim3(kBlock), 0, p->stream, p->gnc.dev(), X_dev,
+                                          nbr_tiles_dev, mu, barc, w_tol, update, p->gnc.e_counts));
   HIPC(hipGetLastError());
   if (update) CHK(refresh_after_weights(p));
   int h[4] = {0, 0, 0, 0};
-  HIPC(hipMemcpyAsync(h, p->e_counts, sizeof(int) * 4, hipMemcpyDeviceToHost, p->stream));
+  HIPC(hipMemcpyAsync(h, p->gnc.e_counts, sizeof(int) * 4, hipMemcpyDeviceToHost, p->stream));
   std::vector<double> rs;
   if (max_rsq) {
-    rs.resize(p->em > 0 ? p->em : 1, 0.0);
-    if (p->em > 0)
-      HIPC(hipMemcpyAsync(rs.data(), p->e_rsq, sizeof(double) * p->em, hipMemcpyDeviceToHost, p->stream));
+    rs.resize(p->gnc.em > 0 ? p->gnc.em : 1, 0.0);
+    if (p->gnc.em > 0)
+      HIPC(hipMemcpyAsync(rs.data(), p->gnc.e_rsq, sizeof(double) * p->gnc.em, hipMemcpyDeviceToHost, p->stream));
   }
   HIPC(hipStreamSynchronize(p->stream));
   if (counts) {
@@ -204,7 +187,7 @@ int dpgo_problem_gnc_reweight_device(dpgo_problem_t p, const double* X_dev, cons
   }
   if (max_rsq) {
     double mx = 0.0;
-    for (int e = 0; e < p->em; ++e) mx = std::max(mx, rs[e]);
+    for (int e = 0; e < p->gnc.em; ++e) mx = std::max(mx, rs[e]);
     *max_rsq = mx;
   }
   return DPGO_OK;
@@ -215,7 +198,7 @@ int dpgo_problem_gnc_reweight(dpgo_problem_t p, const double* X_host, double mu,
                               int counts[3], double* max_rsq) {
   CHK(check_ready(p));
   if (!X_host) return fail(DPGO_ERR_INVALID, "null X");
-  if (p->n_shared_edges > 0) return fail(DPGO_ERR_STATE, "shared edges need the device flavour (neighbour tiles)");
+  if (p->gnc.n_shared_edges > 0) return fail(DPGO_ERR_STATE, "shared edges need the device flavour (neighbour tiles)");
   CHK(h2d(p, p->x2, X_host));
   return dpgo_problem_gnc_reweight_device(p, p->x2, nullptr, mu, barc, w_tol, update, counts, max_rsq);
 }
@@ -223,9 +206,9 @@ int dpgo_problem_gnc_reweight(dpgo_problem_t p, const double* X_host, double mu,
 
 int dpgo_problem_set_edge_weights(dpgo_problem_t p, const double* weight_host) {
   CHK(check_ready(p));
-  if (!p->e_w) return fail(DPGO_ERR_STATE, "re-weightable edges not set");
+  if (!p->gnc.e_w) return fail(DPGO_ERR_STATE, "re-weightable edges not set");
   if (!weight_host) return fail(DPGO_ERR_INVALID, "null weights");
-  if (p->em > 0) HIPC(hipMemcpyAsync(p->e_w, weight_host, sizeof(double) * p->em, hipMemcpyHostToDevice, p->stream));
+  if (p->gnc.em > 0) HIPC(hipMemcpyAsync(p->gnc.e_w, weight_host, sizeof(double) * p->gnc.em, hipMemcpyHostToDevice, p->stream));
   CHK(refresh_after_weights(p));
   HIPC(hipStreamSynchronize(p->stream));
   return DPGO_OK;
@@ -234,11 +217,11 @@ int dpgo_problem_set_edge_weights(dpgo_problem_t p, const double* weight_host) {
 
 int dpgo_problem_get_edge_weights(dpgo_problem_t p, double* weight_host, double* rsq_host) {
   CHK(check_ready(p));
-  if (!p->e_w) return fail(DPGO_ERR_STATE, "re-weightable edges not set");
-  if (weight_host && p->em > 0)
-    HIPC(hipMemcpyAsync(weight_host, p->e_w, sizeof(double) * p->em, hipMemcpyDeviceToHost, p->stream));
-  if (rsq_host && p->em > 0)
-    HIPC(hipMemcpyAsync(rsq_host, p->e_rsq, sizeof(double) * p->em, hipMemcpyDeviceToHost, p->stream));
+  if (!p->gnc.e_w) return fail(DPGO_ERR_STATE, "re-weightable edges not set");
+  if (weight_host && p->gnc.em > 0)
+    HIPC(hipMemcpyAsync(weight_host, p->gnc.e_w, sizeof(double) * p->gnc.em, hipMemcpyDeviceToHost, p->stream));
+  if (rsq_host && p->gnc.em > 0)
+    HIPC(hipMemcpyAsync(rsq_host, p->gnc.e_rsq, sizeof(double) * p->gnc.em, hipMemcpyDeviceToHost, p->stream));
   HIPC(hipStreamSynchronize(p->stream));
   return DPGO_OK;
 }
@@ -249,7 +232,7 @@ namespace {
 // Masked PCG: solve  mask A mask x = rhs  (rhs already masked) for the tiles x; A = the handle's Q.  Host-driven
 // (two tiny read-backs per iteration): initialisation runs once per problem, outside the hot path.
 struct InitBufs {
-  double *x, *r, *z, *p, *Ap, *diag, *partial;
+  DevBuf<double> x, r, z, p, Ap, diag, partial;
 };
 int init_dot(dpgo_problem_s* h, const double* a, const double* b, InitBufs& w, size_t total, int g, double* out) {
   hipLaunchKernelGGL(k_init_dot, dim3(g), dim3(kBlock), 0, h->stream, a, b, w.partial, total);
@@ -348,12 +331,11 @@ int dpgo_chordal_initialization(int d, int n, int m, const int32_t* p1, const in
   dpgo_problem_s* hr = hq[0];
   dpgo_problem_s* ht = hq[1];
   const size_t total = (size_t)n * hr->T;
-  TmpDev tmp;
-  InitBufs w{};
-  double *rhs = nullptr, *V = nullptr, *Tr = nullptr;
-  for (double** v : {&w.x, &w.r, &w.z, &w.p, &w.Ap, &rhs, &V, &Tr}) CHK(tmp.alloc(v, sizeof(double) * total));
-  CHK(tmp.alloc(&w.diag, sizeof(double) * (size_t)n * b));
-  CHK(tmp.alloc(&w.partial, sizeof(double) * kMaxGrid));
+  InitBufs w;
+  DevBuf<double> rhs, V, Tr;
+  for (DevBuf<double>* v : {&w.x, &w.r, &w.z, &w.p, &w.Ap, &rhs, &V, &Tr}) CHK(v->alloc(total));
+  CHK(w.diag.alloc((size_t)n * b));
+  CHK(w.partial.alloc(kMaxGrid));
   const int gflat = std::max(1, std::min(kMaxGrid, (n + kBlock - 1) / kBlock));
   const int gtot = std::max(1, std::min(kMaxGrid, (int)((total + kBlock - 1) / kBlock)));
   int it_rot = 0, it_tr = 0;
@@ -496,11 +478,10 @@ int dpgo_round_trajectory(int r, int d, int n, const double* X_host, const doubl
                           int device) {
   if (!X_host || !T_host) return fail(DPGO_ERR_INVALID, "null pointer");
   CHK(manifold_args(r, d, n, device));
-  TmpDev tmp;
   const size_t xb = sizeof(double) * (size_t)n * (d + 1) * r, tb = sizeof(double) * (size_t)n * (d + 1) * d;
-  double *X = nullptr, *T = nullptr;
-  CHK(tmp.alloc(&X, xb));
-  CHK(tmp.alloc(&T, tb));
+  DevBuf<double> X, T;
+  CHK(X.alloc((size_t)n * (d + 1) * r));
+  CHK(T.alloc((size_t)n * (d + 1) * d));
   HIPC(hipMemcpy(X, X_host, xb, hipMemcpyHostToDevice));
   CHK(dpgo_round_trajectory_device(r, d, n, X, anchor_host, T, nullptr));
   HIPC(hipMemcpy(T_host, T, tb, hipMemcpyDeviceToHost));
@@ -543,7 +524,10 @@ int dpgo_permute_tiles_device(int r, int d, int n, const int32_t* new_index_dev,
 
 struct dpgo_exchange_plan_s {
   int device = 0, T = 0, nmsg = 0, total = 0;
-  void *src = nullptr, *idx = nullptr, *dst = nullptr, *first = nullptr;
+  DevBuf<const double*> src;
+  DevBuf<const int32_t*> idx;
+  DevBuf<double*> dst;
+  DevBuf<int32_t> first;
 };
 
 
@@ -564,10 +548,10 @@ int dpgo_exchange_plan_create(dpgo_exchange_plan_t* out, int r, int d, int nmsg,
   pl->nmsg = nmsg;
   pl->total = first[nmsg];
   int rc = [&]() -> int {
-    HIPC(hipMalloc(&pl->src, sizeof(void*) * nmsg));
-    HIPC(hipMalloc(&pl->idx, sizeof(void*) * nmsg));
-    HIPC(hipMalloc(&pl->dst, sizeof(void*) * nmsg));
-    HIPC(hipMalloc(&pl->first, sizeof(int32_t) * (nmsg + 1)));
+    CHK(pl->src.alloc(nmsg));
+    CHK(pl->idx.alloc(nmsg));
+    CHK(pl->dst.alloc(nmsg));
+    CHK(pl->first.alloc(nmsg + 1));
     HIPC(hipMemcpy(pl->src, src_dev, sizeof(void*) * nmsg, hipMemcpyHostToDevice));
     HIPC(hipMemcpy(pl->idx, idx_dev, sizeof(void*) * nmsg, hipMemcpyHostToDevice));
     HIPC(hipMemcpy(pl->dst, dst_dev, sizeof(void*) * nmsg, hipMemcpyHostToDevice));
@@ -587,8 +571,7 @@ int dpgo_exchange_plan_run(dpgo_exchange_plan_t pl, void* stream) {
   if (!pl) return fail(DPGO_ERR_INVALID, "null exchange plan");
   if (pl->total == 0) return DPGO_OK;
   HIPC(hipSetDevice(pl->device));
-  const ExchangeTable tb{(const double* const*)pl->src, (const int32_t* const*)pl->idx, (double* const*)pl->dst,
-                         (const int32_t*)pl->first, pl->nmsg};
+  const ExchangeTable tb{pl->src, pl->idx, pl->dst, pl->first, pl->nmsg};
   const int g = std::max(1, std::min(kMaxGrid, (pl->total + kBlock / 4 - 1) / (kBlock / 4)));
   switch (pl->T) {
 #define CASE_T(TT) case TT: hipLaunchKernelGGL((k_gather_tiles_batched<TT>), dim3(g), dim3(kBlock), 0, (hipStream_t)stream, tb); break;
@@ -646,9 +629,6 @@ int dpgo_flags_wait_device_checked(int n, unsigned long long* const* words_dev, 
 }
 
 int dpgo_exchange_plan_destroy(dpgo_exchange_plan_t pl) {
-  if (!pl) return DPGO_OK;
-  for (void* q : {pl->src, pl->idx, pl->dst, pl->first})
-    if (q) (void)hipFree(q);
   delete pl;
   return DPGO_OK;
 }
@@ -674,11 +654,10 @@ int dpgo_max_translation_distance_device(int r, int d, int n, const double* X_de
 int dpgo_manifold_project(int r, int d, int n, const double* M, double* out, int device) {
   if (!M || !out) return fail(DPGO_ERR_INVALID, "null pointer");
   CHK(manifold_args(r, d, n, device));
-  TmpDev tmp;
-  const size_t vb = sizeof(double) * (size_t)n * (d + 1) * r;
-  double *a = nullptr, *o = nullptr;
-  CHK(tmp.alloc(&a, vb));
-  CHK(tmp.alloc(&o, vb));
+  const size_t total = (size_t)n * (d + 1) * r, vb = sizeof(double) * total;
+  DevBuf<double> a, o;
+  CHK(a.alloc(total));
+  CHK(o.alloc(total));
   HIPC(hipMemcpy(a, M, vb, hipMemcpyHostToDevice));
   CHK(dpgo_manifold_project_device(r, d, n, a, o, nullptr));
   HIPC(hipMemcpy(out, o, vb, hipMemcpyDeviceToHost));
@@ -689,12 +668,9 @@ int dpgo_manifold_project(int r, int d, int n, const double* M, double* out, int
 int dpgo_manifold_tangent_project(int r, int d, int n, const double* X, const double* V, double* out, int device) {
   if (!X || !V || !out) return fail(DPGO_ERR_INVALID, "null pointer");
   CHK(manifold_args(r, d, n, device));
-  TmpDev tmp;
-  const size_t vb = sizeof(double) * (size_t)n * (d + 1) * r;
-  double *x = nullptr, *v = nullptr, *o = nullptr;
-  CHK(tmp.alloc(&x, vb));
-  CHK(tmp.alloc(&v, vb));
-  CHK(tmp.alloc(&o, vb));
+  const size_t total = (size_t)n * (d + 1) * r, vb = sizeof(double) * total;
+  DevBuf<double> x, v, o;
+  for (DevBuf<double>* q : {&x, &v, &o}) CHK(q->alloc(total));
   HIPC(hipMemcpy(x, X, vb, hipMemcpyHostToDevice));
   HIPC(hipMemcpy(v, V, vb, hipMemcpyHostToDevice));
   DISPATCH(d, r, hipLaunchKernelGGL((k_precond<D, R>), dim3(tiles_grid(d, n)), dim3(kBlock), 0, (hipStream_t) nullptr,
@@ -709,12 +685,9 @@ int dpgo_manifold_retract(int r, int d, int n, const double* X, const double* et
                           int device) {
   if (!X || !eta || !out) return fail(DPGO_ERR_INVALID, "null pointer");
   CHK(manifold_args(r, d, n, device));
-  TmpDev tmp;
-  const size_t vb = sizeof(double) * (size_t)n * (d + 1) * r;
-  double *x = nullptr, *v = nullptr, *o = nullptr;
-  CHK(tmp.alloc(&x, vb));
-  CHK(tmp.alloc(&v, vb));
-  CHK(tmp.alloc(&o, vb));
+  const size_t total = (size_t)n * (d + 1) * r, vb = sizeof(double) * total;
+  DevBuf<double> x, v, o;
+  for (DevBuf<double>* q : {&x, &v, &o}) CHK(q->alloc(total));
   HIPC(hipMemcpy(x, X, vb, hipMemcpyHostToDevice));
   HIPC(hipMemcpy(v, eta, vb, hipMemcpyHostToDevice));
   DISPATCH(d, r, hipLaunchKernelGGL((k_retract<D, R>), dim3(tiles_grid(d, n)), dim3(kBlock), 0, (hipStream_t) nullptr,

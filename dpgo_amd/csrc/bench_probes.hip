@@ -34,66 +34,67 @@ int dpgo_bench_hess_rotating(dpgo_problem_t p, int nsets, int reps, int warmup, 
   p->hstate->max_inner = 1 << 30;
   p->hstate->min_inner = 1 << 30;  // the convergence test is never evaluated, whatever the partial sums hold
   CHK(push_state(p));
-  // every operand of the tCG-step kernel gets nsets private copies; the handle's pointers are swapped per launch
-  const size_t vbytes = sizeof(double) * (size_t)p->Q.nnzb * p->b * p->b;
-  const size_t cbytes = sizeof(int32_t) * (size_t)p->Q.nnzb;
-  const size_t sbytes = sizeof(double) * (size_t)p->n * p->d * p->d;
+  // every operand of the tCG-step kernel gets nsets private copies; per launch a set's buffers are exchanged with the
+  // handle's own and exchanged back before the launch helper's result is looked at: the handle never keeps a copy, a set
+  // never keeps the handle's buffer, whichever way this function is left
   CHK(resolve_tcg_storage(p));
   const bool symq = p->tcg_sym;  // the kernel reads the symmetric copy: that is what rotates
   auto& SY = p->sym;
+  const size_t nvals = (size_t)p->Q.nnzb * p->b * p->b, nu = (size_t)SY.nu, nl = (size_t)std::max(1, SY.nl);
+  const size_t nvec = (size_t)p->n * p->T;
   struct Set {
-    double *vals = nullptr, *x1 = nullptr, *S1 = nullptr, *z = nullptr, *delta = nullptr, *Hd = nullptr;
-    int32_t* colidx = nullptr;
-    double* uv = nullptr;
-    int32_t *uc = nullptr, *lc = nullptr, *ls = nullptr;
+    DevBuf<double> vals, x1, S1, z, delta, Hd, uv;
+    DevBuf<int32_t> colidx, uc, lc, ls;
   };
   std::vector<Set> sets(nsets);
-  const Set orig{p->Q.vals, p->x1, p->S1, p->z, p->delta, p->Hd, p->Q.colidx, SY.uvalsT, SY.ucol, SY.lcol, SY.lslot};
   bool ok = true;
-  auto dup = [&](auto** dst, const void* src, size_t bytes) {
+  auto dup = [&](auto& dst, const void* src, size_t count) {
     if (!ok) return;
-    if (hipMalloc(dst, bytes) != hipSuccess) {
+    if (dst.alloc(count) != DPGO_OK) {
       ok = false;
       return;
     }
-    (void)hipMemcpyAsync(*dst, src, bytes, hipMemcpyDeviceToDevice, p->stream);
+    (void)hipMemcpyAsync(dst, src, sizeof(*dst.get()) * count, hipMemcpyDeviceToDevice, p->stream);
   };
   for (auto& st : sets) {
     if (symq) {
-      dup(&st.uv, orig.uv, sizeof(double) * (size_t)SY.nu * p->b * p->b);
-      dup(&st.uc, orig.uc, sizeof(int32_t) * (size_t)SY.nu);
-      dup(&st.lc, orig.lc, sizeof(int32_t) * (size_t)std::max(1, SY.nl));
-      dup(&st.ls, orig.ls, sizeof(int32_t) * (size_t)std::max(1, SY.nl));
+      dup(st.uv, SY.uvalsT, nu * p->b * p->b);
+      dup(st.uc, SY.ucol, nu);
+      dup(st.lc, SY.lcol, nl);
+      dup(st.ls, SY.lslot, nl);
     } else {
-      dup(&st.vals, orig.vals, vbytes);
-      dup(&st.colidx, orig.colidx, cbytes);
+      dup(st.vals, p->Q.vals, nvals);
+      dup(st.colidx, p->Q.colidx, (size_t)p->Q.nnzb);
     }
-    dup(&st.x1, orig.x1, p->vec_bytes());
-    dup(&st.S1, orig.S1, sbytes);
-    dup(&st.z, orig.z, p->vec_bytes());
-    dup(&st.delta, orig.delta, p->vec_bytes());
-    dup(&st.Hd, orig.Hd, p->vec_bytes());
+    dup(st.x1, p->x1, nvec);
+    dup(st.S1, p->S1, (size_t)p->n * p->d * p->d);
+    dup(st.z, p->z, nvec);
+    dup(st.delta, p->delta, nvec);
+    dup(st.Hd, p->Hd, nvec);
   }
-  auto use = [&](const Set& st) {
+  auto exchange = [&](Set& st) {
     if (symq) {
-      SY.uvalsT = st.uv;
-      SY.ucol = st.uc;
-      SY.lcol = st.lc;
-      SY.lslot = st.ls;
+      std::swap(SY.uvalsT, st.uv);
+      std::swap(SY.ucol, st.uc);
+      std::swap(SY.lcol, st.lc);
+      std::swap(SY.lslot, st.ls);
     } else {
-      p->Q.vals = st.vals;
-      p->Q.colidx = st.colidx;
+      std::swap(p->Q.vals, st.vals);
+      std::swap(p->Q.colidx, st.colidx);
     }
-    p->x1 = st.x1;
-    p->S1 = st.S1;
-    p->z = st.z;
-    p->delta = st.delta;
-    p->Hd = st.Hd;
+    std::swap(p->x1_buf, st.x1);
+    p->x1 = p->x1_buf;
+    std::swap(p->S1, st.S1);
+    std::swap(p->z, st.z);
+    std::swap(p->delta, st.delta);
+    std::swap(p->Hd, st.Hd);
   };
   int rc = ok ? DPGO_OK : fail(DPGO_ERR_HIP, "hipMalloc failed for the rotating buffer sets");
   auto launch = [&](int i) -> int {
-    use(sets[i % nsets]);
-    return launch_tcg_hess_with(p, p->dstate, p->dstate + 1, 0, nullptr, 0u);
+    exchange(sets[i % nsets]);
+    const int r2 = launch_tcg_hess_with(p, p->dstate, p->dstate + 1, 0, nullptr, 0u);
+    exchange(sets[i % nsets]);
+    return r2;
   };
   float ms = 0.f;
   if (rc == DPGO_OK) {
@@ -109,16 +110,10 @@ int dpgo_bench_hess_rotating(dpgo_problem_t p, int nsets, int reps, int warmup, 
     (void)hipEventDestroy(e0);
     (void)hipEventDestroy(e1);
   }
-  use(orig);
   (void)hipStreamSynchronize(p->stream);
-  for (auto& st : sets) {
-    void* ptrs[] = {st.vals, st.colidx, st.x1, st.S1, st.z, st.delta, st.Hd, st.uv, st.uc, st.lc, st.ls};
-    for (void* q : ptrs)
-      if (q) (void)hipFree(q);
-  }
   if (rc != DPGO_OK) return rc;
   *avg_ms = (double)ms / reps;
-  return DPGO_OK;
+  return DPGO_OK;  // (the sets are released here)
 }
 
 
@@ -128,23 +123,16 @@ int bench_spmm_sym_rotating(dpgo_problem_s* p, int nsets, int reps, int warmup, 
   const auto& S = p->sym;
   const size_t vbytes = sizeof(double) * (size_t)S.nu * p->b * p->b;
   struct Set {
-    double *v = nullptr, *x = nullptr, *o = nullptr;
-    int32_t *uc = nullptr, *lc = nullptr, *ls = nullptr;
+    DevBuf<double> v, x, o;
+    DevBuf<int32_t> uc, lc, ls;
   };
-  std::vector<Set> sets(nsets);
+  std::vector<Set> sets(nsets);  // (released when this function returns, whichever way)
+  const size_t nvec = (size_t)p->n * p->T;
   int rc = DPGO_OK;
-  auto cleanup = [&]() {
-    for (auto& st : sets) {
-      void* ptrs[] = {st.v, st.x, st.o, st.uc, st.lc, st.ls};
-      for (void* q : ptrs)
-        if (q) (void)hipFree(q);
-    }
-  };
   for (auto& st : sets) {
-    if (hipMalloc(&st.v, vbytes) != hipSuccess || hipMalloc(&st.x, p->vec_bytes()) != hipSuccess ||
-        hipMalloc(&st.o, p->vec_bytes()) != hipSuccess || hipMalloc(&st.uc, sizeof(int32_t) * S.nu) != hipSuccess ||
-        hipMalloc(&st.lc, sizeof(int32_t) * std::max(1, S.nl)) != hipSuccess ||
-        hipMalloc(&st.ls, sizeof(int32_t) * std::max(1, S.nl)) != hipSuccess) {
+    if (st.v.alloc(vbytes / sizeof(double)) != DPGO_OK || st.x.alloc(nvec) != DPGO_OK || st.o.alloc(nvec) != DPGO_OK ||
+        st.uc.alloc(S.nu) != DPGO_OK || st.lc.alloc(std::max(1, S.nl)) != DPGO_OK ||
+        st.ls.alloc(std::max(1, S.nl)) != DPGO_OK) {
       rc = fail(DPGO_ERR_HIP, "hipMalloc failed for the rotating buffer sets");
       break;
     }
@@ -154,10 +142,7 @@ int bench_spmm_sym_rotating(dpgo_problem_s* p, int nsets, int reps, int warmup, 
     (void)hipMemcpyAsync(st.ls, S.lslot, sizeof(int32_t) * S.nl, hipMemcpyDeviceToDevice, p->stream);
     (void)hipMemcpyAsync(st.x, p->x1, p->vec_bytes(), hipMemcpyDeviceToDevice, p->stream);
   }
-  if (rc != DPGO_OK) {
-    cleanup();
-    return rc;
-  }
+  if (rc != DPGO_OK) return rc;
   auto launch = [&](int i) {
     const Set& st = sets[i % nsets];
     return launch_spmm_sym(p, BsrSymDev{S.urow, st.uc, st.v, S.lrow, st.lc, st.ls, S.tord}, st.x, nullptr, st.o);
@@ -174,7 +159,6 @@ int bench_spmm_sym_rotating(dpgo_problem_s* p, int nsets, int reps, int warmup, 
   (void)hipEventElapsedTime(&ms, e0, e1);
   (void)hipEventDestroy(e0);
   (void)hipEventDestroy(e1);
-  cleanup();
   if (rc != DPGO_OK) return rc;
   *avg_ms = (double)ms / reps;
   if (set_bytes)
@@ -197,47 +181,42 @@ int dpgo_bench_spmm_rotating(dpgo_problem_t p, int nsets, int reps, int warmup, 
   // data that left the 256 MB Infinity Cache ("rotate >= 3 buffer sets > 256 MB total")
   const size_t vbytes = sizeof(double) * (size_t)p->Q.nnzb * p->b * p->b;
   const size_t cbytes = sizeof(int32_t) * (size_t)p->Q.nnzb;
-  std::vector<Bsr> mats(nsets);
-  std::vector<double*> xs(nsets, nullptr), outs(nsets, nullptr);
-  int rc = DPGO_OK;
-  auto cleanup = [&]() {
-    for (int k = 0; k < nsets; ++k) {
-      if (mats[k].vals) (void)hipFree(mats[k].vals);
-      if (mats[k].colidx) (void)hipFree(mats[k].colidx);
-      if (xs[k]) (void)hipFree(xs[k]);
-      if (outs[k]) (void)hipFree(outs[k]);
-    }
+  struct Set {
+    DevBuf<double> vals, x, out;
+    DevBuf<int32_t> colidx;
   };
-  for (int k = 0; k < nsets && rc == DPGO_OK; ++k) {
-    mats[k] = p->Q;  // shares rowptr (0.4 MB)
-    mats[k].vals = nullptr;
-    mats[k].colidx = nullptr;
-    if (hipMalloc(&mats[k].vals, vbytes) != hipSuccess || hipMalloc(&mats[k].colidx, cbytes) != hipSuccess ||
-        hipMalloc(&xs[k], p->vec_bytes()) != hipSuccess || hipMalloc(&outs[k], p->vec_bytes()) != hipSuccess) {
+  std::vector<Set> sets(nsets);  // (released when this function returns, whichever way)
+  const size_t nvec = (size_t)p->n * p->T;
+  int rc = DPGO_OK;
+  for (auto& st : sets) {
+    if (st.vals.alloc(vbytes / sizeof(double)) != DPGO_OK || st.colidx.alloc(p->Q.nnzb) != DPGO_OK ||
+        st.x.alloc(nvec) != DPGO_OK || st.out.alloc(nvec) != DPGO_OK) {
       rc = fail(DPGO_ERR_HIP, "hipMalloc failed for the rotating buffer sets");
       break;
     }
-    (void)hipMemcpyAsync(mats[k].vals, p->Q.vals, vbytes, hipMemcpyDeviceToDevice, p->stream);
-    (void)hipMemcpyAsync(mats[k].colidx, p->Q.colidx, cbytes, hipMemcpyDeviceToDevice, p->stream);
-    (void)hipMemcpyAsync(xs[k], p->x1, p->vec_bytes(), hipMemcpyDeviceToDevice, p->stream);
+    (void)hipMemcpyAsync(st.vals, p->Q.vals, vbytes, hipMemcpyDeviceToDevice, p->stream);
+    (void)hipMemcpyAsync(st.colidx, p->Q.colidx, cbytes, hipMemcpyDeviceToDevice, p->stream);
+    (void)hipMemcpyAsync(st.x, p->x1, p->vec_bytes(), hipMemcpyDeviceToDevice, p->stream);
   }
-  if (rc != DPGO_OK) {
-    cleanup();
-    return rc;
-  }
+  if (rc != DPGO_OK) return rc;
+  // a view per set: private values and block columns, Q's row pointers shared (0.4 MB); the plain kernel, as launch_spmm
+  // runs it on any matrix that is not the handle's Q
+  auto launch = [&](int i) {
+    const Set& st = sets[i % nsets];
+    return launch_spmm_view(p, BsrDev{p->Q.rowptr, st.colidx, st.vals}, st.x, nullptr, st.out, p->n, p->grid_spmm());
+  };
   hipEvent_t e0, e1;
   (void)hipEventCreate(&e0);
   (void)hipEventCreate(&e1);
-  for (int i = 0; i < warmup && rc == DPGO_OK; ++i) rc = launch_spmm(p, mats[i % nsets], xs[i % nsets], nullptr, outs[i % nsets]);
+  for (int i = 0; i < warmup && rc == DPGO_OK; ++i) rc = launch(i);
   (void)hipEventRecord(e0, p->stream);
-  for (int i = 0; i < reps && rc == DPGO_OK; ++i) rc = launch_spmm(p, mats[i % nsets], xs[i % nsets], nullptr, outs[i % nsets]);
+  for (int i = 0; i < reps && rc == DPGO_OK; ++i) rc = launch(i);
   (void)hipEventRecord(e1, p->stream);
   (void)hipEventSynchronize(e1);
   float ms = 0.f;
   (void)hipEventElapsedTime(&ms, e0, e1);
   (void)hipEventDestroy(e0);
   (void)hipEventDestroy(e1);
-  cleanup();
   if (rc != DPGO_OK) return rc;
   *avg_ms = (double)ms / reps;
   if (set_bytes) *set_bytes = (double)(vbytes + cbytes + 2 * p->vec_bytes());
@@ -450,10 +429,10 @@ extern "C" int dpgo_debug_reduction_primitives(int workgroups, int pay, int step
   HIPC(hipGetDevice(&device));
   HIPC(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device));
   if (workgroups > cus) return fail(DPGO_ERR_INVALID, "more workgroups than the device holds at once");
-  unsigned long long* gran = nullptr;
-  int* error = nullptr;
-  HIPC(hipMalloc(&gran, sizeof(unsigned long long) * kGranWords));
-  HIPC(hipMalloc(&error, sizeof(int)));
+  DevBuf<unsigned long long> gran;
+  DevBuf<int> error;
+  CHK(gran.alloc(kGranWords));
+  CHK(error.alloc(1));
   HIPC(hipMemset(gran, 0, sizeof(unsigned long long) * kGranWords));
   HIPC(hipMemset(error, 0, sizeof(int)));
   const unsigned salt = 5u << 20;
@@ -467,16 +446,12 @@ extern "C" int dpgo_debug_reduction_primitives(int workgroups, int pay, int step
     CASE_(6) CASE_(9) CASE_(12) CASE_(15) CASE_(16) CASE_(20) CASE_(24)
 #undef CASE_
     default:
-      (void)hipFree(gran);
-      (void)hipFree(error);
       return fail(DPGO_ERR_UNSUPPORTED, "payload size: one of 6, 9, 12, 15, 16, 20, 24");
   }
   HIPC(hipGetLastError());
   HIPC(hipDeviceSynchronize());
   int herr = 0;
   HIPC(hipMemcpy(&herr, error, sizeof(int), hipMemcpyDeviceToHost));
-  (void)hipFree(gran);
-  (void)hipFree(error);
   if (herr) return fail(DPGO_ERR_HIP, "a reduction timed out");
   return DPGO_OK;
 }

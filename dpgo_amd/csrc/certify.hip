@@ -90,42 +90,41 @@ struct Cert {
   dpgo_problem_s* p;
   int d, r, n;
   bool sym = false;     // products read the symmetric copy of Q
-  double* S = nullptr;  // Lambda blocks at X (k_grad)
-  double* zero = nullptr;  // a zero iterate: the multilevel cycle's projection at it is the identity
-  double* part = nullptr;  // per-workgroup partials
-  double* red = nullptr;   // reduced Gram blocks (device)
-  double* coef = nullptr;  // coefficient matrices of k_cert_combine (device)
-  double* hbuf = nullptr;  // pinned: reduced Gram blocks (host)
-  double* hcoef = nullptr; // pinned: coefficient ring
+  DevBuf<double> S;     // Lambda blocks at X (k_grad)
+  DevBuf<double> zero;  // a zero iterate: the multilevel cycle's projection at it is the identity
+  DevBuf<double> part;  // per-workgroup partials
+  DevBuf<double> red;   // reduced Gram blocks (device)
+  DevBuf<double> coef;  // coefficient matrices of k_cert_combine (device)
+  DevBuf<double> qdiag; // per-workgroup maxima of q_scale
+  PinBuf<double> hbuf;  // reduced Gram blocks (host)
+  PinBuf<double> hcoef; // coefficient ring
+  std::vector<DevBuf<double>> vecs;  // the solver's pose vectors (vec)
   int coef_slot = 0;
   int products = 0;
   int precond = DPGO_PRECOND_NONE;
   double shift = 0.1;
-  TmpDev tmp;
   static constexpr int kCoefSlots = 8;
   static constexpr int kCoefCap = kCertMaxOut * kCertMaxBlocks * 36;
   static constexpr int kGramWg = 512;  // workgroups of k_cert_gram (partials: kGramWg x kCertMaxPairs x 36)
 
-  ~Cert() {
-    if (hbuf) (void)hipHostFree(hbuf);
-    if (hcoef) (void)hipHostFree(hcoef);
-  }
   size_t vec_bytes() const { return (size_t)n * (d + 1) * r * sizeof(double); }
   int flat_grid() const {
     const size_t cols = (size_t)n * (d + 1);
     return (int)std::max<size_t>(1, std::min<size_t>(kMaxGrid, (cols + kBlock - 1) / kBlock));
   }
   int vec(double** out) {
-    CHK(tmp.alloc(out, vec_bytes()));
+    vecs.emplace_back();
+    CHK(vecs.back().alloc((size_t)n * (d + 1) * r));
+    *out = vecs.back();
     return DPGO_OK;
   }
   int init() {
-    CHK(tmp.alloc(&S, sizeof(double) * (size_t)n * d * d));
-    CHK(tmp.alloc(&part, sizeof(double) * (size_t)std::max(kPartialCap * 36, kGramWg * kCertMaxPairs * 36)));
-    CHK(tmp.alloc(&red, sizeof(double) * kCertMaxPairs * 36));
-    CHK(tmp.alloc(&coef, sizeof(double) * kCoefSlots * kCoefCap));
-    HIPC(hipHostMalloc(&hbuf, sizeof(double) * kCertMaxPairs * 36, hipHostMallocDefault));
-    HIPC(hipHostMalloc(&hcoef, sizeof(double) * kCoefSlots * kCoefCap, hipHostMallocDefault));
+    CHK(S.alloc((size_t)n * d * d));
+    CHK(part.alloc((size_t)std::max(kPartialCap * 36, kGramWg * kCertMaxPairs * 36)));
+    CHK(red.alloc(kCertMaxPairs * 36));
+    CHK(coef.alloc(kCoefSlots * kCoefCap));
+    CHK(hbuf.alloc(kCertMaxPairs * 36));
+    CHK(hcoef.alloc(kCoefSlots * kCoefCap));
     return DPGO_OK;
   }
 
@@ -150,7 +149,7 @@ struct Cert {
     HIPC(hipGetLastError());
     HIPC(hipMemcpyAsync(hbuf, red, sizeof(double) * E, hipMemcpyDeviceToHost, p->stream));
     HIPC(hipStreamSynchronize(p->stream));
-    out.assign(hbuf, hbuf + E);
+    out.assign(hbuf.get(), hbuf + E);
     return DPGO_OK;
   }
   // G[k] = B[x_k] B[y_k]^T for every pair k (r x r blocks, row-major, concatenated)
@@ -217,10 +216,9 @@ std::vector<double> eye(int r, double s = 1.0) {
 }
 
 // max_i max diag(Q_ii)
-int q_scale(dpgo_problem_s* p, TmpDev& tmp, double* out) {
+int q_scale(dpgo_problem_s* p, DevBuf<double>& dv, double* out) {
   const int g = (p->n + kBlock - 1) / kBlock;
-  double* dv = nullptr;
-  CHK(tmp.alloc(&dv, sizeof(double) * g));
+  CHK(dv.alloc(g));
   if (p->d == 2)
     hipLaunchKernelGGL(k_cert_scale<2>, dim3(g), dim3(kBlock), 0, p->stream, p->Q.dev(), dv, p->n);
   else
@@ -279,7 +277,7 @@ int certify_impl(dpgo_problem_s* p, const double* X, const dpgo_certify_params* 
   CHK(poll_state(p));
   res->gradnorm = p->hstate->ngf;
   double scale = 0.0;
-  CHK(q_scale(p, c.tmp, &scale));
+  CHK(q_scale(p, c.qdiag, &scale));
   if (!(scale > 0.0)) return fail(DPGO_ERR_INVALID, "certify: Q has no positive diagonal");
   res->scale = scale;
   const double eta = prm.eta * scale, tol = prm.tol_rel * scale;
@@ -288,7 +286,7 @@ int certify_impl(dpgo_problem_s* p, const double* X, const dpgo_certify_params* 
   if (precond == DPGO_PRECOND_MULTILEVEL) {
     CHK(ml_ensure(p, prm.precond_shift));
     CHK(ml_ops32_ensure(p));
-    CHK(c.tmp.alloc(&c.zero, c.vec_bytes()));
+    CHK(c.zero.alloc((size_t)c.n * (c.d + 1) * c.r));
     HIPC(hipMemsetAsync(c.zero, 0, c.vec_bytes(), p->stream));
   }
 
@@ -613,9 +611,8 @@ int dpgo_problem_certify(dpgo_problem_t h, const double* X_host, const dpgo_cert
                          dpgo_certify_result* result, double* witness_host) {
   CHK(check_ready(h));
   if (!X_host) return fail(DPGO_ERR_INVALID, "null X");
-  TmpDev tmp;
-  double* X = nullptr;
-  CHK(tmp.alloc(&X, h->vec_bytes()));
+  DevBuf<double> X;
+  CHK(X.alloc((size_t)h->n * h->T));
   CHK(h2d(h, X, X_host));
   return certify_impl(h, X, params, result, witness_host, true);
 }
@@ -626,13 +623,10 @@ int dpgo_problem_certificate_apply(dpgo_problem_t h, const double* X_host, const
   if (!X_host || !V_host || !CV_host) return fail(DPGO_ERR_INVALID, "null pointer");
   if (h->has_G || h->C.nnzb > 0)
     return fail(DPGO_ERR_INVALID, "the certificate matrix is defined for a problem without a linear term G");
-  TmpDev tmp;
-  double *X, *V, *CV, *S, *part;
-  CHK(tmp.alloc(&X, h->vec_bytes()));
-  CHK(tmp.alloc(&V, h->vec_bytes()));
-  CHK(tmp.alloc(&CV, h->vec_bytes()));
-  CHK(tmp.alloc(&S, sizeof(double) * (size_t)h->n * h->d * h->d));
-  CHK(tmp.alloc(&part, sizeof(double) * (size_t)kPartialCap * 36));
+  DevBuf<double> X, V, CV, S, part;
+  for (DevBuf<double>* v : {&X, &V, &CV}) CHK(v->alloc((size_t)h->n * h->T));
+  CHK(S.alloc((size_t)h->n * h->d * h->d));
+  CHK(part.alloc((size_t)kPartialCap * 36));
   CHK(h2d(h, X, X_host));
   CHK(h2d(h, V, V_host));
   bool sym = false;
@@ -659,9 +653,8 @@ int dpgo_certify_escape_device(dpgo_problem_t h_next, int r, const double* X_dev
   CHK(check_ready(h_next));
   dpgo_problem_s* p = h_next;
   const int g = std::max(1, std::min(kMaxGrid, (int)(((size_t)p->n * (p->d + 1) + kBlock - 1) / kBlock)));
-  TmpDev tmp;
-  double* Xl = nullptr;
-  CHK(tmp.alloc(&Xl, p->vec_bytes()));
+  DevBuf<double> Xl;
+  CHK(Xl.alloc((size_t)p->n * p->T));
   auto lift = [&](double a) -> int {
     DISPATCH(p->d, r, hipLaunchKernelGGL((k_cert_lift<D, R>), dim3(g), dim3(kBlock), 0, p->stream, X_dev, witness_dev, a,
                                          Xl, p->n));

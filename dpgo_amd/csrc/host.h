@@ -99,23 +99,93 @@ inline bool supported(int d, int r) {
 inline bool aligned8(const void* q) { return ((uintptr_t)q & 7) == 0; }
 inline bool aligned16(const void* q) { return ((uintptr_t)q & 15) == 0; }
 
-struct Bsr {
-  int nrows = 0, ncols = 0, nnzb = 0;
-  int32_t* rowptr = nullptr;
-  int32_t* colidx = nullptr;
-  double* vals = nullptr;
-  BsrDev dev() const { return BsrDev{rowptr, colidx, vals}; }
-};
+// ---- the library's own device and pinned memory ----
+// Every buffer the library keeps is a DevBuf (hipMalloc) or a PinBuf (hipHostMalloc): move-only, released by the destructor,
+// so a struct that gains a buffer needs no second edit anywhere and an early return leaks nothing.  Assigning an empty value
+// releases (`S = SymQ()`); the conversion to T* lets code that only reads the pointer -- launch arguments, `p->dstate + 1`,
+// `if (!p->Q.vals)` -- look as it did with raw pointers.  These two types are the only callers of hipMalloc / hipFree /
+// hipHostMalloc / hipHostFree (dpgo_device_malloc / dpgo_device_free hand memory to the caller and are not counted).
+// g_live_*: what all of them hold at the moment (dpgo_debug_live_allocations).
+inline std::atomic<long long> g_live_buffers{0}, g_live_bytes{0};
 
-inline int free_bsr(Bsr& m) {
-  if (m.rowptr) HIPC(hipFree(m.rowptr));
-  if (m.colidx) HIPC(hipFree(m.colidx));
-  if (m.vals) HIPC(hipFree(m.vals));
-  m = Bsr();
+template <class T, bool kPinned>
+class OwnedBuf {
+ public:
+  OwnedBuf() = default;
+  OwnedBuf(OwnedBuf&& o) noexcept : p_(std::exchange(o.p_, nullptr)), bytes_(std::exchange(o.bytes_, 0)) {}
+  OwnedBuf& operator=(OwnedBuf&& o) noexcept {
+    if (this != &o) {
+      reset();
+      p_ = std::exchange(o.p_, nullptr);
+      bytes_ = std::exchange(o.bytes_, 0);
+    }
+    return *this;
+  }
+  ~OwnedBuf() { reset(); }
+  // `count` elements (flags: hipHostMalloc's, pinned memory only); what the buffer held before is released first
+  int alloc(size_t count, unsigned flags = hipHostMallocDefault) {
+    reset();
+    const size_t bytes = sizeof(T) * count;
+    if constexpr (kPinned)
+      HIPC(hipHostMalloc(&p_, bytes, flags));
+    else
+      HIPC(hipMalloc(&p_, bytes));
+    if (!p_) return DPGO_OK;  // (a request for zero bytes)
+    bytes_ = bytes;
+    g_live_buffers.fetch_add(1, std::memory_order_relaxed);
+    g_live_bytes.fetch_add((long long)bytes, std::memory_order_relaxed);
+    return DPGO_OK;
+  }
+  void reset() {
+    if (!p_) return;
+    if constexpr (kPinned)
+      (void)hipHostFree(p_);
+    else
+      (void)hipFree(p_);
+    g_live_buffers.fetch_sub(1, std::memory_order_relaxed);
+    g_live_bytes.fetch_sub((long long)bytes_, std::memory_order_relaxed);
+    p_ = nullptr;
+    bytes_ = 0;
+  }
+  T* get() const { return p_; }
+  operator T*() const { return p_; }
+  T* operator->() const { return p_; }
+
+ private:
+  T* p_ = nullptr;
+  size_t bytes_ = 0;
+};
+template <class T>
+using DevBuf = OwnedBuf<T, false>;
+template <class T>
+using PinBuf = OwnedBuf<T, true>;
+
+// at least one element (an empty edge list, an empty block row); copies `count` of them on `s`
+template <class T>
+inline int upload(DevBuf<T>& dst, const T* src, size_t count, hipStream_t s) {
+  CHK(dst.alloc(count > 0 ? count : 1));
+  if (count > 0) HIPC(hipMemcpyAsync(dst, src, sizeof(T) * count, hipMemcpyHostToDevice, s));
   return DPGO_OK;
 }
 
+// the handle's own stream: declared in front of the buffers, so destroyed after them
+struct OwnedStream {
+  hipStream_t s = nullptr;
+  OwnedStream() = default;
+  OwnedStream(const OwnedStream&) = delete;
+  OwnedStream& operator=(const OwnedStream&) = delete;
+  ~OwnedStream() {
+    if (s) (void)hipStreamDestroy(s);
+  }
+  operator hipStream_t() const { return s; }
+};
 
+struct Bsr {
+  int nrows = 0, ncols = 0, nnzb = 0;
+  DevBuf<int32_t> rowptr, colidx;
+  DevBuf<double> vals;
+  BsrDev dev() const { return BsrDev{rowptr, colidx, vals}; }
+};
 
 // Every tuning / A-B switch of the library in ONE place: read from the environment once (first use; dpgo_options_reload
 // reads again), printed by dpgo_describe_options / dpgo_problem_describe.  -1 (or 0 where noted) = not set: the size rules
@@ -198,48 +268,48 @@ using namespace dpgo_host;
 struct dpgo_problem_s {
   int r = 0, d = 0, n = 0, b = 0, T = 0;
   int device = 0;
-  hipStream_t own_stream = nullptr;
+  OwnedStream own_stream;  // (first: the buffers below are released before the stream is destroyed)
   hipStream_t stream = nullptr;
   Bsr Q;
   Bsr C;  // inter-agent coupling (rectangular), for G
-  double* G0 = nullptr;
-  double* G = nullptr;
+  DevBuf<double> G0, G;
   bool has_G = false;
-  double* dinv = nullptr;
+  DevBuf<double> dinv;
   double dinv_shift = -1.0;
   // work vectors
-  double *x1 = nullptr, *x2 = nullptr, *g1 = nullptr, *g2 = nullptr, *eta = nullptr, *delta = nullptr,
-         *Hd = nullptr, *rr = nullptr, *z = nullptr, *S1 = nullptr, *S2 = nullptr;
+  DevBuf<double> x1_buf, x2, g1, g2, eta, delta, Hd, rr, z, S1, S2;
+  // the iterate the kernels run on: x1_buf, or -- borrowed for the duration of a device solve -- the caller's buffer
+  double* x1 = nullptr;
   // multilevel (aggregation multigrid) preconditioner: levels[0] = the pose level ... levels.back() = the dense level
   struct MlLevel {
     int n = 0;      // nodes
     int k = 0;      // aggregate size towards the next level (0 on the dense level)
     int split = 1;  // lane groups per node of this level's SpMM-family kernels
     Bsr A;          // level >= 1: Galerkin operator (level 0: Q + shift I, never formed)
-    int32_t* slot_row = nullptr;  // level >= 1: block row of every slot of A
-    double *dinv = nullptr, *Pb = nullptr;            // smoother factors; prolongation blocks towards level + 1
-    double *r = nullptr, *x1 = nullptr, *x = nullptr;  // restricted residual, pre-smoothed iterate, corrected iterate
+    DevBuf<int32_t> slot_row;  // level >= 1: block row of every slot of A
+    DevBuf<double> dinv, Pb;  // smoother factors; prolongation blocks towards level + 1
+    DevBuf<double> r, x1, x;  // restricted residual, pre-smoothed iterate, corrected iterate
     // level 0 of a two-level hierarchy: AP = (Q + shift I) P (block rows = poses, block columns = level-1 nodes) and the
     // residual after pre-smoothing, so that the post-smoothing kernel gathers from the SMALL coarse vector:
     // r - A (x1 + P xc) = (r - A x1) - (A P) xc
     Bsr AP;
-    double* res1 = nullptr;
+    DevBuf<double> res1;
     // level 0 of a two-level hierarchy with GRAPH aggregates (ml_graph_aggregates): label of every pose, members of every
     // aggregate in discovery order, the spanning tree the prolongation is composed along, P_i^T res_i of every pose
     bool graph = false;
-    int32_t *lab = nullptr, *agg_ptr = nullptr, *agg_mem = nullptr, *parent = nullptr, *pslot = nullptr;
-    int32_t* mem_pos = nullptr;    // position of every pose in agg_mem (k_ml_build_P_tree_wave)
+    DevBuf<int32_t> lab, agg_ptr, agg_mem, parent, pslot;
+    DevBuf<int32_t> mem_pos;  // position of every pose in agg_mem (k_ml_build_P_tree_wave)
     // restriction of graph aggregates: inside the G consecutive poses a wave of k_ml_restrict owns, every RUN of poses with
     // the same aggregate is added up in the wave and leaves ONE partial sum; seg_info[i] = slot * 32 + length for the first
     // pose of a run (-1 otherwise), slots ordered by aggregate, seg_ptr[a] .. seg_ptr[a+1] = the partial sums of aggregate a
-    int32_t *seg_info = nullptr, *seg_ptr = nullptr;
+    DevBuf<int32_t> seg_info, seg_ptr;
     int nseg = 0;  // partial sums per restriction
-    int32_t* tile_perm = nullptr;  // aggregates of at most one persistent tile: pose of every (aggregate, slot), -1 = empty
+    DevBuf<int32_t> tile_perm;  // aggregates of at most one persistent tile: pose of every (aggregate, slot), -1 = empty
     int perm_tile = 0;             // slots per aggregate in tile_perm
     int merge_cap = 0;             // graph aggregates: fragments merged up to this many poses (0: plain greedy growth)
-    double* tbuf = nullptr;
-    float *Pb32 = nullptr, *AP32 = nullptr;  // fp32 copies of Pb and of A P's values (level 0, ml_operator_bits == 32)
-    float *x1f = nullptr, *res1f = nullptr;  // ... and the cycle-internal vectors of level 0 in that storage: the
+    DevBuf<double> tbuf;
+    DevBuf<float> Pb32, AP32;  // fp32 copies of Pb and of A P's values (level 0, ml_operator_bits == 32)
+    DevBuf<float> x1f, res1f;  // ... and the cycle-internal vectors of level 0 in that storage: the
                                              // pre-smoothed iterate (k_tcg_update -> k_ml_restrict), the kept residual
                                              // (k_ml_restrict -> k_ml_post_ap)
     AggMap agg() const { return AggMap{graph ? lab : nullptr, k}; }
@@ -266,18 +336,23 @@ struct dpgo_problem_s {
     std::vector<int32_t> lab, ptr, mem, parent, pslot;
   } add_agg;
   double ml_omega = 0.7, ml_shift = 1e-1;
-  double* ml_dense = nullptr;  // inverse of the coarsest operator, row-major, leading dimension ml_lda
-  float* ml_dense32 = nullptr;  // its fp32 storage (what the cycle streams when ml_coarse_bits == 32)
-  // lower block triangle of the (exactly symmetric) inverse, packed 64 x 64 tiles: what a two-level cycle streams in 64-bit
-  // mode (k_dense_sym_apply: half the bytes); chunk table, partial-sum buffers
-  double *ml_packed = nullptr, *ml_pd = nullptr, *ml_pt = nullptr;
-  DenseChunk* ml_chunks = nullptr;
-  int* ml_chunk_first = nullptr;
-  int ml_nchunks = 0;
+  // the dense level of the hierarchy: what lives and dies with it (ml_free assigns an empty one)
+  struct DenseLevel {
+    DevBuf<double> inv;   // inverse of the coarsest operator, row-major, leading dimension lda
+    DevBuf<float> inv32;  // its fp32 storage (what the cycle streams when ml_coarse_bits == 32)
+    // lower block triangle of the (exactly symmetric) inverse, packed 64 x 64 tiles: what a two-level cycle streams in 64-bit
+    // mode (k_dense_sym_apply: half the bytes); chunk table, partial-sum buffers
+    DevBuf<double> packed, pd, pt;
+    DevBuf<DenseChunk> chunks;
+    DevBuf<int> chunk_first;
+    int nchunks = 0;
+    int lda = 0;
+    DevBuf<double> W, Rx;  // Gauss-Jordan panels (setup only)
+  } dense;
   bool ml_use_dense_sym() const {
     const int env = options().ml_dense_sym;
-    if (!ml_use_ap() || ml_coarse_bits != 64 || !ml_packed || env == 0) return false;
-    return env == 1 || ml_lda >= 3072;  // below, the row-streaming kernel (one launch, cache-resident inverse) is as fast
+    if (!ml_use_ap() || ml_coarse_bits != 64 || !dense.packed || env == 0) return false;
+    return env == 1 || dense.lda >= 3072;  // below, the row-streaming kernel (one launch, cache-resident inverse) is as fast
   }
   int ml_coarse_bits = 64;  // 32: opt-in (dpgo_problem_multilevel_coarse_bits)
   // Storage precision of the OPERATOR COPIES the V-cycle streams on level 0 of an HBM-bound block (symmetric storage, two
@@ -301,8 +376,6 @@ struct dpgo_problem_s {
   bool coarse32_active() const {
     return ml_coarse_bits == 32 || (ml_vec32_active() && !ml_use_dense_sym() && options().ml_dense_bits == 32);
   }
-  int ml_lda = 0;
-  double *ml_W = nullptr, *ml_Rx = nullptr;  // Gauss-Jordan panels (setup only)
   // DPGO_PRECOND_AUTO: the multilevel cycle is currently selected.  Decided afresh at the first "auto" use after every
   // change of Q (a function of the problem only, so repeated runs reproduce): multilevel for a block without coupling
   // to other agents -- there the tCG budget, not the trust-region boundary, ends the local solves --, block-Jacobi
@@ -335,12 +408,11 @@ struct dpgo_problem_s {
   // symmetric copy of Q for the plain SpMM on Infinity-Cache-cold blocks (k_spmm_sym): upper blocks transposed + lower references
   struct SymQ {
     int nu = 0, nl = 0;
-    int32_t *urow = nullptr, *ucol = nullptr, *usrc = nullptr, *lrow = nullptr, *lcol = nullptr, *lslot = nullptr,
-            *lsrc = nullptr;
-    double* uvalsT = nullptr;
-    float* uvalsT32 = nullptr;  // fp32 copy of the values (the cycle's level-0 restriction, ml_operator_bits == 32)
-    int32_t* tord = nullptr;    // walk over the workgroup tiles (BsrSymDevT::tord; NULL: index order)
-    int* flag = nullptr;       // device: set by k_sym_check when a lower block is not the transpose of its upper one
+    DevBuf<int32_t> urow, ucol, usrc, lrow, lcol, lslot, lsrc;
+    DevBuf<double> uvalsT;
+    DevBuf<float> uvalsT32;  // fp32 copy of the values (the cycle's level-0 restriction, ml_operator_bits == 32)
+    DevBuf<int32_t> tord;  // walk over the workgroup tiles (BsrSymDevT::tord; NULL: index order)
+    DevBuf<int> flag;  // device: set by k_sym_check when a lower block is not the transpose of its upper one
     bool symbolic = false;     // pattern arrays belong to the current block pattern
     bool pattern_ok = false;   // the pattern is structurally symmetric
     bool ready = false;        // uvalsT holds the current values and they passed the symmetry check
@@ -387,39 +459,41 @@ struct dpgo_problem_s {
     bool launched = false;  // the one-launch solve is in flight (else: the solve already ran, `result` holds its outcome)
     dpgo_ropt_params resolved{};
     bool is_auto = false;
+    // borrowed, not owned: the handle's factors or none, the handle's x1, the caller's buffer
     const double* dinv = nullptr;
     double* own_x1 = nullptr;
     double* staged_x = nullptr;  // the caller's iterate when it is not 16-byte aligned (the solve runs on own_x1)
     std::chrono::steady_clock::time_point t0;
     dpgo_ropt_result result{};
   } pending;
-  PersistCtrl* pctrl = nullptr;
+  DevBuf<PersistCtrl> pctrl;
   bool pctrl_dirty = true;  // the control block has to be cleared in front of the next one-launch solve (creation, after a time-out)
-  unsigned long long* pgran = nullptr;  // granule table of the in-kernel all-reduce (kGranWords 8-byte words)
+  DevBuf<unsigned long long> pgran;  // granule table of the in-kernel all-reduce (kGranWords 8-byte words)
   unsigned gran_cleared_at = 0;         // value of `gen` when the table was last cleared
-  PersistCtrl* hctrl = nullptr;  // pinned
-  double* partials = nullptr;  // 5 regions of kPartialCap*kNP
-  DevState* dstate = nullptr;  // 2 slots
-  DevState* hstate = nullptr;  // pinned
-  unsigned long long* hflag = nullptr;  // pinned, host-coherent: device-published tCG progress word
+  PinBuf<PersistCtrl> hctrl;
+  DevBuf<double> partials;  // 5 regions of kPartialCap*kNP
+  DevBuf<DevState> dstate;  // 2 slots
+  PinBuf<DevState> hstate;
+  PinBuf<unsigned long long> hflag;  // host-coherent: host-coherent: device-published tCG progress word
   unsigned gen = 0;
   bool saw_rtr_stop = false;  // set from the progress word in just-in-time mode
-  // re-weightable edges (GNC)
-  int em = 0;
-  int32_t *e_p1 = nullptr, *e_p2 = nullptr, *c_ptr = nullptr, *c_edge = nullptr;
-  double *e_R = nullptr, *e_t = nullptr, *e_kappa = nullptr, *e_tau = nullptr, *e_w = nullptr, *e_rsq = nullptr,
-         *q_base = nullptr;
-  uint8_t *e_fixed = nullptr, *c_kind = nullptr, *e_role = nullptr;
-  int32_t* e_slot = nullptr;
-  // contributions of shared re-weightable edges to the coupling matrix C
-  int32_t *g_ptr = nullptr, *g_edge = nullptr;
-  uint8_t* g_kind = nullptr;
-  double* c_base = nullptr;
-  int n_shared_edges = 0;
-  int* e_counts = nullptr;
-  EdgeDev edges() const {
-    return EdgeDev{e_p1, e_p2, e_R, e_t, e_kappa, e_tau, e_fixed, e_role, e_slot, e_w, e_rsq, em};
-  }
+  // re-weightable edges (GNC): registered, replaced and dropped together (assigning an empty one releases them)
+  struct GncEdges {
+    int em = 0;
+    DevBuf<int32_t> e_p1, e_p2, c_ptr, c_edge;
+    DevBuf<double> e_R, e_t, e_kappa, e_tau, e_w, e_rsq, q_base;
+    DevBuf<uint8_t> e_fixed, c_kind, e_role;
+    DevBuf<int32_t> e_slot;
+    // contributions of shared re-weightable edges to the coupling matrix C
+    DevBuf<int32_t> g_ptr, g_edge;
+    DevBuf<uint8_t> g_kind;
+    DevBuf<double> c_base;
+    int n_shared_edges = 0;
+    DevBuf<int> e_counts;
+    EdgeDev dev() const {
+      return EdgeDev{e_p1, e_p2, e_R, e_t, e_kappa, e_tau, e_fixed, e_role, e_slot, e_w, e_rsq, em};
+    }
+  } gnc;
   int cur = 0;
   size_t vec_bytes() const { return (size_t)n * T * sizeof(double); }
   double* pE() const { return partials; }
@@ -499,13 +573,6 @@ struct Counters {
   int spmm = 0;
   bool vcycle_for_additive = false;  // an outer iteration of an "additive" solve ran the V-cycle instead
 };
-
-template <class Tp>
-inline int upload(Tp** dst, const Tp* src, size_t count, hipStream_t s) {
-  HIPC(hipMalloc(dst, sizeof(Tp) * (count > 0 ? count : 1)));
-  if (count > 0) HIPC(hipMemcpyAsync(*dst, src, sizeof(Tp) * count, hipMemcpyHostToDevice, s));
-  return DPGO_OK;
-}
 
 // Host worker threads of the set-up code (the hierarchy's symbolic set-up): created once per process and kept -- in a
 // process that has the HIP runtime and an ML framework loaded pthread_create costs 0.2-0.4 ms (static TLS of every loaded
@@ -621,25 +688,6 @@ struct JobGuard {
   ~JobGuard() { TaskPool::get().wait(job); }
 };
 
-struct TmpDev {
-  std::vector<void*> ptrs;
-  ~TmpDev() {
-    for (auto q : ptrs) (void)hipFree(q);
-  }
-  int alloc(double** out, size_t bytes) {
-    HIPC(hipMalloc(out, bytes));
-    ptrs.push_back(*out);
-    return DPGO_OK;
-  }
-};
-
-template <typename T>
-inline int sym_upload(T** dst, const std::vector<T>& v, hipStream_t stream) {
-  HIPC(hipMalloc(dst, sizeof(T) * std::max<size_t>(1, v.size())));
-  if (!v.empty()) HIPC(hipMemcpyAsync(*dst, v.data(), sizeof(T) * v.size(), hipMemcpyHostToDevice, stream));
-  return DPGO_OK;
-}
-
 struct PersistGeo {
   int split = 0, mt = 0, wgs = 0, slots = 0;
 };
@@ -655,6 +703,8 @@ int build_dinv(dpgo_problem_s* p, double shift);
 int poll_state(dpgo_problem_s* p);
 int push_state(dpgo_problem_s* p);
 void sym_free(dpgo_problem_s* p);
+int launch_spmm_view(dpgo_problem_s* p, const BsrDev& M, const double* V, const double* Gadd, double* OUT, int rows, int g,
+                     bool stream_nt = false);
 int sym_symbolic_setup(dpgo_problem_s* p);
 int sym_ensure(dpgo_problem_s* p, bool* usable);
 int launch_spmm_sym(dpgo_problem_s* p, const BsrSymDev& M, const double* V, const double* Gadd, double* OUT);
@@ -735,7 +785,6 @@ int tune_launch_caps(dpgo_problem_s* p);
 int tune_persist(dpgo_problem_s* p);
 
 // ---- agents.hip
-int free_edges(dpgo_problem_s* p);
 int rebuild_vals(dpgo_problem_s* p, int nnzb, const int32_t* cptr, const int32_t* cedge, const uint8_t* ckind,
                  const double* base, double sign, double* out);
 int rebuild_Q_from_weights(dpgo_problem_s* p, const double* base, double sign, double* out);

@@ -73,26 +73,8 @@ std::vector<int> ml_default_ks(int n, int b, int split0) {
 
 void ml_free(dpgo_problem_s* p) {
   p->ml_additive_layout = false;
-  for (auto& L : p->ml) {
-    free_bsr(L.A);
-    free_bsr(L.AP);
-    void* ptrs[] = {L.slot_row, L.dinv, L.Pb, L.r, L.x1, L.x, L.res1, L.lab, L.agg_ptr, L.agg_mem, L.parent, L.pslot, L.tbuf, L.tile_perm, L.mem_pos,
-                    L.seg_info, L.seg_ptr, L.Pb32, L.AP32, L.x1f, L.res1f};
-    for (void* q : ptrs)
-      if (q) (void)hipFree(q);
-  }
   p->ml.clear();
-  void* ptrs[] = {p->ml_dense, p->ml_W, p->ml_Rx, p->ml_dense32, p->ml_packed, p->ml_pd, p->ml_pt, p->ml_chunks,
-                  p->ml_chunk_first};
-  for (void* q : ptrs)
-    if (q) (void)hipFree(q);
-  p->ml_dense = p->ml_W = p->ml_Rx = nullptr;
-  p->ml_dense32 = nullptr;
-  p->ml_packed = p->ml_pd = p->ml_pt = nullptr;
-  p->ml_chunks = nullptr;
-  p->ml_chunk_first = nullptr;
-  p->ml_nchunks = 0;
-  p->ml_lda = 0;
+  p->dense = dpgo_problem_s::DenseLevel();
   p->ml_symbolic = p->ml_ready = false;
   p->ml_ops32_ready = false;
 }
@@ -475,7 +457,7 @@ int ml_symbolic_setup(dpgo_problem_s* p, const std::vector<int>& ks_in, int perm
   lap("previous hierarchy freed");
   if ((int)p->h_rowptr.size() != p->n + 1) return fail(DPGO_ERR_STATE, "multilevel: Q's block pattern is not set");
   const int b = p->b, bb = b * b;
-  const size_t tb = sizeof(double) * p->T;
+  const size_t nt = p->T;  // doubles per node
   std::vector<int32_t> rowptr = p->h_rowptr, colidx = p->h_colidx;
   int cur = p->n;
   // a single negative entry -S: two levels, graph aggregates of at most S poses; two negative entries: merged up to -ks[1]
@@ -499,17 +481,21 @@ int ml_symbolic_setup(dpgo_problem_s* p, const std::vector<int>& ks_in, int perm
       std::vector<int32_t> lab, ptr, mem, parent, pslot;
       int na;
       // the level-0 buffers whose sizes are known up front are allocated by a helper thread while the aggregates grow
-      hipError_t alloc_err = hipSuccess;
+      int alloc_rc = DPGO_OK;
+      std::string alloc_msg;  // (the helper's error text is thread-local to the helper)
       const int dev_ = p->device;
       const int nthreads = setup_threads();
       JobGuard alloc_job{TaskPool::get().submit(1, [&, dev_](int) {
-        hipError_t e = hipSetDevice(dev_);
-        if (e == hipSuccess) e = hipMalloc(&L.tbuf, tb * cur);
-        if (e == hipSuccess) e = hipMalloc(&L.res1, tb * cur);
-        if (e == hipSuccess) e = hipMalloc(&L.Pb, sizeof(double) * (size_t)cur * bb);
-        if (e == hipSuccess) e = hipMalloc(&L.x1, tb * cur);
-        if (e == hipSuccess) e = hipMalloc(&L.x, tb * cur);
-        alloc_err = e;
+        alloc_rc = [&]() -> int {
+          HIPC(hipSetDevice(dev_));
+          CHK(L.tbuf.alloc(nt * cur));
+          CHK(L.res1.alloc(nt * cur));
+          CHK(L.Pb.alloc((size_t)cur * bb));
+          CHK(L.x1.alloc(nt * cur));
+          CHK(L.x.alloc(nt * cur));
+          return DPGO_OK;
+        }();
+        if (alloc_rc != DPGO_OK) alloc_msg = g_err;
       }, nthreads)};
       if (p->add_plan_known && p->add_agg.S == L.k && p->add_agg.cap == merge_cap && (int)p->add_agg.lab.size() == cur) {
         const auto& A = p->add_agg;  // (the additive plan of this pattern was found with exactly these aggregates)
@@ -551,19 +537,19 @@ int ml_symbolic_setup(dpgo_problem_s* p, const std::vector<int>& ks_in, int perm
           std::sort(out.begin() + first, out.end());
         }, crow, ccol);
       }, nthreads)};
-      CHK(upload(&L.lab, lab.data(), lab.size(), p->stream));
-      CHK(upload(&L.agg_ptr, ptr.data(), ptr.size(), p->stream));
-      CHK(upload(&L.agg_mem, mem.data(), mem.size(), p->stream));
-      CHK(upload(&L.parent, parent.data(), parent.size(), p->stream));
-      CHK(upload(&L.pslot, pslot.data(), pslot.size(), p->stream));
+      CHK(upload(L.lab, lab.data(), lab.size(), p->stream));
+      CHK(upload(L.agg_ptr, ptr.data(), ptr.size(), p->stream));
+      CHK(upload(L.agg_mem, mem.data(), mem.size(), p->stream));
+      CHK(upload(L.parent, parent.data(), parent.size(), p->stream));
+      CHK(upload(L.pslot, pslot.data(), pslot.size(), p->stream));
       std::vector<int32_t> mpos(cur);
       for (int m = 0; m < cur; ++m) mpos[mem[m]] = m;
-      CHK(upload(&L.mem_pos, mpos.data(), mpos.size(), p->stream));
+      CHK(upload(L.mem_pos, mpos.data(), mpos.size(), p->stream));
       lap("labels, members, trees uploaded");
       std::vector<int32_t> seg_info, seg_ptr;
       L.nseg = ml_run_table(lab, cur, na, 64 / (b * L.split), seg_info, seg_ptr);
-      CHK(upload(&L.seg_info, seg_info.data(), seg_info.size(), p->stream));
-      CHK(upload(&L.seg_ptr, seg_ptr.data(), seg_ptr.size(), p->stream));
+      CHK(upload(L.seg_info, seg_info.data(), seg_info.size(), p->stream));
+      CHK(upload(L.seg_ptr, seg_ptr.data(), seg_ptr.size(), p->stream));
       std::vector<int32_t> tperm;
       // the layout of the additive preconditioner's persistent kernel: aggregate = workgroup tile of `perm_tile` slots
       if (!perm_tile && !merge_cap && L.k == additive_tile(p)) perm_tile = L.k;
@@ -572,7 +558,7 @@ int ml_symbolic_setup(dpgo_problem_s* p, const std::vector<int>& ks_in, int perm
         tperm.assign((size_t)na * perm_tile, -1);
         for (int a = 0; a < na; ++a)
           for (int m = ptr[a]; m < ptr[a + 1]; ++m) tperm[(size_t)a * perm_tile + (m - ptr[a])] = mem[m];
-        CHK(upload(&L.tile_perm, tperm.data(), tperm.size(), p->stream));
+        CHK(upload(L.tile_perm, tperm.data(), tperm.size(), p->stream));
         L.perm_tile = perm_tile;
       }
       lap("run table, tile table");
@@ -581,7 +567,7 @@ int ml_symbolic_setup(dpgo_problem_s* p, const std::vector<int>& ks_in, int perm
       CHK(upload_bsr(L.AP, cur, na, (int)acol.size(), b, arow.data(), acol.data(), nullptr, p->stream));
       lap("A P allocated, pattern uploaded");
       TaskPool::get().wait(alloc_job.job);
-      if (alloc_err != hipSuccess) return fail(DPGO_ERR_HIP, std::string("hipMalloc (level-0 buffers): ") + hipGetErrorString(alloc_err));
+      if (alloc_rc != DPGO_OK) return fail(alloc_rc, "level-0 buffers: " + alloc_msg);
       lap("level-0 vectors joined");
       HIPC(hipStreamSynchronize(p->stream));  // the host vectors go out of scope
       lap("stream synchronised");
@@ -600,10 +586,10 @@ int ml_symbolic_setup(dpgo_problem_s* p, const std::vector<int>& ks_in, int perm
       std::vector<int32_t> srow(colidx.size());
       for (int i = 0; i < cur; ++i)
         for (int t = rowptr[i]; t < rowptr[i + 1]; ++t) srow[t] = i;
-      CHK(upload(&L.slot_row, srow.data(), srow.size(), p->stream));
+      CHK(upload(L.slot_row, srow.data(), srow.size(), p->stream));
       HIPC(hipStreamSynchronize(p->stream));  // srow goes out of scope at the end of this block
-      HIPC(hipMalloc(&L.r, tb * cur));
-      if (!L.k) HIPC(hipMalloc(&L.x, tb * cur));  // dense level: its solution, read by the level above
+      CHK(L.r.alloc(nt * cur));
+      if (!L.k) CHK(L.x.alloc(nt * cur));  // dense level: its solution, read by the level above
     }
     if (l == 0 && L.k) {  // pattern of A P: the aggregates the block columns of every row fall into
       const int k = L.k;
@@ -617,13 +603,13 @@ int ml_symbolic_setup(dpgo_problem_s* p, const std::vector<int>& ks_in, int perm
         arow[i + 1] = (int32_t)acol.size();
       }
       CHK(upload_bsr(L.AP, cur, (cur + k - 1) / k, (int)acol.size(), b, arow.data(), acol.data(), nullptr, p->stream));
-      HIPC(hipMalloc(&L.res1, tb * cur));
+      CHK(L.res1.alloc(nt * cur));
     }
     if (L.k) {
-      if (l > 0) HIPC(hipMalloc(&L.dinv, sizeof(double) * (size_t)cur * bb));
-      HIPC(hipMalloc(&L.Pb, sizeof(double) * (size_t)cur * bb));
-      HIPC(hipMalloc(&L.x1, tb * cur));
-      HIPC(hipMalloc(&L.x, tb * cur));
+      if (l > 0) CHK(L.dinv.alloc((size_t)cur * bb));
+      CHK(L.Pb.alloc((size_t)cur * bb));
+      CHK(L.x1.alloc(nt * cur));
+      CHK(L.x.alloc(nt * cur));
       // pattern of the next level: block columns j / k of the rows of every aggregate
       const int k = L.k, nc = (cur + k - 1) / k;
       std::vector<int32_t> crow(nc + 1, 0), ccol;
@@ -649,12 +635,12 @@ int ml_symbolic_setup(dpgo_problem_s* p, const std::vector<int>& ks_in, int perm
   const int N = cur * b;
   if (N > 16384) return fail(DPGO_ERR_INVALID, "multilevel: dense coarsest operator too large (" + std::to_string(N) +
                                                    " unknowns): use more levels / larger aggregates");
-  p->ml_lda = ((N + kNB - 1) / kNB) * kNB;
+  p->dense.lda = ((N + kNB - 1) / kNB) * kNB;
   // + 8 rows: the apply kernel reads (and discards) the rows of a ghost node behind a ragged last node group
-  HIPC(hipMalloc(&p->ml_dense, sizeof(double) * (size_t)p->ml_lda * (p->ml_lda + 8)));
-  HIPC(hipMalloc(&p->ml_dense32, sizeof(float) * (size_t)p->ml_lda * (p->ml_lda + 8)));
+  CHK(p->dense.inv.alloc((size_t)p->dense.lda * (p->dense.lda + 8)));
+  CHK(p->dense.inv32.alloc((size_t)p->dense.lda * (p->dense.lda + 8)));
   if (p->ml.size() == 2) {  // two levels: the packed lower triangle and the bookkeeping of k_dense_sym_apply
-    const int nT = p->ml_lda / kNB;
+    const int nT = p->dense.lda / kNB;
     int chunk = kDenseChunk;
     if (options().dense_chunk > 0) chunk = options().dense_chunk;  // tuning knob
     std::vector<DenseChunk> chunks;
@@ -664,16 +650,16 @@ int ml_symbolic_setup(dpgo_problem_s* p, const std::vector<int>& ks_in, int perm
       for (int J0 = 0; J0 <= I; J0 += chunk) chunks.push_back(DenseChunk{I, J0, std::min(chunk, I + 1 - J0), 0});
     }
     first[nT] = (int)chunks.size();
-    p->ml_nchunks = (int)chunks.size();
-    CHK(upload(&p->ml_chunks, chunks.data(), chunks.size(), p->stream));
-    CHK(upload(&p->ml_chunk_first, first.data(), first.size(), p->stream));
-    HIPC(hipMalloc(&p->ml_packed, sizeof(double) * (size_t)nT * (nT + 1) / 2 * kNB * kNB));
-    HIPC(hipMalloc(&p->ml_pd, sizeof(double) * (size_t)p->ml_nchunks * kNB * p->r));
-    HIPC(hipMalloc(&p->ml_pt, sizeof(double) * (size_t)nT * p->ml_lda * p->r));
+    p->dense.nchunks = (int)chunks.size();
+    CHK(upload(p->dense.chunks, chunks.data(), chunks.size(), p->stream));
+    CHK(upload(p->dense.chunk_first, first.data(), first.size(), p->stream));
+    CHK(p->dense.packed.alloc((size_t)nT * (nT + 1) / 2 * kNB * kNB));
+    CHK(p->dense.pd.alloc((size_t)p->dense.nchunks * kNB * p->r));
+    CHK(p->dense.pt.alloc((size_t)nT * p->dense.lda * p->r));
     HIPC(hipStreamSynchronize(p->stream));  // the host vectors go out of scope
   }
-  HIPC(hipMalloc(&p->ml_W, sizeof(double) * (size_t)p->ml_lda * kNB));
-  HIPC(hipMalloc(&p->ml_Rx, sizeof(double) * (size_t)p->ml_lda * kNB));
+  CHK(p->dense.W.alloc((size_t)p->dense.lda * kNB));
+  CHK(p->dense.Rx.alloc((size_t)p->dense.lda * kNB));
   HIPC(hipStreamSynchronize(p->stream));
   lap("coarser levels, dense level allocated");
   if (timing)
@@ -749,16 +735,16 @@ int ml_numeric_setup_d(dpgo_problem_s* p) {
   }
   HIPC(hipGetLastError());
   auto& Lc = p->ml.back();
-  const int lda = p->ml_lda, N = Lc.n * p->b;
-  HIPC(hipMemsetAsync(p->ml_dense, 0, sizeof(double) * (size_t)lda * (lda + 8), p->stream));
-  hipLaunchKernelGGL(k_dense_pad_identity, dim3(1), dim3(kBlock), 0, p->stream, p->ml_dense, lda, N);
+  const int lda = p->dense.lda, N = Lc.n * p->b;
+  HIPC(hipMemsetAsync(p->dense.inv, 0, sizeof(double) * (size_t)lda * (lda + 8), p->stream));
+  hipLaunchKernelGGL(k_dense_pad_identity, dim3(1), dim3(kBlock), 0, p->stream, p->dense.inv, lda, N);
   hipLaunchKernelGGL(k_ml_dense_assemble<D>, dim3(flat_grid(Lc.A.nnzb)), dim3(kBlock), 0, p->stream, Lc.A.dev(),
-                     Lc.slot_row, p->ml_dense, lda, Lc.A.nnzb);
+                     Lc.slot_row, p->dense.inv, lda, Lc.A.nnzb);
   HIPC(hipGetLastError());
-  CHK(dense_spd_inverse(p->stream, p->ml_dense, lda, p->ml_W, p->ml_Rx, gj_use_mfma()));
-  if (p->ml_packed) {
+  CHK(dense_spd_inverse(p->stream, p->dense.inv, lda, p->dense.W, p->dense.Rx, gj_use_mfma()));
+  if (p->dense.packed) {
     const int nT = lda / kNB;
-    hipLaunchKernelGGL(k_dense_pack_lower, dim3(nT, nT), dim3(kBlock), 0, p->stream, p->ml_dense, lda, p->ml_packed);
+    hipLaunchKernelGGL(k_dense_pack_lower, dim3(nT, nT), dim3(kBlock), 0, p->stream, p->dense.inv, lda, p->dense.packed);
     HIPC(hipGetLastError());
   }
   {  // the fp32 storage of the inverse: what the cycle streams when the dense level is kept in fp32 -- by request
@@ -767,10 +753,10 @@ int ml_numeric_setup_d(dpgo_problem_s* p) {
      // array stays exact, the cycle applies its rounding)
     const size_t total = (size_t)lda * (lda + 8);
     if (p->ml_coarse_bits == 32)
-      hipLaunchKernelGGL(k_dense_round_f32, dim3(flat_grid(total)), dim3(kBlock), 0, p->stream, p->ml_dense, p->ml_dense32,
+      hipLaunchKernelGGL(k_dense_round_f32, dim3(flat_grid(total)), dim3(kBlock), 0, p->stream, p->dense.inv, p->dense.inv32,
                          total);
     else
-      hipLaunchKernelGGL(k_copy_f32, dim3(flat_grid(total)), dim3(kBlock), 0, p->stream, p->ml_dense, p->ml_dense32, total);
+      hipLaunchKernelGGL(k_copy_f32, dim3(flat_grid(total)), dim3(kBlock), 0, p->stream, p->dense.inv, p->dense.inv32, total);
     HIPC(hipGetLastError());
   }
   return DPGO_OK;
@@ -934,11 +920,11 @@ int ml_ops32_ensure(dpgo_problem_s* p) {
   auto& L0 = p->ml[0];
   const size_t bb = (size_t)p->b * p->b;
   const size_t nu = (size_t)p->sym.nu * bb, nap = (size_t)L0.AP.nnzb * bb, npb = (size_t)L0.n * bb;
-  if (!p->sym.uvalsT32) HIPC(hipMalloc(&p->sym.uvalsT32, sizeof(float) * nu));
-  if (!L0.AP32) HIPC(hipMalloc(&L0.AP32, sizeof(float) * nap));
-  if (!L0.Pb32) HIPC(hipMalloc(&L0.Pb32, sizeof(float) * npb));
-  if (!L0.x1f) HIPC(hipMalloc(&L0.x1f, sizeof(float) * (size_t)L0.n * p->T));
-  if (!L0.res1f) HIPC(hipMalloc(&L0.res1f, sizeof(float) * (size_t)L0.n * p->T));
+  if (!p->sym.uvalsT32) CHK(p->sym.uvalsT32.alloc(nu));
+  if (!L0.AP32) CHK(L0.AP32.alloc(nap));
+  if (!L0.Pb32) CHK(L0.Pb32.alloc(npb));
+  if (!L0.x1f) CHK(L0.x1f.alloc((size_t)L0.n * p->T));
+  if (!L0.res1f) CHK(L0.res1f.alloc((size_t)L0.n * p->T));
   auto copy = [&](const double* in, float* out, size_t total) {
     hipLaunchKernelGGL(k_copy_f32, dim3(flat_grid(total)), dim3(kBlock), 0, p->stream, in, out, total);
   };
@@ -974,23 +960,23 @@ int launch_coarse_prolong(dpgo_problem_s* p, const dpgo_problem_s::MlLevel& L, c
   int hint = p->beyond_cache();
   if (options().coarse_nt >= 0) hint = options().coarse_nt != 0;  // tuning knob
 #define COARSE_LAUNCH(NODES, MT, MPTR)                                                                               \
-  hipLaunchKernelGGL((k_ml_coarse_prolong<D, R, NODES, MT>), dim3(gc), dim3(kBlock), 0, p->stream, MPTR, p->ml_lda,   \
-                     reinterpret_cast<const MT*>(C.r), L.x1, L.Pb, L.k, L.x, gate, L.n, C.n, xc_out, hint)
+  hipLaunchKernelGGL((k_ml_coarse_prolong<D, R, NODES, MT>), dim3(gc), dim3(kBlock), 0, p->stream, MPTR, p->dense.lda,   \
+                     reinterpret_cast<const MT*>(C.r.get()), L.x1, L.Pb, L.k, L.x, gate, L.n, C.n, xc_out, hint)
   DISPATCH(p->d, p->r, {
     if (nodes == 4 && f32)
-      COARSE_LAUNCH(4, float, p->ml_dense32);
+      COARSE_LAUNCH(4, float, p->dense.inv32);
     else if (nodes == 4)
-      COARSE_LAUNCH(4, double, p->ml_dense);
+      COARSE_LAUNCH(4, double, p->dense.inv);
     else if (nodes == 3)
-      COARSE_LAUNCH(3, double, p->ml_dense);
+      COARSE_LAUNCH(3, double, p->dense.inv);
     else if (nodes == 2 && f32)
-      COARSE_LAUNCH(2, float, p->ml_dense32);
+      COARSE_LAUNCH(2, float, p->dense.inv32);
     else if (nodes == 2)
-      COARSE_LAUNCH(2, double, p->ml_dense);
+      COARSE_LAUNCH(2, double, p->dense.inv);
     else if (f32)
-      COARSE_LAUNCH(1, float, p->ml_dense32);
+      COARSE_LAUNCH(1, float, p->dense.inv32);
     else
-      COARSE_LAUNCH(1, double, p->ml_dense);
+      COARSE_LAUNCH(1, double, p->dense.inv);
   });
 #undef COARSE_LAUNCH
   HIPC(hipGetLastError());
@@ -999,14 +985,14 @@ int launch_coarse_prolong(dpgo_problem_s* p, const dpgo_problem_s::MlLevel& L, c
 
 // Dense level from the packed lower triangle: xc = A_c^-1 rc into C.x (two launches: partial products, fixed-order sums)
 int launch_dense_sym(dpgo_problem_s* p, const dpgo_problem_s::MlLevel& C, const DevState* gate) {
-  const int N = C.n * p->b, nT = p->ml_lda / kNB;
+  const int N = C.n * p->b, nT = p->dense.lda / kNB;
   switch (p->r) {
 #define DENSE_SYM_CASE(RR)                                                                                              \
   case RR:                                                                                                              \
-    hipLaunchKernelGGL((k_dense_sym_apply<RR>), dim3(p->ml_nchunks), dim3(kBlock), 0, p->stream, p->ml_packed,          \
-                       p->ml_chunks, C.r, N, p->ml_lda, p->ml_pd, p->ml_pt, gate);                                       \
-    hipLaunchKernelGGL((k_dense_sym_finish<RR>), dim3(nT, 4), dim3(kBlock), 0, p->stream, p->ml_pd, p->ml_pt,            \
-                       p->ml_chunk_first, nT, N, p->ml_lda, C.x, gate);                                                  \
+    hipLaunchKernelGGL((k_dense_sym_apply<RR>), dim3(p->dense.nchunks), dim3(kBlock), 0, p->stream, p->dense.packed,          \
+                       p->dense.chunks, C.r, N, p->dense.lda, p->dense.pd, p->dense.pt, gate);                                       \
+    hipLaunchKernelGGL((k_dense_sym_finish<RR>), dim3(nT, 4), dim3(kBlock), 0, p->stream, p->dense.pd, p->dense.pt,            \
+                       p->dense.chunk_first, nT, N, p->dense.lda, C.x, gate);                                                  \
     break;
     DENSE_SYM_CASE(2)
     DENSE_SYM_CASE(3)
@@ -1037,7 +1023,7 @@ int launch_ml_restrict0(dpgo_problem_s* p, const double* r, const DevState* gate
     stop.hflag = p->hflag;
     stop.gen = p->gen;
   }
-  float* rc32 = (C.k == 0 && p->coarse32_active()) ? reinterpret_cast<float*>(C.r) : (float*)nullptr;
+  float* rc32 = (C.k == 0 && p->coarse32_active()) ? reinterpret_cast<float*>(C.r.get()) : (float*)nullptr;
   double* res_out = p->ml_use_ap() ? L.res1 : nullptr;
   const double* dnext = C.k ? C.dinv : (const double*)nullptr;
   if (p->ml_vec32_active()) {  // ... its fp32 copy (and the prolongation's), the cycle's internal vectors in fp32 as well
@@ -1050,10 +1036,10 @@ int launch_ml_restrict0(dpgo_problem_s* p, const double* r, const DevState* gate
                                             p->ml_omega, C.x1, gate, L.n, res_out, L.tbuf, L.seg_info, stop));
   } else if (p->tcg_sym) {  // level 0 reads Q: the symmetric copy when the tCG-step kernel does
     DISPATCH(p->d, p->r, hipLaunchKernelGGL((k_ml_restrict<D, R, 1, BsrSymDev>), dim3(g0), dim3(kBlock), 0, p->stream,
-                                            p->sym.dev(), L.x1, r, L.Pb, p->ml_shift, L.k, C.r, rc32, dnext, p->ml_omega,
+                                            p->sym.dev(), L.x1.get(), r, L.Pb.get(), p->ml_shift, L.k, C.r, rc32, dnext, p->ml_omega,
                                             C.x1, gate, L.n, res_out, L.tbuf, L.seg_info, stop));
   } else {
-    DISPATCH(p->d, p->r, LAUNCH_SPLIT(p, k_ml_restrict, g0, p->Q.dev(), L.x1, r, L.Pb, p->ml_shift, L.k, C.r, rc32, dnext,
+    DISPATCH(p->d, p->r, LAUNCH_SPLIT(p, k_ml_restrict, g0, p->Q.dev(), L.x1.get(), r, L.Pb.get(), p->ml_shift, L.k, C.r, rc32, dnext,
                                       p->ml_omega, C.x1, gate, L.n, res_out, L.tbuf, L.seg_info, stop));
   }
   if (L.graph)
@@ -1080,7 +1066,7 @@ int launch_ml_post_ap(dpgo_problem_s* p, const double* Xdev, const double* r, do
     HIPC(hipGetLastError());
     return DPGO_OK;
   }
-  DISPATCH(p->d, p->r, LAUNCH_SPLIT(p, k_ml_post_ap, p->grid_post(), L0.AP.dev(), Xdev, r, L0.res1, p->ml[1].x, L0.Pb,
+  DISPATCH(p->d, p->r, LAUNCH_SPLIT(p, k_ml_post_ap, p->grid_post(), L0.AP.dev(), Xdev, r, L0.res1.get(), p->ml[1].x, L0.Pb.get(),
                                     L0.agg(), p->dinv, p->ml_omega, z, pout, gate, p->n));
   HIPC(hipGetLastError());
   return DPGO_OK;
@@ -1093,7 +1079,7 @@ int launch_ml_tail(dpgo_problem_s* p, const double* Xdev, const double* r, doubl
   const int nl = (int)p->ml.size();
   // the dense level reads its right-hand side in the precision its inverse is stored in (same buffer)
   auto rc32_of = [&](const dpgo_problem_s::MlLevel& C) {
-    return (C.k == 0 && p->coarse32_active()) ? reinterpret_cast<float*>(C.r) : (float*)nullptr;
+    return (C.k == 0 && p->coarse32_active()) ? reinterpret_cast<float*>(C.r.get()) : (float*)nullptr;
   };
   auto A_of = [&](int l) { return l == 0 ? p->Q.dev() : p->ml[l].A.dev(); };
   auto r_of = [&](int l) { return l == 0 ? r : (const double*)p->ml[l].r; };
@@ -1118,7 +1104,7 @@ int launch_ml_tail(dpgo_problem_s* p, const double* Xdev, const double* r, doubl
   for (int l = 1; l + 1 < nl; ++l) {  // down
     auto& L = p->ml[l];
     auto& C = p->ml[l + 1];
-    DISPATCH(p->d, p->r, ML_SPLIT_LAUNCH(L, k_ml_restrict, A_of(l), L.x1, r_of(l), L.Pb, 0.0, L.k, C.r, rc32_of(C),
+    DISPATCH(p->d, p->r, ML_SPLIT_LAUNCH(L, k_ml_restrict, A_of(l), L.x1.get(), r_of(l), L.Pb.get(), 0.0, L.k, C.r, rc32_of(C),
                                          C.k ? C.dinv : (const double*)nullptr, p->ml_omega, C.x1, gate, L.n,
                                          (double*)nullptr, (double*)nullptr, (const int32_t*)nullptr));
   }
@@ -1355,7 +1341,7 @@ int dpgo_problem_multilevel_get(dpgo_problem_t p, int level, int what, void* out
     case DPGO_ML_DENSE_INVERSE: {
       if (level + 1 != (int)p->ml.size()) return fail(DPGO_ERR_INVALID, "the dense inverse belongs to the last level");
       const int N = L.n * p->b;  // the N x N corner of the padded lda x lda array
-      HIPC(hipMemcpy2DAsync(out_host, sizeof(double) * N, p->ml_dense, sizeof(double) * p->ml_lda, sizeof(double) * N, N,
+      HIPC(hipMemcpy2DAsync(out_host, sizeof(double) * N, p->dense.inv, sizeof(double) * p->dense.lda, sizeof(double) * N, N,
                             hipMemcpyDeviceToHost, p->stream));
       HIPC(hipStreamSynchronize(p->stream));
       return DPGO_OK;
@@ -1378,11 +1364,10 @@ int dpgo_dense_spd_inverse(int N, const double* A_host, double* Ainv_host, int d
   if (device < 0 || device >= cnt) return fail(DPGO_ERR_INVALID, "device index out of range");
   HIPC(hipSetDevice(device));
   const int lda = ((N + kNB - 1) / kNB) * kNB;
-  TmpDev tmp;
-  double *M = nullptr, *W = nullptr, *Rx = nullptr;
-  CHK(tmp.alloc(&M, sizeof(double) * (size_t)lda * lda));
-  CHK(tmp.alloc(&W, sizeof(double) * (size_t)lda * kNB));
-  CHK(tmp.alloc(&Rx, sizeof(double) * (size_t)lda * kNB));
+  DevBuf<double> M, W, Rx;
+  CHK(M.alloc((size_t)lda * lda));
+  CHK(W.alloc((size_t)lda * kNB));
+  CHK(Rx.alloc((size_t)lda * kNB));
   HIPC(hipMemset(M, 0, sizeof(double) * (size_t)lda * lda));
   HIPC(hipMemcpy2D(M, sizeof(double) * lda, A_host, sizeof(double) * N, sizeof(double) * N, N, hipMemcpyHostToDevice));
   hipLaunchKernelGGL(k_dense_pad_identity, dim3(1), dim3(kBlock), 0, (hipStream_t) nullptr, M, lda, N);

@@ -10,13 +10,13 @@ int set_device(dpgo_problem_s* p) {
 
 int upload_bsr(Bsr& m, int nrows, int ncols, int nnzb, int b, const int32_t* rowptr, const int32_t* colidx,
                const double* vals, hipStream_t s) {
-  CHK(free_bsr(m));
+  m = Bsr();
   m.nrows = nrows;
   m.ncols = ncols;
   m.nnzb = nnzb;
-  HIPC(hipMalloc(&m.rowptr, sizeof(int32_t) * (nrows + 1)));
-  HIPC(hipMalloc(&m.colidx, sizeof(int32_t) * (nnzb > 0 ? nnzb : 1)));
-  HIPC(hipMalloc(&m.vals, sizeof(double) * (size_t)(nnzb > 0 ? nnzb : 1) * b * b));
+  CHK(m.rowptr.alloc(nrows + 1));
+  CHK(m.colidx.alloc(nnzb > 0 ? nnzb : 1));
+  CHK(m.vals.alloc((size_t)(nnzb > 0 ? nnzb : 1) * b * b));
   HIPC(hipMemcpyAsync(m.rowptr, rowptr, sizeof(int32_t) * (nrows + 1), hipMemcpyHostToDevice, s));
   if (nnzb > 0) {
     HIPC(hipMemcpyAsync(m.colidx, colidx, sizeof(int32_t) * nnzb, hipMemcpyHostToDevice, s));
@@ -72,11 +72,7 @@ int push_state(dpgo_problem_s* p) {
 
 // ---- symmetric copy of Q (plain SpMM on cold blocks) ----
 void sym_free(dpgo_problem_s* p) {
-  auto& S = p->sym;
-  void* ptrs[] = {S.urow, S.ucol, S.usrc, S.lrow, S.lcol, S.lslot, S.lsrc, S.uvalsT, S.flag, S.uvalsT32, S.tord};
-  for (void* q : ptrs)
-    if (q) (void)hipFree(q);
-  S = dpgo_problem_s::SymQ();
+  p->sym = dpgo_problem_s::SymQ();
   p->tcg_sym = false;
 }
 
@@ -118,15 +114,15 @@ int sym_symbolic_setup(dpgo_problem_s* p) {
   if (2 * lcol.size() + (size_t)n != ci.size()) return DPGO_OK;  // an upper block without its lower one
   S.nu = (int)ucol.size();
   S.nl = (int)lcol.size();
-  CHK(sym_upload(&S.urow, urow, p->stream));
-  CHK(sym_upload(&S.ucol, ucol, p->stream));
-  CHK(sym_upload(&S.usrc, usrc, p->stream));
-  CHK(sym_upload(&S.lrow, lrow, p->stream));
-  CHK(sym_upload(&S.lcol, lcol, p->stream));
-  CHK(sym_upload(&S.lslot, lslot, p->stream));
-  CHK(sym_upload(&S.lsrc, lsrc, p->stream));
-  HIPC(hipMalloc(&S.uvalsT, sizeof(double) * (size_t)std::max(1, S.nu) * p->b * p->b));
-  HIPC(hipMalloc(&S.flag, sizeof(int)));
+  CHK(upload(S.urow, urow.data(), urow.size(), p->stream));
+  CHK(upload(S.ucol, ucol.data(), ucol.size(), p->stream));
+  CHK(upload(S.usrc, usrc.data(), usrc.size(), p->stream));
+  CHK(upload(S.lrow, lrow.data(), lrow.size(), p->stream));
+  CHK(upload(S.lcol, lcol.data(), lcol.size(), p->stream));
+  CHK(upload(S.lslot, lslot.data(), lslot.size(), p->stream));
+  CHK(upload(S.lsrc, lsrc.data(), lsrc.size(), p->stream));
+  CHK(S.uvalsT.alloc((size_t)std::max(1, S.nu) * p->b * p->b));
+  CHK(S.flag.alloc(1));
   if (options().tile_walk != 0) {
     // The walk over the workgroup tiles of the symmetric-storage kernels (BsrSymDevT::tord).  tile_iter gives XCD x the
     // contiguous eighth [T x / 8, T (x + 1) / 8) of the T tiles and its workgroups walk it with a stride of their count, so
@@ -171,7 +167,7 @@ int sym_symbolic_setup(dpgo_problem_s* p) {
         }
       }
       if ((int)order.size() == T) {
-        CHK(sym_upload(&S.tord, order, p->stream));
+        CHK(upload(S.tord, order.data(), order.size(), p->stream));
         HIPC(hipStreamSynchronize(p->stream));  // (`order` goes out of scope)
       }
     }
@@ -226,6 +222,19 @@ int launch_spmm_sym(dpgo_problem_s* p, const BsrSymDev& M, const double* V, cons
   return DPGO_OK;
 }
 
+// the plain kernel on a view of a matrix: the tail of launch_spmm, and the rotating probe's private copies of Q
+int launch_spmm_view(dpgo_problem_s* p, const BsrDev& M, const double* V, const double* Gadd, double* OUT, int rows, int g,
+                     bool stream_nt) {
+  DISPATCH(p->d, p->r, {
+    if (stream_nt)
+      hipLaunchKernelGGL((k_spmm<D, R, 1, 1>), dim3(g), dim3(kBlock), 0, p->stream, M, V, Gadd, OUT, rows);
+    else
+      LAUNCH_SPLIT(p, k_spmm, g, M, V, Gadd, OUT, rows);
+  });
+  HIPC(hipGetLastError());
+  return DPGO_OK;
+}
+
 int launch_spmm(dpgo_problem_s* p, const Bsr& M, const double* V, const double* Gadd, double* OUT, int nrows, bool plain_only) {
   if (&M == &p->Q && nrows < 0 && !plain_only && p->sym_wanted()) {
     bool usable = false;
@@ -238,14 +247,7 @@ int launch_spmm(dpgo_problem_s* p, const Bsr& M, const double* V, const double* 
     const int P = (64 / (p->b * p->split)) * kWaves;
     g = std::max(1, std::min(kMaxGrid, (rows + P - 1) / P));
   }
-  DISPATCH(p->d, p->r, {
-    if (p->want_stream_nt() && p->split == 1 && &M == &p->Q)
-      hipLaunchKernelGGL((k_spmm<D, R, 1, 1>), dim3(g), dim3(kBlock), 0, p->stream, M.dev(), V, Gadd, OUT, rows);
-    else
-      LAUNCH_SPLIT(p, k_spmm, g, M.dev(), V, Gadd, OUT, rows);
-  });
-  HIPC(hipGetLastError());
-  return DPGO_OK;
+  return launch_spmm_view(p, M.dev(), V, Gadd, OUT, rows, g, p->want_stream_nt() && p->split == 1 && &M == &p->Q);
 }
 
 bool outer_sym_enabled() {  // tuning knob: DPGO_OUTER_SYM=0 keeps the outer iteration on the plain copy of Q
@@ -405,28 +407,29 @@ int dpgo_problem_create(dpgo_problem_t* out, int r, int d, int n, int device) {
   int rc = [&]() -> int {
     HIPC(hipSetDevice(device));
     CHK(tune_launch_caps(p));
-    HIPC(hipStreamCreateWithFlags(&p->own_stream, hipStreamNonBlocking));
+    HIPC(hipStreamCreateWithFlags(&p->own_stream.s, hipStreamNonBlocking));
     p->stream = p->own_stream;
     const size_t vb = p->vec_bytes();
-    double** vecs[] = {&p->x1, &p->x2, &p->g1, &p->g2, &p->eta, &p->delta, &p->Hd, &p->rr, &p->z, &p->G, &p->G0};
+    DevBuf<double>* vecs[] = {&p->x1_buf, &p->x2, &p->g1, &p->g2, &p->eta, &p->delta, &p->Hd, &p->rr, &p->z, &p->G, &p->G0};
     for (auto v : vecs) {
-      HIPC(hipMalloc(v, vb));
+      CHK(v->alloc((size_t)n * p->T));
       HIPC(hipMemsetAsync(*v, 0, vb, p->stream));
     }
-    HIPC(hipMalloc(&p->S1, sizeof(double) * (size_t)n * d * d));
-    HIPC(hipMalloc(&p->S2, sizeof(double) * (size_t)n * d * d));
-    HIPC(hipMalloc(&p->dinv, sizeof(double) * (size_t)n * p->b * p->b));
-    HIPC(hipMalloc(&p->partials, sizeof(double) * 5 * kPartialCap * kNP));
+    p->x1 = p->x1_buf;
+    CHK(p->S1.alloc((size_t)n * d * d));
+    CHK(p->S2.alloc((size_t)n * d * d));
+    CHK(p->dinv.alloc((size_t)n * p->b * p->b));
+    CHK(p->partials.alloc(5 * kPartialCap * kNP));
     HIPC(hipMemsetAsync(p->partials, 0, sizeof(double) * 5 * kPartialCap * kNP, p->stream));
-    HIPC(hipMalloc(&p->dstate, sizeof(DevState) * 2));
+    CHK(p->dstate.alloc(2));
     // (host-coherent, device-visible: the one-launch solve's commit kernel writes its report straight into them)
-    HIPC(hipHostMalloc(&p->hstate, sizeof(DevState), hipHostMallocCoherent | hipHostMallocMapped));
-    HIPC(hipMalloc(&p->pctrl, sizeof(PersistCtrl)));
-    HIPC(hipMalloc(&p->pgran, sizeof(unsigned long long) * kGranWords));
+    CHK(p->hstate.alloc(1, hipHostMallocCoherent | hipHostMallocMapped));
+    CHK(p->pctrl.alloc(1));
+    CHK(p->pgran.alloc(kGranWords));
     HIPC(hipMemsetAsync(p->pgran, 0, sizeof(unsigned long long) * kGranWords, p->stream));
-    HIPC(hipHostMalloc(&p->hctrl, sizeof(PersistCtrl), hipHostMallocCoherent | hipHostMallocMapped));
+    CHK(p->hctrl.alloc(1, hipHostMallocCoherent | hipHostMallocMapped));
     CHK(tune_persist(p));
-    HIPC(hipHostMalloc(&p->hflag, 64, hipHostMallocCoherent | hipHostMallocMapped));
+    CHK(p->hflag.alloc(8, hipHostMallocCoherent | hipHostMallocMapped));  // (64 bytes)
     *p->hflag = 0ull;
     HIPC(hipStreamSynchronize(p->stream));
     return DPGO_OK;
@@ -484,23 +487,7 @@ int dpgo_problem_destroy(dpgo_problem_t p) {
   if (!p) return DPGO_OK;
   (void)hipSetDevice(p->device);
   if (p->own_stream) (void)hipStreamSynchronize(p->own_stream);
-  free_bsr(p->Q);
-  free_bsr(p->C);
-  ml_free(p);
-  sym_free(p);
-  free_edges(p);
-  double* vecs[] = {p->x1, p->x2, p->g1, p->g2, p->eta, p->delta, p->Hd, p->rr, p->z, p->G, p->G0,
-                    p->S1, p->S2, p->dinv, p->partials};
-  for (auto v : vecs)
-    if (v) (void)hipFree(v);
-  if (p->dstate) (void)hipFree(p->dstate);
-  if (p->hstate) (void)hipHostFree(p->hstate);
-  if (p->hflag) (void)hipHostFree(p->hflag);
-  if (p->pctrl) (void)hipFree(p->pctrl);
-  if (p->pgran) (void)hipFree(p->pgran);
-  if (p->hctrl) (void)hipHostFree(p->hctrl);
-  if (p->own_stream) (void)hipStreamDestroy(p->own_stream);
-  delete p;
+  delete p;  // (every buffer, then the stream: the members' destructors)
   return DPGO_OK;
 }
 
@@ -540,7 +527,7 @@ int dpgo_problem_set_Q_bsr(dpgo_problem_t p, int nnzb, const int32_t* rowptr, co
   CHK(validate_bsr(p->n, p->n, nnzb, rowptr, colidx, true));
   CHK(set_device(p));
   // registered re-weightable edges index into the old pattern: drop them (the caller re-registers)
-  if (p->e_w) CHK(free_edges(p));
+  if (p->gnc.e_w) p->gnc = dpgo_problem_s::GncEdges();
   CHK(upload_bsr(p->Q, p->n, p->n, nnzb, p->b, rowptr, colidx, vals, p->stream));
   const bool same_pattern = (int)p->h_rowptr.size() == p->n + 1 && (int)p->h_colidx.size() == nnzb &&
                             std::equal(rowptr, rowptr + p->n + 1, p->h_rowptr.begin()) &&
@@ -615,7 +602,7 @@ int dpgo_problem_update_Q_values(dpgo_problem_t p, const double* vals) {
                       p->stream));
   // registered re-weightable edges: the constant part of Q is whatever the new values hold beyond the listed
   // edges' contributions at the current weights
-  if (p->e_w) CHK(rebuild_Q_from_weights(p, p->Q.vals, -1.0, p->q_base));
+  if (p->gnc.e_w) CHK(rebuild_Q_from_weights(p, p->Q.vals, -1.0, p->gnc.q_base));
   const double s = p->dinv_shift > 0 ? p->dinv_shift : 1e-1;
   p->dinv_shift = -1.0;  // PoseGraph::clearQuadraticMatrix also drops the preconditioner (src/PoseGraph.cpp:352-355)
   p->ml_ready = false;
@@ -672,7 +659,7 @@ int dpgo_problem_set_G_coupling(dpgo_problem_t p, int ncols, int nnzb, const int
   CHK(validate_bsr(p->n, ncols, nnzb, rowptr, colidx, false));
   CHK(set_device(p));
   // shared re-weightable edges index into the old coupling pattern: drop them (the caller re-registers)
-  if (p->n_shared_edges > 0) CHK(free_edges(p));
+  if (p->gnc.n_shared_edges > 0) p->gnc = dpgo_problem_s::GncEdges();
   CHK(upload_bsr(p->C, p->n, ncols, nnzb, p->b, rowptr, colidx, vals, p->stream));
   if (G0_host) {
     CHK(h2d(p, p->G0, G0_host));
@@ -845,6 +832,15 @@ int dpgo_device_malloc(void** out, size_t bytes, int device) {
   if (device < 0 || device >= cnt) return fail(DPGO_ERR_INVALID, "device index out of range");
   HIPC(hipSetDevice(device));
   HIPC(hipMalloc(out, bytes > 0 ? bytes : 1));
+  return DPGO_OK;
+}
+
+
+// what the library's own buffers (DevBuf / PinBuf) hold at the moment, device and pinned together
+int dpgo_debug_live_allocations(long long* buffers, long long* bytes) {
+  if (!buffers || !bytes) return fail(DPGO_ERR_INVALID, "null out");
+  *buffers = g_live_buffers.load();
+  *bytes = g_live_bytes.load();
   return DPGO_OK;
 }
 

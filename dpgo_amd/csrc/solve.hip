@@ -264,7 +264,7 @@ int launch_rtr_persistent(dpgo_problem_s* p, const dpgo_ropt_params* prm, const 
   if (additive) {
     auto& L0 = p->ml[0];
     auto& C = p->ml[1];
-    add = AddDev{L0.Pb, p->ml_dense, p->ml_lda, C.n, C.r, 1.0, L0.graph ? L0.tile_perm : nullptr,
+    add = AddDev{L0.Pb, p->dense.inv, p->dense.lda, C.n, C.r, 1.0, L0.graph ? L0.tile_perm : nullptr,
                  L0.graph ? L0.lab : nullptr, L0.graph ? L0.mem_pos : nullptr, L0.graph ? L0.agg_ptr : nullptr};
     lds = sizeof(double) * (size_t)p->b * C.n * p->b;  // (d+1) rows of the inverse
   }
@@ -380,7 +380,7 @@ int rtr_outer_iteration(dpgo_problem_s* p, const dpgo_ropt_params* prm, const do
     int enq = 0, last_j = -1;
     auto t_progress = std::chrono::steady_clock::now();
     while (true) {
-      const unsigned long long w = __atomic_load_n(p->hflag, __ATOMIC_ACQUIRE);
+      const unsigned long long w = __atomic_load_n(p->hflag.get(), __ATOMIC_ACQUIRE);
       int dev_j = 0;
       if ((unsigned)(w >> 32) == p->gen) {
         dev_j = (int)((w >> 8) & 0xFFFFFFu);
@@ -577,7 +577,7 @@ int run_optimize(dpgo_problem_s* p, const dpgo_ropt_params* prm, dpgo_ropt_resul
   if (!resume) {
     p->loop_extra_bytes = 0;
     if (prm->precond == DPGO_PRECOND_MULTILEVEL && !p->ml.empty()) {
-      const size_t nd = (size_t)p->ml_lda;
+      const size_t nd = (size_t)p->dense.lda;
       size_t bytes = nd * nd * (size_t)(p->ml_coarse_bits / 8) / (p->ml_use_dense_sym() ? 2 : 1);
       const auto& L0 = p->ml[0];
       bytes += (size_t)L0.AP.nnzb * (sizeof(double) * p->b * p->b + sizeof(int32_t)) + sizeof(double) * (size_t)p->n * p->b * p->b;

@@ -175,6 +175,7 @@ SIGNATURES = {
     "dpgo_build_G_coupling": ([_I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P,
                                C.POINTER(_I), _P, _P, _P], _I),
     "dpgo_debug_reduction_primitives": ([_I, _I, _I, _P, _P, _P, _P, _P], _I),
+    "dpgo_debug_live_allocations": ([C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)], _I),
     "dpgo_certify_params_default": ([C.POINTER(CertifyParamsC)], None),
     "dpgo_problem_certify": ([_P, _P, C.POINTER(CertifyParamsC), C.POINTER(CertifyResultC), _P], _I),
     "dpgo_problem_certify_device": ([_P, _P, C.POINTER(CertifyParamsC), C.POINTER(CertifyResultC), _P], _I),

@@ -469,6 +469,12 @@ int dpgo_bench_iteration_kernels(dpgo_problem_t h, int reps, int warmup, double 
 int dpgo_debug_reduction_primitives(int workgroups, int pay, int steps, const double* in_dev, const double* pay_in_dev,
                                     double* sums_dev, double* pay_out_dev, double* rows_out_dev);
 
+/* Test probe: the device and pinned buffers the library itself holds at the moment, in this process, over all handles,
+ * exchange plans and calls in flight -- their number and their bytes.  Memory handed out by dpgo_device_malloc is the
+ * caller's and is not counted.  After the last handle and plan are destroyed both return to what they were before the
+ * first was created. */
+int dpgo_debug_live_allocations(long long* buffers, long long* bytes);
+
 /* One-launch solve (kernels/persist.h, k_rtr_persist): for blocks in the latency regime (every block the kernel can hold:
  * <= 32 768 poses in 3-D; environment DPGO_PERSIST_MAX_POSES lowers the limit) with the block-Jacobi, additive or no
  * preconditioner, dpgo_optimize* runs the WHOLE local solve -- initial statistics, every RTR iteration's tCG_TR loop,

@@ -63,6 +63,22 @@ def test_no_cpu_fallback_without_device():
     assert L.load().dpgo_dense_spd_inverse(3, L.ptr(A), L.ptr(A.copy()), 0, 1) == L.ERR_HIP
 
 
+def test_failed_create_without_device_leaves_no_allocation():
+    """dpgo_debug_live_allocations counts the device and pinned buffers the library itself holds.  Without a HIP device
+    dpgo_problem_create fails with DPGO_ERR_HIP before it allocates, and the count is (0, 0) buffers / bytes."""
+    import dpgo_amd
+    import dpgo_amd.lib as L
+    if dpgo_amd.device_count() > 0:
+        pytest.skip("a GPU is present (tests/test_device_memory_gpu.py checks the count there)")
+    lib = L.load()
+    h = L._P()
+    assert lib.dpgo_problem_create(C.byref(h), 5, 3, 10, 0) == L.ERR_HIP and not h.value
+    buffers, nbytes = C.c_longlong(-1), C.c_longlong(-1)
+    assert lib.dpgo_debug_live_allocations(C.byref(buffers), C.byref(nbytes)) == L.OK
+    assert (buffers.value, nbytes.value) == (0, 0)
+    assert lib.dpgo_debug_live_allocations(None, C.byref(nbytes)) == L.ERR_INVALID
+
+
 def test_invalid_arguments_are_reported_not_aborted():
     """Reference: glog CHECK aborts (src/PoseGraph.cpp:19, QuadraticProblem.cpp:30-31); C ABI: codes."""
     import dpgo_amd
