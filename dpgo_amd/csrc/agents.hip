@@ -8,11 +8,9 @@ int rebuild_vals(dpgo_problem_s* p, int nnzb, const int32_t* cptr, const int32_t
   if (nnzb <= 0) return DPGO_OK;
   const int g = std::max(1, std::min(kMaxGrid, (nnzb + kBlock - 1) / kBlock));
   if (p->d == 2)
-    hipLaunchKernelGGL(k_rebuild_Q<2>, dim3(g), dim3(kBlock), 0, p->stream, p->gnc.dev(), cptr, cedge, ckind, base,
-                       sign, out, nnzb);
+    launch(k_rebuild_Q<2>, g, 0, p->stream, p->gnc.dev(), cptr, cedge, ckind, base, sign, out, nnzb);
   else
-    hipLaunchKernelGGL(k_rebuild_Q<3>, dim3(g), dim3(kBlock), 0, p->stream, p->gnc.dev(), cptr, cedge, ckind, base,
-                       sign, out, nnzb);
+    launch(k_rebuild_Q<3>, g, 0, p->stream, p->gnc.dev(), cptr, cedge, ckind, base, sign, out, nnzb);
   HIPC(hipGetLastError());
   return DPGO_OK;
 }
@@ -167,8 +165,10 @@ int dpgo_problem_gnc_reweight_device(dpgo_problem_t p, const double* X_dev, cons
   if (update && !(mu > 0.0)) return fail(DPGO_ERR_INVALID, "GNC mu must be positive");
   HIPC(hipMemsetAsync(p->gnc.e_counts, 0, sizeof(int) * 4, p->stream));
   const int g = std::max(1, std::min(kMaxGrid, (p->gnc.em + kBlock - 1) / kBlock));
-  DISPATCH(p->d, p->r, hipLaunchKernelGGL((k_edge_weights<D, R>), dim3(g), dim3(kBlock), 0, p->stream, p->gnc.dev(), X_dev,
-                                          nbr_tiles_dev, mu, barc, w_tol, update, p->gnc.e_counts));
+  CHK(dispatch_dr(p->d, p->r, [&](auto D, auto R) {
+    return launch(k_edge_weights<D, R>, g, 0, p->stream, p->gnc.dev(), X_dev, nbr_tiles_dev, mu, barc, w_tol, update,
+                  p->gnc.e_counts);
+  }));
   HIPC(hipGetLastError());
   if (update) CHK(refresh_after_weights(p));
   int h[4] = {0, 0, 0, 0};
@@ -235,7 +235,7 @@ struct InitBufs {
   DevBuf<double> x, r, z, p, Ap, diag, partial;
 };
 int init_dot(dpgo_problem_s* h, const double* a, const double* b, InitBufs& w, size_t total, int g, double* out) {
-  hipLaunchKernelGGL(k_init_dot, dim3(g), dim3(kBlock), 0, h->stream, a, b, w.partial, total);
+  launch(k_init_dot, g, 0, h->stream, a, b, w.partial, total);
   HIPC(hipGetLastError());
   std::vector<double> host(g);
   HIPC(hipMemcpyAsync(host.data(), w.partial, sizeof(double) * g, hipMemcpyDeviceToHost, h->stream));
@@ -250,7 +250,7 @@ int init_pcg(dpgo_problem_s* h, InitBufs& w, const double* rhs, int mode, double
   const size_t total = (size_t)h->n * T;
   const int g = std::max(1, std::min(kMaxGrid, (int)((total + kBlock - 1) / kBlock)));
   auto axpby = [&](double a, const double* x, double b, double* y) -> int {
-    hipLaunchKernelGGL(k_init_axpby, dim3(g), dim3(kBlock), 0, h->stream, a, x, b, y, total, T, R, D, mode);
+    launch(k_init_axpby, g, 0, h->stream, a, x, b, y, total, T, R, D, mode);
     HIPC(hipGetLastError());
     return DPGO_OK;
   };
@@ -259,7 +259,7 @@ int init_pcg(dpgo_problem_s* h, InitBufs& w, const double* rhs, int mode, double
     return axpby(1.0, out, 0.0, out);
   };
   auto precond = [&](const double* r, double* z) -> int {
-    hipLaunchKernelGGL(k_init_jacobi, dim3(g), dim3(kBlock), 0, h->stream, r, w.diag, z, total, T, R, D, mode);
+    launch(k_init_jacobi, g, 0, h->stream, r, w.diag, z, total, T, R, D, mode);
     HIPC(hipGetLastError());
     return DPGO_OK;
   };
@@ -348,16 +348,16 @@ int dpgo_chordal_initialization(int d, int n, int m, const int32_t* p1, const in
   HIPC(hipMemcpyAsync(V, e0.data(), sizeof(double) * hr->T, hipMemcpyHostToDevice, hr->stream));
   HIPC(hipStreamSynchronize(hr->stream));
   CHK(launch_spmm(hr, hr->Q, V, nullptr, rhs));
-  hipLaunchKernelGGL(k_init_axpby, dim3(gtot), dim3(kBlock), 0, hr->stream, -1.0, rhs, 0.0, rhs, total, hr->T, r, d, 0);
+  launch(k_init_axpby, gtot, 0, hr->stream, -1.0, rhs, 0.0, rhs, total, hr->T, r, d, 0);
   if (d == 2)
-    hipLaunchKernelGGL(k_init_diag<2>, dim3(gflat), dim3(kBlock), 0, hr->stream, hr->Q.dev(), w.diag, n);
+    launch(k_init_diag<2>, gflat, 0, hr->stream, hr->Q.dev(), w.diag, n);
   else
-    hipLaunchKernelGGL(k_init_diag<3>, dim3(gflat), dim3(kBlock), 0, hr->stream, hr->Q.dev(), w.diag, n);
+    launch(k_init_diag<3>, gflat, 0, hr->stream, hr->Q.dev(), w.diag, n);
   HIPC(hipGetLastError());
   CHK(init_pcg(hr, w, rhs, 0, tol, max_iter, &it_rot));
   // V = E0 + x, then every block to SO(d) (projectToRotationGroup, src/DPGO_utils.cpp:464-478): the rounding kernel with
   // the identity as anchor
-  hipLaunchKernelGGL(k_init_axpby, dim3(gtot), dim3(kBlock), 0, hr->stream, 1.0, w.x, 0.0, w.x, total, hr->T, r, d, 0);
+  launch(k_init_axpby, gtot, 0, hr->stream, 1.0, w.x, 0.0, w.x, total, hr->T, r, d, 0);
   HIPC(hipMemcpyAsync(V, w.x, sizeof(double) * total, hipMemcpyDeviceToDevice, hr->stream));
   HIPC(hipStreamSynchronize(hr->stream));  // (as above)
   HIPC(hipMemcpyAsync(V, e0.data(), sizeof(double) * hr->T, hipMemcpyHostToDevice, hr->stream));
@@ -366,16 +366,16 @@ int dpgo_chordal_initialization(int d, int n, int m, const int32_t* p1, const in
   HIPC(hipStreamSynchronize(hr->stream));
   // ---- translations: minimise sum tau |t_j - t_i - R_i t_ij|^2, t_0 = 0: the translation columns of Q [R | t] = 0
   CHK(launch_spmm(ht, ht->Q, Tr, nullptr, rhs));
-  hipLaunchKernelGGL(k_init_axpby, dim3(gtot), dim3(kBlock), 0, ht->stream, -1.0, rhs, 0.0, rhs, total, ht->T, r, d, 1);
+  launch(k_init_axpby, gtot, 0, ht->stream, -1.0, rhs, 0.0, rhs, total, ht->T, r, d, 1);
   if (d == 2)
-    hipLaunchKernelGGL(k_init_diag<2>, dim3(gflat), dim3(kBlock), 0, ht->stream, ht->Q.dev(), w.diag, n);
+    launch(k_init_diag<2>, gflat, 0, ht->stream, ht->Q.dev(), w.diag, n);
   else
-    hipLaunchKernelGGL(k_init_diag<3>, dim3(gflat), dim3(kBlock), 0, ht->stream, ht->Q.dev(), w.diag, n);
+    launch(k_init_diag<3>, gflat, 0, ht->stream, ht->Q.dev(), w.diag, n);
   HIPC(hipGetLastError());
   CHK(init_pcg(ht, w, rhs, 1, tol, max_iter, &it_tr));
   // T = [R | t]: rotation columns from Tr, translation column from the solve (pose 0: zero)
-  hipLaunchKernelGGL(k_init_axpby, dim3(gtot), dim3(kBlock), 0, ht->stream, 1.0, w.x, 0.0, w.x, total, ht->T, r, d, 1);
-  hipLaunchKernelGGL(k_axpby_plain, dim3(gtot), dim3(kBlock), 0, ht->stream, 1.0, w.x, 1.0, Tr, total);
+  launch(k_init_axpby, gtot, 0, ht->stream, 1.0, w.x, 0.0, w.x, total, ht->T, r, d, 1);
+  launch(k_axpby_plain, gtot, 0, ht->stream, 1.0, w.x, 1.0, Tr, total);
   HIPC(hipGetLastError());
   HIPC(hipMemcpyAsync(T_host, Tr, sizeof(double) * total, hipMemcpyDeviceToHost, ht->stream));
   HIPC(hipStreamSynchronize(ht->stream));
@@ -432,12 +432,7 @@ int manifold_args(int r, int d, int n, int device) {
   HIPC(hipSetDevice(device));
   return DPGO_OK;
 }
-int tiles_grid(int d, int n) {
-  const int P = (64 / (d + 1)) * kWaves;
-  int t = (n + P - 1) / P;
-  if (t < 1) t = 1;
-  return t < kMaxGrid ? t : kMaxGrid;
-}
+int tiles_grid(int d, int n) { return std::min(kMaxGrid, pose_tiles(n, d + 1)); }
 }  // namespace
 
 
@@ -450,8 +445,10 @@ int dpgo_axpby_project_device(int r, int d, int n, double a, const double* A_dev
                               double c, const double* C_dev, int project, double* out_dev, void* stream) {
   if (!A_dev || !out_dev) return fail(DPGO_ERR_INVALID, "null pointer");
   if (n <= 0) return fail(DPGO_ERR_INVALID, "n <= 0");
-  DISPATCH(d, r, hipLaunchKernelGGL((k_axpby_project<D, R>), dim3(tiles_grid(d, n)), dim3(kBlock), 0,
-                                    (hipStream_t)stream, a, A_dev, b, B_dev, c, C_dev, project, out_dev, n));
+  CHK(dispatch_dr(d, r, [&](auto D, auto R) {
+    return launch(k_axpby_project<D, R>, tiles_grid(d, n), 0, (hipStream_t)stream, a, A_dev, b, B_dev, c, C_dev, project,
+                  out_dev, n);
+  }));
   HIPC(hipGetLastError());
   return DPGO_OK;
 }
@@ -468,7 +465,9 @@ int dpgo_round_trajectory_device(int r, int d, int n, const double* X_dev, const
   if (anchor_host) std::memcpy(an.v, anchor_host, sizeof(double) * (size_t)(d + 1) * r);
   int g = (n + kBlock - 1) / kBlock;
   if (g > kMaxGrid) g = kMaxGrid;
-  DISPATCH(d, r, hipLaunchKernelGGL((k_round<D, R>), dim3(g), dim3(kBlock), 0, (hipStream_t)stream, X_dev, an, T_dev, n));
+  CHK(dispatch_dr(d, r, [&](auto D, auto R) {
+    return launch(k_round<D, R>, g, 0, (hipStream_t)stream, X_dev, an, T_dev, n);
+  }));
   HIPC(hipGetLastError());
   return DPGO_OK;
 }
@@ -496,8 +495,9 @@ int dpgo_gather_tiles_device(int r, int d, const double* src_dev, const int32_t*
   size_t total = (size_t)count * (d + 1) * r;
   int g = (int)((total + kBlock - 1) / kBlock);
   if (g > kMaxGrid) g = kMaxGrid;
-  DISPATCH(d, r, hipLaunchKernelGGL((k_gather_tiles<D, R>), dim3(g), dim3(kBlock), 0, (hipStream_t)stream, src_dev,
-                                    idx_dev, count, dst_dev));
+  CHK(dispatch_dr(d, r, [&](auto D, auto R) {
+    return launch(k_gather_tiles<D, R>, g, 0, (hipStream_t)stream, src_dev, idx_dev, count, dst_dev);
+  }));
   HIPC(hipGetLastError());
   return DPGO_OK;
 }
@@ -510,13 +510,10 @@ int dpgo_permute_tiles_device(int r, int d, int n, const int32_t* new_index_dev,
   size_t total = (size_t)n * (d + 1) * r;
   int g = (int)((total + kBlock - 1) / kBlock);
   if (g > kMaxGrid) g = kMaxGrid;
-  if (forward) {
-    DISPATCH(d, r, hipLaunchKernelGGL((k_scatter_tiles<D, R>), dim3(g), dim3(kBlock), 0, (hipStream_t)stream, in_dev,
-                                      new_index_dev, n, out_dev));
-  } else {
-    DISPATCH(d, r, hipLaunchKernelGGL((k_gather_tiles<D, R>), dim3(g), dim3(kBlock), 0, (hipStream_t)stream, in_dev,
-                                      new_index_dev, n, out_dev));
-  }
+  CHK(dispatch_dr(d, r, [&](auto D, auto R) {
+    return launch(forward ? k_scatter_tiles<D, R> : k_gather_tiles<D, R>, g, 0, (hipStream_t)stream, in_dev, new_index_dev, n,
+                  out_dev);
+  }));
   HIPC(hipGetLastError());
   return DPGO_OK;
 }
@@ -574,7 +571,7 @@ int dpgo_exchange_plan_run(dpgo_exchange_plan_t pl, void* stream) {
   const ExchangeTable tb{pl->src, pl->idx, pl->dst, pl->first, pl->nmsg};
   const int g = std::max(1, std::min(kMaxGrid, (pl->total + kBlock / 4 - 1) / (kBlock / 4)));
   switch (pl->T) {
-#define CASE_T(TT) case TT: hipLaunchKernelGGL((k_gather_tiles_batched<TT>), dim3(g), dim3(kBlock), 0, (hipStream_t)stream, tb); break;
+#define CASE_T(TT) case TT: launch(k_gather_tiles_batched<TT>, g, 0, (hipStream_t)stream, tb); break;
     CASE_T(6) CASE_T(9) CASE_T(12) CASE_T(15) CASE_T(16) CASE_T(20) CASE_T(24)
 #undef CASE_T
     default: return fail(DPGO_ERR_UNSUPPORTED, "unsupported (d, r)");
@@ -599,7 +596,7 @@ int dpgo_flags_write_device(int n, unsigned long long* const* words_dev, const u
   for (int first = 0; first < n; first += kFlagCap) {
     FlagTable t;
     CHK(flag_table(n, words_dev, values, first, &t));
-    hipLaunchKernelGGL(k_flags_write, dim3(1), dim3(64), 0, (hipStream_t)stream, t);
+    launch_wg(k_flags_write, 1, dim3(64), 0, (hipStream_t)stream, t);
   }
   HIPC(hipGetLastError());
   return DPGO_OK;
@@ -610,7 +607,7 @@ int flags_wait(int n, unsigned long long* const* words_dev, const unsigned long 
   for (int first = 0; first < n; first += kFlagCap) {
     FlagTable t;
     CHK(flag_table(n, words_dev, values, first, &t));
-    hipLaunchKernelGGL(k_flags_wait, dim3(1), dim3(64), 0, (hipStream_t)stream, t, timeout_ms * 100000LL, err_word);
+    launch_wg(k_flags_wait, 1, dim3(64), 0, (hipStream_t)stream, t, timeout_ms * 100000LL, err_word);
   }
   HIPC(hipGetLastError());
   return DPGO_OK;
@@ -640,8 +637,10 @@ int dpgo_max_translation_distance_device(int r, int d, int n, const double* X_de
   hipStream_t s = (hipStream_t)stream;
   HIPC(hipMemsetAsync(out_dev, 0, sizeof(double), s));
   const int g = std::max(1, std::min(kMaxGrid, (n + kBlock - 1) / kBlock));
-  DISPATCH(d, r, hipLaunchKernelGGL((k_max_translation_distance<D, R>), dim3(g), dim3(kBlock), 0, s, X_dev, Xprev_dev, n,
-                                    reinterpret_cast<unsigned long long*>(out_dev)));
+  CHK(dispatch_dr(d, r, [&](auto D, auto R) {
+    return launch(k_max_translation_distance<D, R>, g, 0, s, X_dev, Xprev_dev, n,
+                  reinterpret_cast<unsigned long long*>(out_dev));
+  }));
   HIPC(hipGetLastError());
   if (out_host) {
     HIPC(hipMemcpyAsync(out_host, out_dev, sizeof(double), hipMemcpyDeviceToHost, s));
@@ -673,8 +672,9 @@ int dpgo_manifold_tangent_project(int r, int d, int n, const double* X, const do
   for (DevBuf<double>* q : {&x, &v, &o}) CHK(q->alloc(total));
   HIPC(hipMemcpy(x, X, vb, hipMemcpyHostToDevice));
   HIPC(hipMemcpy(v, V, vb, hipMemcpyHostToDevice));
-  DISPATCH(d, r, hipLaunchKernelGGL((k_precond<D, R>), dim3(tiles_grid(d, n)), dim3(kBlock), 0, (hipStream_t) nullptr,
-                                    x, v, (const double*)nullptr, o, n));
+  CHK(dispatch_dr(d, r, [&](auto D, auto R) {
+    return launch(k_precond<D, R>, tiles_grid(d, n), 0, nullptr, x, v, nullptr, o, n);
+  }));
   HIPC(hipGetLastError());
   HIPC(hipMemcpy(out, o, vb, hipMemcpyDeviceToHost));
   return DPGO_OK;
@@ -690,8 +690,9 @@ int dpgo_manifold_retract(int r, int d, int n, const double* X, const double* et
   for (DevBuf<double>* q : {&x, &v, &o}) CHK(q->alloc(total));
   HIPC(hipMemcpy(x, X, vb, hipMemcpyHostToDevice));
   HIPC(hipMemcpy(v, eta, vb, hipMemcpyHostToDevice));
-  DISPATCH(d, r, hipLaunchKernelGGL((k_retract<D, R>), dim3(tiles_grid(d, n)), dim3(kBlock), 0, (hipStream_t) nullptr,
-                                    x, v, scale, o, (const DevState*)nullptr, n));
+  CHK(dispatch_dr(d, r, [&](auto D, auto R) {
+    return launch(k_retract<D, R>, tiles_grid(d, n), 0, nullptr, x, v, scale, o, nullptr, n);
+  }));
   HIPC(hipGetLastError());
   HIPC(hipMemcpy(out, o, vb, hipMemcpyDeviceToHost));
   return DPGO_OK;

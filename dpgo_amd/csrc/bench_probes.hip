@@ -350,14 +350,14 @@ int dpgo_bench_iteration_kernels(dpgo_problem_t p, int reps, int warmup, double 
     if (rc == DPGO_OK) rc = timed([&]() -> int {
       if (ap) {
         return launch_ml_post_ap(p, p->x1, p->rr, p->z, p->pB(), nullptr);
-      } else if (p->tcg_sym) {
-        DISPATCH(p->d, p->r, hipLaunchKernelGGL((k_ml_post<D, R, 1, BsrSymDev>), dim3(p->grid_post()), dim3(kBlock), 0,
-                                                p->stream, p->sym.dev(), p->x1, L0.x, p->rr, p->dinv, p->ml_omega,
-                                                p->ml_shift, p->z, p->pB(), (const DevState*)nullptr, p->n));
-      } else {
-        DISPATCH(p->d, p->r, LAUNCH_SPLIT(p, k_ml_post, p->grid_post(), p->Q.dev(), p->x1, L0.x, p->rr, p->dinv, p->ml_omega,
-                                          p->ml_shift, p->z, p->pB(), (const DevState*)nullptr, p->n));
       }
+      CHK(dispatch_drs(p->d, p->r, p->split, [&](auto D, auto R, auto SPLIT) {
+        auto go = [&](auto kernel, const auto& Q) {
+          return launch(kernel, p->grid_post(), 0, p->stream, Q, p->x1, L0.x, p->rr, p->dinv, p->ml_omega, p->ml_shift, p->z,
+                        p->pB(), nullptr, p->n);
+        };
+        return p->tcg_sym ? go(k_ml_post<D, R, 1, BsrSymDev>, p->sym.dev()) : go(k_ml_post<D, R, SPLIT>, p->Q.dev());
+      }));
       HIPC(hipGetLastError());
       return DPGO_OK;
     }, &out_ms[3]);
@@ -440,8 +440,8 @@ extern "C" int dpgo_debug_reduction_primitives(int workgroups, int pay, int step
   switch (pay) {
 #define CASE_(P)                                                                                                         \
   case P:                                                                                                                \
-    hipLaunchKernelGGL((k_probe_allreduce<P>), dim3(workgroups), dim3(kBlock), 0, nullptr, gran, salt, steps, in_dev,   \
-                       pay_in_dev, sums_dev, pay_out_dev, rows_out_dev, error, poll);                                    \
+    launch(k_probe_allreduce<P>, workgroups, 0, nullptr, gran, salt, steps, in_dev, pay_in_dev, sums_dev, pay_out_dev,     \
+           rows_out_dev, error, poll);                                                                                   \
     break;
     CASE_(6) CASE_(9) CASE_(12) CASE_(15) CASE_(16) CASE_(20) CASE_(24)
 #undef CASE_

@@ -86,6 +86,17 @@ void solve_lt(const std::vector<double>& Lm, int n, std::vector<double>& Y, int 
 }
 
 // ---------------------------------------------------------------- the solver's device state
+// CW = W C(X) (k_cert_apply) on `g` workgroups: the symmetric copy of Q at one pose per d+1 lanes, or Q at the handle's split
+int launch_cert_apply(dpgo_problem_s* p, int d, int r, bool sym, int g, const double* S, const double* W, double* CW,
+                      double* part, int n) {
+  CHK(dispatch_drs(d, r, p->split, [&](auto D, auto R, auto SPLIT) {
+    if (sym) return launch(k_cert_apply<D, R, 1, BsrSymDev>, g, 0, p->stream, p->sym.dev(), S, W, CW, part, n);
+    return launch(k_cert_apply<D, R, SPLIT>, g, 0, p->stream, p->Q.dev(), S, W, CW, part, n);
+  }));
+  HIPC(hipGetLastError());
+  return DPGO_OK;
+}
+
 struct Cert {
   dpgo_problem_s* p;
   int d, r, n;
@@ -130,22 +141,14 @@ struct Cert {
 
   // CW = W C(X); with wcw != null also W CW^T (r x r, row-major) on the host
   int apply(const double* W, double* CW, std::vector<double>* wcw = nullptr) {
-    int g = 0;
-    if (sym) {
-      g = p->grid_outer_sym();
-      DISPATCH(d, r, hipLaunchKernelGGL((k_cert_apply<D, R, 1, BsrSymDev>), dim3(g), dim3(kBlock), 0, p->stream,
-                                        p->sym.dev(), S, W, CW, part, n));
-    } else {
-      g = p->grid_s();
-      DISPATCH(d, r, LAUNCH_SPLIT(p, k_cert_apply, g, p->Q.dev(), S, W, CW, part, n));
-    }
-    HIPC(hipGetLastError());
+    const int g = sym ? p->grid_outer_sym() : p->grid_s();
+    CHK(launch_cert_apply(p, d, r, sym, g, S, W, CW, part, n));
     ++products;
     if (wcw) CHK(reduce(g, r * r, *wcw));
     return DPGO_OK;
   }
   int reduce(int nwg, int E, std::vector<double>& out) {
-    hipLaunchKernelGGL(k_cert_reduce, dim3((E + kBlock - 1) / kBlock), dim3(kBlock), 0, p->stream, part, nwg, E, red);
+    launch(k_cert_reduce, (E + kBlock - 1) / kBlock, 0, p->stream, part, nwg, E, red);
     HIPC(hipGetLastError());
     HIPC(hipMemcpyAsync(hbuf, red, sizeof(double) * E, hipMemcpyDeviceToHost, p->stream));
     HIPC(hipStreamSynchronize(p->stream));
@@ -166,8 +169,9 @@ struct Cert {
     const size_t chunks = ((size_t)n * (d + 1) + kCertCols - 1) / kCertCols;
     const int g = (int)std::max<size_t>(1, std::min<size_t>(kGramWg, chunks));
     const int nb = (int)B.size(), np = (int)pairs.size();
-    DISPATCH(d, r, hipLaunchKernelGGL((k_cert_gram<D, R, kCertMaxBlocks>), dim3(g), dim3(kBlock), 0, p->stream, in, nb, pr,
-                                      np, part, n));
+    CHK(dispatch_dr(d, r, [&](auto D, auto R) {
+      return launch(k_cert_gram<D, R, kCertMaxBlocks>, g, 0, p->stream, in, nb, pr, np, part, n);
+    }));
     HIPC(hipGetLastError());
     return reduce(g, np * r * r, G);
   }
@@ -186,15 +190,18 @@ struct Cert {
     std::copy(M.begin(), M.end(), h);
     HIPC(hipMemcpyAsync(dv, h, sizeof(double) * M.size(), hipMemcpyHostToDevice, p->stream));
     const int nb = (int)B.size(), nout = (int)out.size();
-    DISPATCH(d, r, hipLaunchKernelGGL((k_cert_combine<D, R, kCertMaxBlocks>), dim3(flat_grid()), dim3(kBlock), 0,
-                                      p->stream, in, nb, o, nout, (const double*)dv, n));
+    CHK(dispatch_dr(d, r, [&](auto D, auto R) {
+      return launch(k_cert_combine<D, R, kCertMaxBlocks>, flat_grid(), 0, p->stream, in, nb, o, nout, (const double*)dv, n);
+    }));
     HIPC(hipGetLastError());
     return DPGO_OK;
   }
   // Z = M^-1 V without tangent projection
   int precondition(const double* V, double* Z) {
     if (precond == DPGO_PRECOND_BLOCK_JACOBI) {
-      DISPATCH(d, r, hipLaunchKernelGGL((k_cert_jacobi<D, R>), dim3(p->grid()), dim3(kBlock), 0, p->stream, V, p->dinv, Z, n));
+      CHK(dispatch_dr(d, r, [&](auto D, auto R) {
+        return launch(k_cert_jacobi<D, R>, p->grid(), 0, p->stream, V, p->dinv, Z, n);
+      }));
       HIPC(hipGetLastError());
     } else if (precond == DPGO_PRECOND_MULTILEVEL) {
       CHK(launch_ml_apply(p, zero, V, Z));
@@ -220,9 +227,9 @@ int q_scale(dpgo_problem_s* p, DevBuf<double>& dv, double* out) {
   const int g = (p->n + kBlock - 1) / kBlock;
   CHK(dv.alloc(g));
   if (p->d == 2)
-    hipLaunchKernelGGL(k_cert_scale<2>, dim3(g), dim3(kBlock), 0, p->stream, p->Q.dev(), dv, p->n);
+    launch(k_cert_scale<2>, g, 0, p->stream, p->Q.dev(), dv, p->n);
   else
-    hipLaunchKernelGGL(k_cert_scale<3>, dim3(g), dim3(kBlock), 0, p->stream, p->Q.dev(), dv, p->n);
+    launch(k_cert_scale<3>, g, 0, p->stream, p->Q.dev(), dv, p->n);
   HIPC(hipGetLastError());
   std::vector<double> h(g);
   HIPC(hipMemcpyAsync(h.data(), dv, sizeof(double) * g, hipMemcpyDeviceToHost, p->stream));
@@ -297,7 +304,9 @@ int certify_impl(dpgo_problem_s* p, const double* X, const dpgo_certify_params* 
   CHK(c.vec(&CK1));
   CHK(c.vec(&Z0));
   CHK(c.vec(&Z1));
-  DISPATCH(c.d, r, hipLaunchKernelGGL((k_cert_indicator<D, R>), dim3(c.flat_grid()), dim3(kBlock), 0, p->stream, K1, c.n));
+  CHK(dispatch_dr(c.d, r, [&](auto D, auto R) {
+    return launch(k_cert_indicator<D, R>, c.flat_grid(), 0, p->stream, K1, c.n);
+  }));
   HIPC(hipGetLastError());
   CHK(c.apply(X, CK0));
   CHK(c.apply(K1, CK1));
@@ -372,8 +381,9 @@ int certify_impl(dpgo_problem_s* p, const double* X, const dpgo_certify_params* 
   // ---- block LOBPCG on the complement of Z
   double *W, *T, *P, *CW, *CT, *CP, *W2, *P2, *CW2, *CP2, *Rs;
   for (double** v : {&W, &T, &P, &CW, &CT, &CP, &W2, &P2, &CW2, &CP2, &Rs}) CHK(c.vec(v));
-  DISPATCH(c.d, r, hipLaunchKernelGGL((k_cert_random<D, R>), dim3(c.flat_grid()), dim3(kBlock), 0, p->stream,
-                                      (unsigned long long)prm.seed, W, c.n));
+  CHK(dispatch_dr(c.d, r, [&](auto D, auto R) {
+    return launch(k_cert_random<D, R>, c.flat_grid(), 0, p->stream, (unsigned long long)prm.seed, W, c.n);
+  }));
   HIPC(hipGetLastError());
   // V <- V - (V Z^T) Z - (V U^T) U for orthonormal Z blocks and (optionally) an orthonormal block U; into `out`
   auto project = [&](const double* V, const double* U, double* out) -> int {
@@ -632,13 +642,7 @@ int dpgo_problem_certificate_apply(dpgo_problem_t h, const double* X_host, const
   bool sym = false;
   if (h->sym_wanted() && h->split == 1) CHK(sym_ensure(h, &sym));
   CHK(launch_grad(h, X, nullptr, S, nullptr, nullptr, sym));
-  if (sym) {
-    DISPATCH(h->d, h->r, hipLaunchKernelGGL((k_cert_apply<D, R, 1, BsrSymDev>), dim3(h->grid_outer_sym()), dim3(kBlock), 0,
-                                            h->stream, h->sym.dev(), S, V, CV, part, h->n));
-  } else {
-    DISPATCH(h->d, h->r, LAUNCH_SPLIT(h, k_cert_apply, h->grid_s(), h->Q.dev(), S, V, CV, part, h->n));
-  }
-  HIPC(hipGetLastError());
+  CHK(launch_cert_apply(h, h->d, h->r, sym, sym ? h->grid_outer_sym() : h->grid_s(), S, V, CV, part, h->n));
   return d2h(h, CV_host, CV);
 }
 
@@ -656,8 +660,9 @@ int dpgo_certify_escape_device(dpgo_problem_t h_next, int r, const double* X_dev
   DevBuf<double> Xl;
   CHK(Xl.alloc((size_t)p->n * p->T));
   auto lift = [&](double a) -> int {
-    DISPATCH(p->d, r, hipLaunchKernelGGL((k_cert_lift<D, R>), dim3(g), dim3(kBlock), 0, p->stream, X_dev, witness_dev, a,
-                                         Xl, p->n));
+    CHK(dispatch_dr(p->d, r, [&](auto D, auto R) {
+      return launch(k_cert_lift<D, R>, g, 0, p->stream, X_dev, witness_dev, a, Xl, p->n);
+    }));
     HIPC(hipGetLastError());
     return DPGO_OK;
   };

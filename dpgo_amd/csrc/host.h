@@ -1,4 +1,5 @@
-// host.h -- what the translation units of libdpgo_hip.so share: error reporting, the (d, r) dispatch macros, the problem
+// host.h -- what the translation units of libdpgo_hip.so share: error reporting, the typed helpers that choose a kernel
+// instance (dispatch_dr, dispatch_split, dispatch_drs) and launch it (launch), the tile count of a pose grid (pose_tiles), the problem
 // handle (struct dpgo_problem_s: device buffers, hierarchy, solver state of one PoseGraph) and the declarations of the
 // host-side helpers each unit defines.
 //   problem.hip     handle lifecycle, Q / G upload, symmetric storage, QuadraticProblem evaluations (k_spmm, k_grad, k_hess ...)
@@ -21,6 +22,7 @@
 #include <sched.h>
 #include <mutex>
 #include <thread>
+#include <type_traits>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -68,31 +70,59 @@ inline bool supported(int d, int r) {
   return false;
 }
 
-// DISPATCH(d, r, body): body sees constexpr int D, R
-#define DPGO_CASE(dd, rr, ...)   \
-  case (dd) * 16 + (rr): {       \
-    constexpr int D = dd, R = rr; \
-    __VA_ARGS__;                 \
-  } break;
-#define DISPATCH(d, r, ...)                                                                         \
-  switch ((d) * 16 + (r)) {                                                                         \
-    DPGO_CASE(2, 2, __VA_ARGS__) DPGO_CASE(2, 3, __VA_ARGS__) DPGO_CASE(2, 4, __VA_ARGS__)          \
-    DPGO_CASE(2, 5, __VA_ARGS__) DPGO_CASE(3, 3, __VA_ARGS__) DPGO_CASE(3, 4, __VA_ARGS__)          \
-    DPGO_CASE(3, 5, __VA_ARGS__) DPGO_CASE(3, 6, __VA_ARGS__)                                       \
-    default:                                                                                        \
-      return fail(DPGO_ERR_UNSUPPORTED, "unsupported (d, r)");                                      \
-  }
+// ---- choosing and launching a kernel instance ----
+// Run-time values that select a template instance reach the code as types: Int<V> for a number, a value of the type
+// itself (float{}, double{}) for a storage type.  A dispatch_* helper calls a generic lambda with them and returns what the
+// lambda returns (a DPGO_* code); the call of the lambda is always inlined, so a launch function compiles to the straight
+// code a switch would give.  An Int<V> converts to its number at compile time, so a lambda that takes
+// (auto D, auto R) writes k_retract<D, R>; only a lambda NESTED in it cannot (it would capture D by reference): a body that
+// nests takes (auto Dc, auto Rc) and starts with
+//   constexpr int D = decltype(Dc)::value, R = decltype(Rc)::value;
+template <int V>
+using Int = std::integral_constant<int, V>;
 
-// launch a <D, R, SPLIT> kernel with the handle's split factor
-#define LAUNCH_SPLIT(p, KERNEL, GRID, ...)                                                            \
-  do {                                                                                                \
-    if ((p)->split == 4)                                                                              \
-      hipLaunchKernelGGL((KERNEL<D, R, 4>), dim3(GRID), dim3(kBlock), 0, (p)->stream, __VA_ARGS__);   \
-    else if ((p)->split == 2)                                                                         \
-      hipLaunchKernelGGL((KERNEL<D, R, 2>), dim3(GRID), dim3(kBlock), 0, (p)->stream, __VA_ARGS__);   \
-    else                                                                                              \
-      hipLaunchKernelGGL((KERNEL<D, R, 1>), dim3(GRID), dim3(kBlock), 0, (p)->stream, __VA_ARGS__);   \
-  } while (0)
+// f(Int<D>{}, Int<R>{}) for the pair of DPGO_FOR_DR that equals (d, r)
+template <class F>
+__attribute__((always_inline)) inline int dispatch_dr(int d, int r, F&& f) {
+#define M(dd, rr) \
+  if (d == dd && r == rr) [[clang::always_inline]] return f(Int<dd>{}, Int<rr>{});
+  DPGO_FOR_DR(M)
+#undef M
+  return fail(DPGO_ERR_UNSUPPORTED, "unsupported (d, r)");
+}
+// f(Int<SPLIT>{}) for the lane groups per pose of a <D, R, SPLIT> kernel: 4, 2, anything else is 1
+template <class F>
+__attribute__((always_inline)) inline int dispatch_split(int split, F&& f) {
+  [[clang::always_inline]] return split == 4 ? f(Int<4>{}) : split == 2 ? f(Int<2>{}) : f(Int<1>{});
+}
+
+// both at once: f(Int<D>{}, Int<R>{}, Int<SPLIT>{})
+template <class F>
+__attribute__((always_inline)) inline int dispatch_drs(int d, int r, int split, F&& f) {
+  return dispatch_dr(d, r, [&](auto D, auto R) { return dispatch_split(split, [&](auto S) { return f(D, R, S); }); });
+}
+
+// The one place a kernel is launched.  The parameter types are the kernel's own and every argument is converted to its
+// parameter's type here: nullptr needs no cast, a DevBuf<T> no .get(), and an argument of the wrong type or a wrong number
+// of them is an error at the call.  Workgroups of kBlock threads unless launch_wg says otherwise.  Nothing is checked
+// at run time: the launch function's HIPC(hipGetLastError()) does that once for all its launches, and the DPGO_OK returned
+// only lets a selector's lambda end in `return launch(...)`.
+template <class... KArgs, class... Args>
+inline int launch_wg(void (*kernel)(KArgs...), dim3 grid, dim3 block, size_t lds_bytes, hipStream_t stream, Args&&... args) {
+  static_assert(sizeof...(KArgs) == sizeof...(Args), "launch: as many arguments as the kernel has parameters");
+  hipLaunchKernelGGL(kernel, grid, block, lds_bytes, stream, static_cast<KArgs>(std::forward<Args>(args))...);
+  return DPGO_OK;
+}
+template <class... KArgs, class... Args>
+inline int launch(void (*kernel)(KArgs...), dim3 grid, size_t lds_bytes, hipStream_t stream, Args&&... args) {
+  return launch_wg(kernel, grid, dim3(kBlock), lds_bytes, stream, std::forward<Args>(args)...);
+}
+
+// workgroups that hold n poses at (64 / (b * split)) * kWaves poses each (b = d + 1 lanes per lane group), at least one
+inline int pose_tiles(int n, int b, int split = 1) {
+  const int P = (64 / (b * split)) * kWaves;
+  return std::max(1, (n + P - 1) / P);
+}
 
 // Caller pointers (include/dpgo_hip.h, "Alignment"): any 8-byte-aligned address is valid; the kernels that move own-tile
 // spans in 16-byte pieces (dbl2, span_from_lds) run on 16-byte-aligned buffers only
@@ -500,65 +530,33 @@ struct dpgo_problem_s {
   double* pA() const { return partials + 1 * kPartialCap * kNP; }
   double* pB() const { return partials + 2 * kPartialCap * kNP; }
   double* pH() const { return partials + 3 * kPartialCap * kNP; }
-  int grid() const {
-    const int P = (64 / b) * kWaves;
-    int tiles = (n + P - 1) / P;
-    if (tiles < 1) tiles = 1;
-    return tiles < cap_u ? tiles : cap_u;
-  }
+  int grid() const { return std::min(pose_tiles(n, b), cap_u); }
   int cap_u = kMaxGrid, cap_h = kMaxGrid;  // launch caps of the streaming / SpMM kernel families
   // k_tcg_update_span's multilevel-mode instance (no iterate, no projection: 143 VGPRs = 3 waves per SIMD) has its own cap
   int cap_u_ml = kMaxGrid;
-  int grid_u(bool ml_mode) const {
-    const int P = (64 / b) * kWaves;
-    const int tiles = std::max(1, (n + P - 1) / P);
-    return std::min(tiles, ml_mode ? cap_u_ml : cap_u);
-  }
+  int grid_u(bool ml_mode) const { return std::min(pose_tiles(n, b), ml_mode ? cap_u_ml : cap_u); }
   // entries of partial region B (<r,r>, <z,r>) that k_tcg_hess has to sum: written by k_tcg_update (its grid) or,
   // with the fused multilevel cycle, by k_ml_post (SpMM-family grid)
   bool zr_from_post = false;
   int nb_zr() const { return zr_from_post ? grid_post() : grid(); }
   int split = 1;  // lane groups per pose in the SpMM kernels (latency layout for small blocks)
-  int grid_s() const {  // SpMM kernels (k_spmm, k_grad, k_hess, k_tcg_hess)
-    const int P = (64 / (b * split)) * kWaves;
-    int tiles = (n + P - 1) / P;
-    if (tiles < 1) tiles = 1;
-    const int cap = tcg_sym ? cap_hs : cap_h;
-    return tiles < cap ? tiles : cap;
-  }
+  // SpMM kernels (k_spmm, k_grad, k_hess, k_tcg_hess)
+  int grid_s() const { return std::min(pose_tiles(n, b, split), tcg_sym ? cap_hs : cap_h); }
   // level-0 restriction / post-smoothing of the multilevel cycle: their own resident-slot counts (lighter kernels than
   // k_tcg_hess: with 4 instead of 3 waves per SIMD the 1 563 tiles of the 100k block take 2 rounds instead of 3)
   int cap_restrict = kMaxGrid, cap_post = kMaxGrid;
-  int grid_tiles(int cap) const {
-    const int P = (64 / (b * split)) * kWaves;
-    int tiles = (n + P - 1) / P;
-    if (tiles < 1) tiles = 1;
-    return tiles < cap ? tiles : cap;
-  }
-  int grid_restrict() const { return grid_tiles(cap_restrict); }
-  int grid_post() const { return grid_tiles(cap_post); }
+  int grid_restrict() const { return std::min(pose_tiles(n, b, split), cap_restrict); }
+  int grid_post() const { return std::min(pose_tiles(n, b, split), cap_post); }
   // the outer iteration's kernels on the symmetric storage (k_grad, k_hess: 110-114 VGPRs = 4 waves per SIMD) have their own
   // cap -- grid_s() is sized for the tCG-step kernel's 2 waves per SIMD -- and whoever sums their partials is told the
   // grid of the launch that wrote them
   int cap_outer_sym = kMaxGrid;
   int nb_grad = 0, nb_hess = 0;
-  int grid_outer_sym() const {
-    const int P = (64 / b) * kWaves;
-    const int tiles = std::max(1, (n + P - 1) / P);
-    return std::min(tiles, cap_outer_sym);
-  }
+  int grid_outer_sym() const { return std::min(pose_tiles(n, b), cap_outer_sym); }
   int cap_spmm_sym = kMaxGrid;  // launch cap of k_spmm_sym (resident count of the compiled kernel)
-  int grid_spmm_sym() const {
-    const int P = (64 / b) * kWaves;
-    const int tiles = std::max(1, (n + P - 1) / P);
-    return std::min(tiles, cap_spmm_sym);
-  }
-  int grid_spmm() const {  // plain k_spmm: no partial sums, higher occupancy than the fused tCG kernel
-    const int P = (64 / (b * split)) * kWaves;
-    int tiles = (n + P - 1) / P;
-    if (tiles < 1) tiles = 1;
-    return tiles < kMaxGrid ? tiles : kMaxGrid;
-  }
+  int grid_spmm_sym() const { return std::min(pose_tiles(n, b), cap_spmm_sym); }
+  // plain k_spmm: no partial sums, higher occupancy than the fused tCG kernel
+  int grid_spmm() const { return std::min(pose_tiles(n, b, split), kMaxGrid); }
   int grid_flat() const {  // elementwise kernels
     size_t total = (size_t)n * T;
     size_t g = (total + kBlock - 1) / kBlock;

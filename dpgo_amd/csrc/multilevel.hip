@@ -690,13 +690,10 @@ bool gj_use_mfma() {
 int dense_spd_inverse(hipStream_t s, double* M, int lda, double* W, double* Rx, bool mfma) {
   const int nt = lda / kNB;
   for (int kb = 0; kb < nt; ++kb) {
-    hipLaunchKernelGGL(k_sweep_panel, dim3(nt), dim3(kBlock), 0, s, M, lda, kb, W, Rx);
-    if (mfma)
-      hipLaunchKernelGGL(k_sweep_update<true>, dim3(nt, nt), dim3(kBlock), 0, s, M, lda, kb, W, Rx);
-    else
-      hipLaunchKernelGGL(k_sweep_update<false>, dim3(nt, nt), dim3(kBlock), 0, s, M, lda, kb, W, Rx);
+    launch(k_sweep_panel, nt, 0, s, M, lda, kb, W, Rx);
+    launch(mfma ? k_sweep_update<true> : k_sweep_update<false>, dim3(nt, nt), 0, s, M, lda, kb, W, Rx);
   }
-  hipLaunchKernelGGL(k_sweep_finish, dim3(nt, nt), dim3(kBlock), 0, s, M, lda);
+  launch(k_sweep_finish, dim3(nt, nt), 0, s, M, lda);
   HIPC(hipGetLastError());
   return DPGO_OK;
 }
@@ -712,39 +709,36 @@ int ml_numeric_setup_d(dpgo_problem_s* p) {
     // (the wave-parallel set-up kernels: one wave per aggregate / per coarse slot)
     auto wave_grid = [](int items) { return std::max(1, std::min(kMaxGrid, (items + kWaves - 1) / kWaves)); };
     if (L.graph)
-      hipLaunchKernelGGL(k_ml_build_P_tree_wave<D>, dim3(wave_grid(C.n)), dim3(kBlock), 0, p->stream, p->Q.dev(), L.agg_ptr,
-                         L.agg_mem, L.parent, L.pslot, L.mem_pos, L.Pb, C.n);
+      launch(k_ml_build_P_tree_wave<D>, wave_grid(C.n), 0, p->stream, p->Q.dev(), L.agg_ptr, L.agg_mem, L.parent, L.pslot,
+             L.mem_pos, L.Pb, C.n);
     else
-      hipLaunchKernelGGL(k_ml_build_P<D>, dim3(flat_grid(C.n)), dim3(kBlock), 0, p->stream, p->Q.dev(), p->n, (int)stride,
-                         (int)span, L.Pb, C.n);
+      launch(k_ml_build_P<D>, flat_grid(C.n), 0, p->stream, p->Q.dev(), p->n, (int)stride, (int)span, L.Pb, C.n);
     const BsrDev A = (l == 0) ? p->Q.dev() : L.A.dev();
     const bool have_ap = l == 0 && L.AP.vals;
     if (have_ap)  // A P first: the Galerkin operator of a two-level hierarchy is its restriction
-      hipLaunchKernelGGL(k_ml_build_AP<D>, dim3(flat_grid(L.n)), dim3(kBlock), 0, p->stream, p->Q.dev(), p->ml_shift, L.Pb,
-                         L.agg(), L.n, L.AP.dev(), L.AP.vals);
+      launch(k_ml_build_AP<D>, flat_grid(L.n), 0, p->stream, p->Q.dev(), p->ml_shift, L.Pb, L.agg(), L.n, L.AP.dev(),
+             L.AP.vals);
     if (have_ap)
-      hipLaunchKernelGGL(k_ml_galerkin_ap<D>, dim3(wave_grid(C.A.nnzb)), dim3(kBlock), 0, p->stream, L.AP.dev(), L.Pb,
-                         L.agg(), L.agg_ptr, L.agg_mem, L.n, C.slot_row, C.A.colidx, C.A.vals, C.A.nnzb);
+      launch(k_ml_galerkin_ap<D>, wave_grid(C.A.nnzb), 0, p->stream, L.AP.dev(), L.Pb, L.agg(), L.agg_ptr, L.agg_mem, L.n,
+             C.slot_row, C.A.colidx, C.A.vals, C.A.nnzb);
     else
-      hipLaunchKernelGGL(k_ml_galerkin<D>, dim3(flat_grid(C.A.nnzb)), dim3(kBlock), 0, p->stream, A,
-                         (l == 0) ? p->ml_shift : 0.0, L.Pb, L.agg(), L.agg_ptr, L.agg_mem, L.n, C.slot_row, C.A.colidx,
-                         C.A.vals, C.A.nnzb);
+      launch(k_ml_galerkin<D>, flat_grid(C.A.nnzb), 0, p->stream, A, (l == 0) ? p->ml_shift : 0.0, L.Pb, L.agg(), L.agg_ptr,
+             L.agg_mem, L.n, C.slot_row, C.A.colidx, C.A.vals, C.A.nnzb);
     if (C.k)  // smoother of the next level (level 0 uses the handle's block-Jacobi factors)
-      hipLaunchKernelGGL(k_build_dinv<D>, dim3(flat_grid(C.n)), dim3(kBlock), 0, p->stream, C.A.dev(), 0.0, C.dinv, C.n);
+      launch(k_build_dinv<D>, flat_grid(C.n), 0, p->stream, C.A.dev(), 0.0, C.dinv, C.n);
     stride = span;
   }
   HIPC(hipGetLastError());
   auto& Lc = p->ml.back();
   const int lda = p->dense.lda, N = Lc.n * p->b;
   HIPC(hipMemsetAsync(p->dense.inv, 0, sizeof(double) * (size_t)lda * (lda + 8), p->stream));
-  hipLaunchKernelGGL(k_dense_pad_identity, dim3(1), dim3(kBlock), 0, p->stream, p->dense.inv, lda, N);
-  hipLaunchKernelGGL(k_ml_dense_assemble<D>, dim3(flat_grid(Lc.A.nnzb)), dim3(kBlock), 0, p->stream, Lc.A.dev(),
-                     Lc.slot_row, p->dense.inv, lda, Lc.A.nnzb);
+  launch(k_dense_pad_identity, 1, 0, p->stream, p->dense.inv, lda, N);
+  launch(k_ml_dense_assemble<D>, flat_grid(Lc.A.nnzb), 0, p->stream, Lc.A.dev(), Lc.slot_row, p->dense.inv, lda, Lc.A.nnzb);
   HIPC(hipGetLastError());
   CHK(dense_spd_inverse(p->stream, p->dense.inv, lda, p->dense.W, p->dense.Rx, gj_use_mfma()));
   if (p->dense.packed) {
     const int nT = lda / kNB;
-    hipLaunchKernelGGL(k_dense_pack_lower, dim3(nT, nT), dim3(kBlock), 0, p->stream, p->dense.inv, lda, p->dense.packed);
+    launch(k_dense_pack_lower, dim3(nT, nT), 0, p->stream, p->dense.inv, lda, p->dense.packed);
     HIPC(hipGetLastError());
   }
   {  // the fp32 storage of the inverse: what the cycle streams when the dense level is kept in fp32 -- by request
@@ -753,10 +747,9 @@ int ml_numeric_setup_d(dpgo_problem_s* p) {
      // array stays exact, the cycle applies its rounding)
     const size_t total = (size_t)lda * (lda + 8);
     if (p->ml_coarse_bits == 32)
-      hipLaunchKernelGGL(k_dense_round_f32, dim3(flat_grid(total)), dim3(kBlock), 0, p->stream, p->dense.inv, p->dense.inv32,
-                         total);
+      launch(k_dense_round_f32, flat_grid(total), 0, p->stream, p->dense.inv, p->dense.inv32, total);
     else
-      hipLaunchKernelGGL(k_copy_f32, dim3(flat_grid(total)), dim3(kBlock), 0, p->stream, p->dense.inv, p->dense.inv32, total);
+      launch(k_copy_f32, flat_grid(total), 0, p->stream, p->dense.inv, p->dense.inv32, total);
     HIPC(hipGetLastError());
   }
   return DPGO_OK;
@@ -926,7 +919,7 @@ int ml_ops32_ensure(dpgo_problem_s* p) {
   if (!L0.x1f) CHK(L0.x1f.alloc((size_t)L0.n * p->T));
   if (!L0.res1f) CHK(L0.res1f.alloc((size_t)L0.n * p->T));
   auto copy = [&](const double* in, float* out, size_t total) {
-    hipLaunchKernelGGL(k_copy_f32, dim3(flat_grid(total)), dim3(kBlock), 0, p->stream, in, out, total);
+    launch(k_copy_f32, flat_grid(total), 0, p->stream, in, out, total);
   };
   copy(p->sym.uvalsT, p->sym.uvalsT32, nu);
   copy(L0.AP.vals, L0.AP32, nap);
@@ -940,6 +933,15 @@ int ml_ops32_ensure(dpgo_problem_s* p) {
 // matrix byte); balanced rounds: every workgroup takes the same number of node groups (a ragged last round would leave
 // most of the chip idle while the dense inverse streams).
 int persist_capacity(int device);  // (two resident slots per CU; below)
+// f(Int<NODES>{}, a value of the storage type) for the k_ml_coarse_prolong<D, R, NODES, MT> instances that are compiled:
+// 4 / 2 / 1 nodes per workgroup in float and double, 3 in double only
+template <class F>
+int dispatch_coarse(int nodes, bool f32, F&& f) {
+  if (nodes == 4) return f32 ? f(Int<4>{}, float{}) : f(Int<4>{}, double{});
+  if (nodes == 3) return f(Int<3>{}, double{});
+  if (nodes == 2) return f32 ? f(Int<2>{}, float{}) : f(Int<2>{}, double{});
+  return f32 ? f(Int<1>{}, float{}) : f(Int<1>{}, double{});
+}
 int launch_coarse_prolong(dpgo_problem_s* p, const dpgo_problem_s::MlLevel& L, const dpgo_problem_s::MlLevel& C,
                           const DevState* gate, double* xc_out) {
   const bool f32 = p->coarse32_active();
@@ -959,26 +961,16 @@ int launch_coarse_prolong(dpgo_problem_s* p, const dpgo_problem_s::MlLevel& L, c
   // non-temporal loads of the inverse whenever the loop's working set does not fit the Infinity Cache (kernel comment)
   int hint = p->beyond_cache();
   if (options().coarse_nt >= 0) hint = options().coarse_nt != 0;  // tuning knob
-#define COARSE_LAUNCH(NODES, MT, MPTR)                                                                               \
-  hipLaunchKernelGGL((k_ml_coarse_prolong<D, R, NODES, MT>), dim3(gc), dim3(kBlock), 0, p->stream, MPTR, p->dense.lda,   \
-                     reinterpret_cast<const MT*>(C.r.get()), L.x1, L.Pb, L.k, L.x, gate, L.n, C.n, xc_out, hint)
-  DISPATCH(p->d, p->r, {
-    if (nodes == 4 && f32)
-      COARSE_LAUNCH(4, float, p->dense.inv32);
-    else if (nodes == 4)
-      COARSE_LAUNCH(4, double, p->dense.inv);
-    else if (nodes == 3)
-      COARSE_LAUNCH(3, double, p->dense.inv);
-    else if (nodes == 2 && f32)
-      COARSE_LAUNCH(2, float, p->dense.inv32);
-    else if (nodes == 2)
-      COARSE_LAUNCH(2, double, p->dense.inv);
-    else if (f32)
-      COARSE_LAUNCH(1, float, p->dense.inv32);
-    else
-      COARSE_LAUNCH(1, double, p->dense.inv);
-  });
-#undef COARSE_LAUNCH
+  CHK(dispatch_dr(p->d, p->r, [&](auto Dc, auto Rc) {
+    constexpr int D = decltype(Dc)::value, R = decltype(Rc)::value;
+    return dispatch_coarse(nodes, f32, [&](auto Nc, auto mt) {
+      using MT = decltype(mt);  // (the inverse and, in the same buffer, the right-hand side are stored in this type)
+      const MT* inv;
+      if constexpr (std::is_same_v<MT, float>) inv = p->dense.inv32; else inv = p->dense.inv;
+      return launch(k_ml_coarse_prolong<D, R, decltype(Nc)::value, MT>, gc, 0, p->stream, inv, p->dense.lda,
+                    reinterpret_cast<const MT*>(C.r.get()), L.x1, L.Pb, L.k, L.x, gate, L.n, C.n, xc_out, hint);
+    });
+  }));
   HIPC(hipGetLastError());
   return DPGO_OK;
 }
@@ -986,25 +978,36 @@ int launch_coarse_prolong(dpgo_problem_s* p, const dpgo_problem_s::MlLevel& L, c
 // Dense level from the packed lower triangle: xc = A_c^-1 rc into C.x (two launches: partial products, fixed-order sums)
 int launch_dense_sym(dpgo_problem_s* p, const dpgo_problem_s::MlLevel& C, const DevState* gate) {
   const int N = C.n * p->b, nT = p->dense.lda / kNB;
-  switch (p->r) {
-#define DENSE_SYM_CASE(RR)                                                                                              \
-  case RR:                                                                                                              \
-    hipLaunchKernelGGL((k_dense_sym_apply<RR>), dim3(p->dense.nchunks), dim3(kBlock), 0, p->stream, p->dense.packed,          \
-                       p->dense.chunks, C.r, N, p->dense.lda, p->dense.pd, p->dense.pt, gate);                                       \
-    hipLaunchKernelGGL((k_dense_sym_finish<RR>), dim3(nT, 4), dim3(kBlock), 0, p->stream, p->dense.pd, p->dense.pt,            \
-                       p->dense.chunk_first, nT, N, p->dense.lda, C.x, gate);                                                  \
-    break;
-    DENSE_SYM_CASE(2)
-    DENSE_SYM_CASE(3)
-    DENSE_SYM_CASE(4)
-    DENSE_SYM_CASE(5)
-    DENSE_SYM_CASE(6)
-#undef DENSE_SYM_CASE
-    default:
-      return fail(DPGO_ERR_UNSUPPORTED, "unsupported r");
+  auto go = [&](auto Rc) {
+    constexpr int R = decltype(Rc)::value;
+    launch(k_dense_sym_apply<R>, p->dense.nchunks, 0, p->stream, p->dense.packed, p->dense.chunks, C.r, N, p->dense.lda,
+           p->dense.pd, p->dense.pt, gate);
+    return launch(k_dense_sym_finish<R>, dim3(nT, 4), 0, p->stream, p->dense.pd, p->dense.pt, p->dense.chunk_first, nT, N,
+                  p->dense.lda, C.x, gate);
+  };
+  switch (p->r) {  // (these two kernels know r alone)
+    case 2: CHK(go(Int<2>{})); break;
+    case 3: CHK(go(Int<3>{})); break;
+    case 4: CHK(go(Int<4>{})); break;
+    case 5: CHK(go(Int<5>{})); break;
+    case 6: CHK(go(Int<6>{})); break;
+    default: return fail(DPGO_ERR_UNSUPPORTED, "unsupported r");
   }
   HIPC(hipGetLastError());
   return DPGO_OK;
+}
+
+// f(kernel, Q in the storage it reads, pre-smoothed iterate, prolongation blocks, where the residual is kept) for the level-0
+// restriction: the cycle's fp32 copies (operators and vectors, or -- A/B, DPGO_ML_VECTOR_BITS=64 -- operators only), else the
+// symmetric copy of Q when the tCG-step kernel reads it, else Q at the handle's split
+template <int D, int R, class F>
+int dispatch_restrict0(const dpgo_problem_s* p, F&& f) {
+  auto& L = p->ml[0];
+  double* res_out = p->ml_use_ap() ? L.res1.get() : nullptr;
+  if (p->ml_vec32_active()) return f(k_ml_restrict<D, R, 1, BsrSymDev32, float, float>, p->sym.dev32(), L.x1f, L.Pb32, L.res1f);
+  if (p->ml_ops32_active()) return f(k_ml_restrict<D, R, 1, BsrSymDev32, float, double>, p->sym.dev32(), L.x1, L.Pb32, res_out);
+  if (p->tcg_sym) return f(k_ml_restrict<D, R, 1, BsrSymDev>, p->sym.dev(), L.x1, L.Pb, res_out);
+  return dispatch_split(p->split, [&](auto Sc) { return f(k_ml_restrict<D, R, decltype(Sc)::value>, p->Q.dev(), L.x1, L.Pb, res_out); });
 }
 
 // Level-0 restriction of the cycle: rc = P^T (r - A x1) into ml[1].r (+ the residual itself for k_ml_post_ap).  Graph
@@ -1023,51 +1026,45 @@ int launch_ml_restrict0(dpgo_problem_s* p, const double* r, const DevState* gate
     stop.hflag = p->hflag;
     stop.gen = p->gen;
   }
-  float* rc32 = (C.k == 0 && p->coarse32_active()) ? reinterpret_cast<float*>(C.r.get()) : (float*)nullptr;
-  double* res_out = p->ml_use_ap() ? L.res1 : nullptr;
-  const double* dnext = C.k ? C.dinv : (const double*)nullptr;
-  if (p->ml_vec32_active()) {  // ... its fp32 copy (and the prolongation's), the cycle's internal vectors in fp32 as well
-    DISPATCH(p->d, p->r, hipLaunchKernelGGL((k_ml_restrict<D, R, 1, BsrSymDev32, float, float>), dim3(g0), dim3(kBlock), 0,
-                                            p->stream, p->sym.dev32(), L.x1f, r, L.Pb32, p->ml_shift, L.k, C.r, rc32, dnext,
-                                            p->ml_omega, C.x1, gate, L.n, L.res1f, L.tbuf, L.seg_info, stop));
-  } else if (p->ml_ops32_active()) {  // (A/B: fp32 operator copies, fp64 vectors -- DPGO_ML_VECTOR_BITS=64)
-    DISPATCH(p->d, p->r, hipLaunchKernelGGL((k_ml_restrict<D, R, 1, BsrSymDev32, float, double>), dim3(g0), dim3(kBlock), 0,
-                                            p->stream, p->sym.dev32(), L.x1, r, L.Pb32, p->ml_shift, L.k, C.r, rc32, dnext,
-                                            p->ml_omega, C.x1, gate, L.n, res_out, L.tbuf, L.seg_info, stop));
-  } else if (p->tcg_sym) {  // level 0 reads Q: the symmetric copy when the tCG-step kernel does
-    DISPATCH(p->d, p->r, hipLaunchKernelGGL((k_ml_restrict<D, R, 1, BsrSymDev>), dim3(g0), dim3(kBlock), 0, p->stream,
-                                            p->sym.dev(), L.x1.get(), r, L.Pb.get(), p->ml_shift, L.k, C.r, rc32, dnext, p->ml_omega,
-                                            C.x1, gate, L.n, res_out, L.tbuf, L.seg_info, stop));
-  } else {
-    DISPATCH(p->d, p->r, LAUNCH_SPLIT(p, k_ml_restrict, g0, p->Q.dev(), L.x1.get(), r, L.Pb.get(), p->ml_shift, L.k, C.r, rc32, dnext,
-                                      p->ml_omega, C.x1, gate, L.n, res_out, L.tbuf, L.seg_info, stop));
-  }
+  float* rc32 = (C.k == 0 && p->coarse32_active()) ? reinterpret_cast<float*>(C.r.get()) : nullptr;
+  const double* dnext = C.k ? C.dinv : nullptr;
+  CHK(dispatch_dr(p->d, p->r, [&](auto Dc, auto Rc) {
+    constexpr int D = decltype(Dc)::value, R = decltype(Rc)::value;
+    return dispatch_restrict0<D, R>(p, [&](auto kernel, const auto& A, const auto& x1, const auto& Pb, const auto& res_out) {
+      return launch(kernel, g0, 0, p->stream, A, x1, r, Pb, p->ml_shift, L.k, C.r, rc32, dnext, p->ml_omega, C.x1, gate, L.n,
+                    res_out, L.tbuf, L.seg_info, stop);
+    });
+  }));
   if (L.graph)
-    DISPATCH(p->d, p->r, hipLaunchKernelGGL((k_ml_agg_sum<D, R>), dim3(std::min(C.n, kMaxGrid)), dim3(kBlock), 0, p->stream,
-                                            L.tbuf, L.seg_ptr, C.n, C.r, rc32, gate));
+    CHK(dispatch_dr(p->d, p->r, [&](auto D, auto R) {
+      return launch(k_ml_agg_sum<D, R>, std::min(C.n, kMaxGrid), 0, p->stream, L.tbuf, L.seg_ptr, C.n, C.r, rc32, gate);
+    }));
   HIPC(hipGetLastError());
   return DPGO_OK;
 }
 
-// Level-0 post-smoothing of a two-level hierarchy through A P (k_ml_post_ap).
-int launch_ml_post_ap(dpgo_problem_s* p, const double* Xdev, const double* r, double* z, double* pout, const DevState* gate) {
+// f(kernel, A P, kept residual, prolongation blocks) for the level-0 post-smoothing through A P: the fp32 copies (and beside
+// them the fp32 or the fp64 residual) at one pose per D+1 lanes, the fp64 originals at the handle's split
+template <int D, int R, class F>
+int dispatch_post_ap(const dpgo_problem_s* p, F&& f) {
   auto& L0 = p->ml[0];
   if (p->ml_ops32_active()) {
     const BsrDev32 ap32{L0.AP.rowptr, L0.AP.colidx, L0.AP32};
-    if (p->ml_vec32_active()) {
-      DISPATCH(p->d, p->r, hipLaunchKernelGGL((k_ml_post_ap<D, R, 1, float, float>), dim3(p->grid_post()), dim3(kBlock), 0,
-                                              p->stream, ap32, Xdev, r, L0.res1f, p->ml[1].x, L0.Pb32, L0.agg(), p->dinv,
-                                              p->ml_omega, z, pout, gate, p->n));
-    } else {
-      DISPATCH(p->d, p->r, hipLaunchKernelGGL((k_ml_post_ap<D, R, 1, float, double>), dim3(p->grid_post()), dim3(kBlock), 0,
-                                              p->stream, ap32, Xdev, r, L0.res1, p->ml[1].x, L0.Pb32, L0.agg(), p->dinv,
-                                              p->ml_omega, z, pout, gate, p->n));
-    }
-    HIPC(hipGetLastError());
-    return DPGO_OK;
+    if (p->ml_vec32_active()) return f(k_ml_post_ap<D, R, 1, float, float>, ap32, L0.res1f, L0.Pb32);
+    return f(k_ml_post_ap<D, R, 1, float, double>, ap32, L0.res1, L0.Pb32);
   }
-  DISPATCH(p->d, p->r, LAUNCH_SPLIT(p, k_ml_post_ap, p->grid_post(), L0.AP.dev(), Xdev, r, L0.res1.get(), p->ml[1].x, L0.Pb.get(),
-                                    L0.agg(), p->dinv, p->ml_omega, z, pout, gate, p->n));
+  return dispatch_split(p->split, [&](auto Sc) { return f(k_ml_post_ap<D, R, decltype(Sc)::value>, L0.AP.dev(), L0.res1, L0.Pb); });
+}
+
+// Level-0 post-smoothing of a two-level hierarchy through A P (k_ml_post_ap).
+int launch_ml_post_ap(dpgo_problem_s* p, const double* Xdev, const double* r, double* z, double* pout, const DevState* gate) {
+  CHK(dispatch_dr(p->d, p->r, [&](auto Dc, auto Rc) {
+    constexpr int D = decltype(Dc)::value, R = decltype(Rc)::value;
+    return dispatch_post_ap<D, R>(p, [&](auto kernel, const auto& AP, const auto& res1, const auto& Pb) {
+      return launch(kernel, p->grid_post(), 0, p->stream, AP, Xdev, r, res1, p->ml[1].x, Pb, p->ml[0].agg(), p->dinv,
+                    p->ml_omega, z, pout, gate, p->n);
+    });
+  }));
   HIPC(hipGetLastError());
   return DPGO_OK;
 }
@@ -1079,34 +1076,23 @@ int launch_ml_tail(dpgo_problem_s* p, const double* Xdev, const double* r, doubl
   const int nl = (int)p->ml.size();
   // the dense level reads its right-hand side in the precision its inverse is stored in (same buffer)
   auto rc32_of = [&](const dpgo_problem_s::MlLevel& C) {
-    return (C.k == 0 && p->coarse32_active()) ? reinterpret_cast<float*>(C.r.get()) : (float*)nullptr;
+    return (C.k == 0 && p->coarse32_active()) ? reinterpret_cast<float*>(C.r.get()) : nullptr;
   };
   auto A_of = [&](int l) { return l == 0 ? p->Q.dev() : p->ml[l].A.dev(); };
   auto r_of = [&](int l) { return l == 0 ? r : (const double*)p->ml[l].r; };
   int g0 = p->grid_restrict();  // grid of the level-0 launches: restriction first, post-smoothing later
   auto grid_of = [&](const dpgo_problem_s::MlLevel& L) {
-    if (&L == &p->ml[0]) return g0;
-    const int P = ml_tile(p->b, L.split);
-    return std::max(1, std::min(kMaxGrid, (L.n + P - 1) / P));
+    return &L == &p->ml[0] ? g0 : std::min(kMaxGrid, pose_tiles(L.n, p->b, L.split));
   };
-#define ML_SPLIT_LAUNCH(L, KERNEL, ...)                                                                  \
-  do {                                                                                                   \
-    const int g_ = grid_of(L);                                                                           \
-    if ((L).split == 4)                                                                                  \
-      hipLaunchKernelGGL((KERNEL<D, R, 4>), dim3(g_), dim3(kBlock), 0, p->stream, __VA_ARGS__);          \
-    else if ((L).split == 2)                                                                             \
-      hipLaunchKernelGGL((KERNEL<D, R, 2>), dim3(g_), dim3(kBlock), 0, p->stream, __VA_ARGS__);          \
-    else                                                                                                 \
-      hipLaunchKernelGGL((KERNEL<D, R, 1>), dim3(g_), dim3(kBlock), 0, p->stream, __VA_ARGS__);          \
-  } while (0)
   const bool ap = p->ml_use_ap();  // two levels: the residual after pre-smoothing is kept, the dense level hands over xc
   CHK(launch_ml_restrict0(p, r, gate, g0, stop_check));
   for (int l = 1; l + 1 < nl; ++l) {  // down
     auto& L = p->ml[l];
     auto& C = p->ml[l + 1];
-    DISPATCH(p->d, p->r, ML_SPLIT_LAUNCH(L, k_ml_restrict, A_of(l), L.x1.get(), r_of(l), L.Pb.get(), 0.0, L.k, C.r, rc32_of(C),
-                                         C.k ? C.dinv : (const double*)nullptr, p->ml_omega, C.x1, gate, L.n,
-                                         (double*)nullptr, (double*)nullptr, (const int32_t*)nullptr));
+    CHK(dispatch_drs(p->d, p->r, L.split, [&](auto D, auto R, auto SPLIT) {
+      return launch(k_ml_restrict<D, R, SPLIT>, grid_of(L), 0, p->stream, A_of(l), L.x1, r_of(l), L.Pb, 0.0, L.k, C.r, rc32_of(C),
+                    C.k ? C.dinv : nullptr, p->ml_omega, C.x1, gate, L.n, nullptr, nullptr, nullptr, TcgStopCheck());
+    }));
   }
   {  // dense level (+ prolongation unless the level above does it itself)
     auto& L = p->ml[nl - 2];
@@ -1121,26 +1107,26 @@ int launch_ml_tail(dpgo_problem_s* p, const double* Xdev, const double* r, doubl
   for (int l = nl - 2; l >= 1; --l) {  // up
     auto& L = p->ml[l];
     auto& F = p->ml[l - 1];
-    DISPATCH(p->d, p->r, ML_SPLIT_LAUNCH(L, k_ml_post_mid, L.A.dev(), L.x, L.r, L.dinv, p->ml_omega, F.x1, F.Pb, F.k, F.x,
-                                         F.n, gate, L.n));
+    CHK(dispatch_drs(p->d, p->r, L.split, [&](auto D, auto R, auto SPLIT) {
+      return launch(k_ml_post_mid<D, R, SPLIT>, grid_of(L), 0, p->stream, L.A.dev(), L.x, L.r, L.dinv, p->ml_omega, F.x1, F.Pb,
+                    F.k, F.x, F.n, gate, L.n);
+    }));
   }
-  if (p->tcg_sym) {
-    DISPATCH(p->d, p->r, hipLaunchKernelGGL((k_ml_post<D, R, 1, BsrSymDev>), dim3(g0), dim3(kBlock), 0, p->stream,
-                                            p->sym.dev(), Xdev, p->ml[0].x, r, p->dinv, p->ml_omega, p->ml_shift, z, pout,
-                                            gate, p->n));
-  } else {
-    DISPATCH(p->d, p->r, ML_SPLIT_LAUNCH(p->ml[0], k_ml_post, p->Q.dev(), Xdev, p->ml[0].x, r, p->dinv, p->ml_omega,
-                                         p->ml_shift, z, pout, gate, p->n));
-  }
-#undef ML_SPLIT_LAUNCH
+  CHK(dispatch_drs(p->d, p->r, p->ml[0].split, [&](auto D, auto R, auto SPLIT) {
+    auto go = [&](auto kernel, const auto& Q) {  // level 0 reads Q: the symmetric copy when the tCG-step kernel does
+      return launch(kernel, g0, 0, p->stream, Q, Xdev, p->ml[0].x, r, p->dinv, p->ml_omega, p->ml_shift, z, pout, gate, p->n);
+    };
+    return p->tcg_sym ? go(k_ml_post<D, R, 1, BsrSymDev>, p->sym.dev()) : go(k_ml_post<D, R, SPLIT>, p->Q.dev());
+  }));
   HIPC(hipGetLastError());
   return DPGO_OK;
 }
 
 // Stand-alone application z = proj_X(M^-1 v) (QuadraticProblem::PreConditioner outside the tCG loop).
 int launch_ml_apply(dpgo_problem_s* p, const double* Xdev, const double* v, double* z) {
-  DISPATCH(p->d, p->r, hipLaunchKernelGGL((k_ml_presmooth<D, R>), dim3(p->grid()), dim3(kBlock), 0, p->stream, v, p->dinv,
-                                          p->ml_omega, p->ml[0].x1, (const DevState*)nullptr, p->n));
+  CHK(dispatch_dr(p->d, p->r, [&](auto D, auto R) {
+    return launch(k_ml_presmooth<D, R>, p->grid(), 0, p->stream, v, p->dinv, p->ml_omega, p->ml[0].x1, nullptr, p->n);
+  }));
   HIPC(hipGetLastError());
   // (outside the tCG loop the cycle reads the fp64 originals: its pre-smoothed iterate was written in fp64 just above)
   p->ml_ops32_suspend = true;
@@ -1370,7 +1356,7 @@ int dpgo_dense_spd_inverse(int N, const double* A_host, double* Ainv_host, int d
   CHK(Rx.alloc((size_t)lda * kNB));
   HIPC(hipMemset(M, 0, sizeof(double) * (size_t)lda * lda));
   HIPC(hipMemcpy2D(M, sizeof(double) * lda, A_host, sizeof(double) * N, sizeof(double) * N, N, hipMemcpyHostToDevice));
-  hipLaunchKernelGGL(k_dense_pad_identity, dim3(1), dim3(kBlock), 0, (hipStream_t) nullptr, M, lda, N);
+  launch(k_dense_pad_identity, 1, 0, nullptr, M, lda, N);
   CHK(dense_spd_inverse(nullptr, M, lda, W, Rx, use_mfma != 0));
   HIPC(hipMemcpy2D(Ainv_host, sizeof(double) * N, M, sizeof(double) * lda, sizeof(double) * N, N, hipMemcpyDeviceToHost));
   return DPGO_OK;

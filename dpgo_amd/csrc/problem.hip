@@ -49,9 +49,9 @@ int build_dinv(dpgo_problem_s* p, double shift) {
   if (p->dinv_shift == shift) return DPGO_OK;
   const int g = (p->n + kBlock - 1) / kBlock;
   if (p->d == 2)
-    hipLaunchKernelGGL(k_build_dinv<2>, dim3(g), dim3(kBlock), 0, p->stream, p->Q.dev(), shift, p->dinv, p->n);
+    launch(k_build_dinv<2>, g, 0, p->stream, p->Q.dev(), shift, p->dinv, p->n);
   else
-    hipLaunchKernelGGL(k_build_dinv<3>, dim3(g), dim3(kBlock), 0, p->stream, p->Q.dev(), shift, p->dinv, p->n);
+    launch(k_build_dinv<3>, g, 0, p->stream, p->Q.dev(), shift, p->dinv, p->n);
   HIPC(hipGetLastError());
   p->dinv_shift = shift;
   return DPGO_OK;
@@ -188,13 +188,11 @@ int sym_ensure(dpgo_problem_s* p, bool* usable) {
     const int g = (int)std::min<size_t>(kMaxGrid, (total + kBlock - 1) / kBlock);
     HIPC(hipMemsetAsync(S.flag, 0, sizeof(int), p->stream));
     if (p->d == 2) {
-      hipLaunchKernelGGL(k_sym_refresh<2>, dim3(g), dim3(kBlock), 0, p->stream, p->Q.vals, S.usrc, S.uvalsT, S.nu);
-      hipLaunchKernelGGL(k_sym_check<2>, dim3(g), dim3(kBlock), 0, p->stream, p->Q.vals, S.lsrc, S.lslot, S.uvalsT, S.nl,
-                         S.flag);
+      launch(k_sym_refresh<2>, g, 0, p->stream, p->Q.vals, S.usrc, S.uvalsT, S.nu);
+      launch(k_sym_check<2>, g, 0, p->stream, p->Q.vals, S.lsrc, S.lslot, S.uvalsT, S.nl, S.flag);
     } else {
-      hipLaunchKernelGGL(k_sym_refresh<3>, dim3(g), dim3(kBlock), 0, p->stream, p->Q.vals, S.usrc, S.uvalsT, S.nu);
-      hipLaunchKernelGGL(k_sym_check<3>, dim3(g), dim3(kBlock), 0, p->stream, p->Q.vals, S.lsrc, S.lslot, S.uvalsT, S.nl,
-                         S.flag);
+      launch(k_sym_refresh<3>, g, 0, p->stream, p->Q.vals, S.usrc, S.uvalsT, S.nu);
+      launch(k_sym_check<3>, g, 0, p->stream, p->Q.vals, S.lsrc, S.lslot, S.uvalsT, S.nl, S.flag);
     }
     HIPC(hipGetLastError());
     int bad = 0;
@@ -208,16 +206,12 @@ int sym_ensure(dpgo_problem_s* p, bool* usable) {
   return DPGO_OK;
 }
 
-// ---- kernel launch helpers (templated on D, R through DISPATCH) ----
+// ---- kernel launch helpers (the <D, R> instance through dispatch_dr) ----
 int launch_spmm_sym(dpgo_problem_s* p, const BsrSymDev& M, const double* V, const double* Gadd, double* OUT) {
   const int g = p->grid_spmm_sym();
-  DISPATCH(p->d, p->r,
-           {
-             if (p->want_stream_nt())
-               hipLaunchKernelGGL((k_spmm_sym<D, R, 1>), dim3(g), dim3(kBlock), 0, p->stream, M, V, Gadd, OUT, p->n);
-             else
-               hipLaunchKernelGGL((k_spmm_sym<D, R, 0>), dim3(g), dim3(kBlock), 0, p->stream, M, V, Gadd, OUT, p->n);
-           });
+  CHK(dispatch_dr(p->d, p->r, [&](auto D, auto R) {
+    return launch(p->want_stream_nt() ? k_spmm_sym<D, R, 1> : k_spmm_sym<D, R, 0>, g, 0, p->stream, M, V, Gadd, OUT, p->n);
+  }));
   HIPC(hipGetLastError());
   return DPGO_OK;
 }
@@ -225,12 +219,10 @@ int launch_spmm_sym(dpgo_problem_s* p, const BsrSymDev& M, const double* V, cons
 // the plain kernel on a view of a matrix: the tail of launch_spmm, and the rotating probe's private copies of Q
 int launch_spmm_view(dpgo_problem_s* p, const BsrDev& M, const double* V, const double* Gadd, double* OUT, int rows, int g,
                      bool stream_nt) {
-  DISPATCH(p->d, p->r, {
-    if (stream_nt)
-      hipLaunchKernelGGL((k_spmm<D, R, 1, 1>), dim3(g), dim3(kBlock), 0, p->stream, M, V, Gadd, OUT, rows);
-    else
-      LAUNCH_SPLIT(p, k_spmm, g, M, V, Gadd, OUT, rows);
-  });
+  CHK(dispatch_drs(p->d, p->r, p->split, [&](auto D, auto R, auto SPLIT) {
+    if (stream_nt) return launch(k_spmm<D, R, 1, 1>, g, 0, p->stream, M, V, Gadd, OUT, rows);
+    return launch(k_spmm<D, R, SPLIT>, g, 0, p->stream, M, V, Gadd, OUT, rows);
+  }));
   HIPC(hipGetLastError());
   return DPGO_OK;
 }
@@ -243,10 +235,7 @@ int launch_spmm(dpgo_problem_s* p, const Bsr& M, const double* V, const double* 
   }
   const int rows = nrows >= 0 ? nrows : p->n;
   int g = p->grid_spmm();
-  if (nrows >= 0) {  // rectangular operator with its own row count (restriction)
-    const int P = (64 / (p->b * p->split)) * kWaves;
-    g = std::max(1, std::min(kMaxGrid, (rows + P - 1) / P));
-  }
+  if (nrows >= 0) g = std::min(kMaxGrid, pose_tiles(rows, p->b, p->split));  // rectangular operator with its own row count (restriction)
   return launch_spmm_view(p, M.dev(), V, Gadd, OUT, rows, g, p->want_stream_nt() && p->split == 1 && &M == &p->Q);
 }
 
@@ -259,29 +248,26 @@ bool outer_sym_enabled() {  // tuning knob: DPGO_OUTER_SYM=0 keeps the outer ite
 int launch_grad(dpgo_problem_s* p, const double* X, double* RG, double* S, double* EG,
                 const DevState* st, bool sym) {
   const double* Gm = p->has_G ? p->G : nullptr;
-  if (sym && p->split == 1) {
-    p->nb_grad = p->grid_outer_sym();
-    DISPATCH(p->d, p->r, hipLaunchKernelGGL((k_grad<D, R, 1, BsrSymDev>), dim3(p->nb_grad), dim3(kBlock), 0, p->stream,
-                                            p->sym.dev(), X, Gm, RG, S, EG, p->pE(), st, p->n));
-  } else {
-    p->nb_grad = p->grid_s();
-    DISPATCH(p->d, p->r, LAUNCH_SPLIT(p, k_grad, p->nb_grad, p->Q.dev(), X, Gm, RG, S, EG, p->pE(), st, p->n));
-  }
+  sym = sym && p->split == 1;
+  p->nb_grad = sym ? p->grid_outer_sym() : p->grid_s();
+  CHK(dispatch_drs(p->d, p->r, p->split, [&](auto D, auto R, auto SPLIT) {
+    if (sym) return launch(k_grad<D, R, 1, BsrSymDev>, p->nb_grad, 0, p->stream, p->sym.dev(), X, Gm, RG, S, EG, p->pE(), st, p->n);
+    return launch(k_grad<D, R, SPLIT>, p->nb_grad, 0, p->stream, p->Q.dev(), X, Gm, RG, S, EG, p->pE(), st, p->n);
+  }));
   HIPC(hipGetLastError());
   return DPGO_OK;
 }
 
 int launch_hess(dpgo_problem_s* p, const double* X, const double* S, const double* V, const double* Gdot,
                 double* HV, double* partials, const DevState* st, int check_tcg, bool sym) {
-  if (sym && p->split == 1) {
-    p->nb_hess = p->grid_outer_sym();
-    DISPATCH(p->d, p->r, hipLaunchKernelGGL((k_hess<D, R, 1, BsrSymDev>), dim3(p->nb_hess), dim3(kBlock), 0, p->stream,
-                                            p->sym.dev(), X, S, V, Gdot, HV, partials, st, check_tcg, p->n));
-  } else {
-    p->nb_hess = p->grid_s();
-    DISPATCH(p->d, p->r,
-             LAUNCH_SPLIT(p, k_hess, p->nb_hess, p->Q.dev(), X, S, V, Gdot, HV, partials, st, check_tcg, p->n));
-  }
+  sym = sym && p->split == 1;
+  p->nb_hess = sym ? p->grid_outer_sym() : p->grid_s();
+  CHK(dispatch_drs(p->d, p->r, p->split, [&](auto D, auto R, auto SPLIT) {
+    if (sym)
+      return launch(k_hess<D, R, 1, BsrSymDev>, p->nb_hess, 0, p->stream, p->sym.dev(), X, S, V, Gdot, HV, partials, st,
+                    check_tcg, p->n);
+    return launch(k_hess<D, R, SPLIT>, p->nb_hess, 0, p->stream, p->Q.dev(), X, S, V, Gdot, HV, partials, st, check_tcg, p->n);
+  }));
   HIPC(hipGetLastError());
   return DPGO_OK;
 }
@@ -289,10 +275,10 @@ int launch_hess(dpgo_problem_s* p, const double* X, const double* S, const doubl
 int launch_retract(dpgo_problem_s* p, const double* X, const double* eta, double scale, double* X2,
                    const DevState* st) {
   // (no partial sums, 50 VGPRs: not bound to the update kernel's grid -- at most DPGO_GRID_RETRACT workgroups, 1 024 by default; 512 / 1 024 / 1 563 measured 259.4 / 261.4 / 260.0 it/s)
-  const int tiles_r = std::max(1, (p->n + (64 / p->b) * kWaves - 1) / ((64 / p->b) * kWaves));
-  const int gr = std::min(tiles_r, options().grid_retract > 0 ? options().grid_retract : kMaxGrid);
-  DISPATCH(p->d, p->r, hipLaunchKernelGGL((k_retract<D, R>), dim3(gr), dim3(kBlock), 0, p->stream, X, eta,
-                                          scale, X2, st, p->n));
+  const int gr = std::min(pose_tiles(p->n, p->b), options().grid_retract > 0 ? options().grid_retract : kMaxGrid);
+  CHK(dispatch_dr(p->d, p->r, [&](auto D, auto R) {
+    return launch(k_retract<D, R>, gr, 0, p->stream, X, eta, scale, X2, st, p->n);
+  }));
   HIPC(hipGetLastError());
   return DPGO_OK;
 }
@@ -300,25 +286,26 @@ int launch_retract(dpgo_problem_s* p, const double* X, const double* eta, double
 int launch_rtr_update(dpgo_problem_s* p) {
   // (the partial sums of the last k_grad / k_hess launch: their grids, launch_grad / launch_hess)
   const int ge = p->nb_grad > 0 ? p->nb_grad : p->grid_s(), gh = p->nb_hess > 0 ? p->nb_hess : p->grid_s();
-  DISPATCH(p->d, p->r,
-           hipLaunchKernelGGL((k_rtr_update<D, R>), dim3(p->grid_flat()), dim3(kBlock), 0, p->stream, p->x1, p->x2,
-                              p->g1, p->g2, p->S1, p->S2, p->pE(), ge, p->pH(), gh, p->dstate + p->cur,
-                              p->dstate + (p->cur ^ 1), p->n));
+  CHK(dispatch_dr(p->d, p->r, [&](auto D, auto R) {
+    return launch(k_rtr_update<D, R>, p->grid_flat(), 0, p->stream, p->x1, p->x2, p->g1, p->g2, p->S1, p->S2, p->pE(), ge,
+                  p->pH(), gh, p->dstate + p->cur, p->dstate + (p->cur ^ 1), p->n);
+  }));
   HIPC(hipGetLastError());
   p->cur ^= 1;
   return DPGO_OK;
 }
 
 int launch_precond(dpgo_problem_s* p, const double* X, const double* V, const double* dinv, double* Z) {
-  DISPATCH(p->d, p->r, hipLaunchKernelGGL((k_precond<D, R>), dim3(p->grid()), dim3(kBlock), 0, p->stream, X, V,
-                                          dinv, Z, p->n));
+  CHK(dispatch_dr(p->d, p->r, [&](auto D, auto R) {
+    return launch(k_precond<D, R>, p->grid(), 0, p->stream, X, V, dinv, Z, p->n);
+  }));
   HIPC(hipGetLastError());
   return DPGO_OK;
 }
 
 int launch_rtr_begin(dpgo_problem_s* p, double tol, double Delta0, double Dmax, int max_inner, int tiny) {
-  hipLaunchKernelGGL(k_rtr_begin, dim3(1), dim3(kBlock), 0, p->stream, p->pE(), p->nb_grad > 0 ? p->nb_grad : p->grid_s(), p->dstate, tol, Delta0,
-                     Dmax, max_inner, tiny);
+  launch(k_rtr_begin, 1, 0, p->stream, p->pE(), p->nb_grad > 0 ? p->nb_grad : p->grid_s(), p->dstate, tol, Delta0, Dmax,
+         max_inner, tiny);
   HIPC(hipGetLastError());
   p->cur = 0;
   return DPGO_OK;

@@ -10,25 +10,24 @@ int launch_tcg_update(dpgo_problem_s* p, const double* dinv, int first, double* 
   double* zt = z_out ? z_out : p->z;
   // (the pre-smoothed iterate of a cycle that keeps its internal vectors in fp32 goes to that buffer instead)
   float* z32 = (ml_omega > 0.0 && !p->ml.empty() && z_out == p->ml[0].x1 && p->ml_vec32_active()) ? p->ml[0].x1f : nullptr;
-  DISPATCH(p->d, p->r, {
+  CHK(dispatch_dr(p->d, p->r, [&](auto Dc, auto Rc) {
+    constexpr int D = decltype(Dc)::value, R = decltype(Rc)::value;
+    // (the span kernels end in the fp32 output, the generic one has none)
+    auto go = [&](auto kernel, auto... z32_arg) {
+      return launch(kernel, g, 0, p->stream, p->x1, p->g1, dinv, p->delta, p->Hd, p->eta, p->rr, zt, p->pA(), p->grid_s(),
+                    p->pB(), p->dstate + p->cur, p->dstate + (p->cur ^ 1), first, p->n, p->hflag, p->gen, ml_omega,
+                    z32_arg...);
+    };
     if constexpr (Span<D, R, 1>::kOk) {
-      if (ml_mode)  // (the instance compiled for the multilevel mode: 3 waves per SIMD)
-        hipLaunchKernelGGL((k_tcg_update_span<D, R, 1>), dim3(g), dim3(kBlock), 0, p->stream, p->x1, p->g1, dinv, p->delta,
-                           p->Hd, p->eta, p->rr, zt, p->pA(), p->grid_s(), p->pB(), p->dstate + p->cur,
-                           p->dstate + (p->cur ^ 1), first, p->n, p->hflag, p->gen, ml_omega, z32);
-      else
-        hipLaunchKernelGGL((k_tcg_update_span<D, R, 0>), dim3(g), dim3(kBlock), 0, p->stream, p->x1, p->g1, dinv, p->delta,
-                           p->Hd, p->eta, p->rr, zt, p->pA(), p->grid_s(), p->pB(), p->dstate + p->cur,
-                           p->dstate + (p->cur ^ 1), first, p->n, p->hflag, p->gen, ml_omega, z32);
+      // (its own instance for the multilevel mode: 3 waves per SIMD)
+      return go(ml_mode ? k_tcg_update_span<D, R, 1> : k_tcg_update_span<D, R, 0>, z32);
     } else {
       // (odd tile size: the generic kernel has no fp32 output -- resolve_tcg_storage keeps such blocks off the symmetric
       // storage, hence off the cycle's fp32 vectors; a state that says otherwise is refused instead of dropping z32)
       if (z32) return fail(DPGO_ERR_STATE, "fp32 cycle vectors need the span kernels (even pose tile size)");
-      hipLaunchKernelGGL((k_tcg_update<D, R>), dim3(g), dim3(kBlock), 0, p->stream, p->x1, p->g1, dinv, p->delta,
-                         p->Hd, p->eta, p->rr, zt, p->pA(), p->grid_s(), p->pB(), p->dstate + p->cur,
-                         p->dstate + (p->cur ^ 1), first, p->n, p->hflag, p->gen, ml_omega);
+      return go(k_tcg_update<D, R>);
     }
-  });
+  }));
   HIPC(hipGetLastError());
   p->cur ^= 1;
   return DPGO_OK;
@@ -36,32 +35,27 @@ int launch_tcg_update(dpgo_problem_s* p, const double* dinv, int first, double* 
 
 // fused direction update + Riemannian Hessian-vector product (one tCG step)
 // the tCG-step kernel: span variant whenever the pose tile size is even (all 3-D cases)
-#define LAUNCH_TCG_HESS(p, SIN, SOUT, FIRST, HFLAG, GEN)                                                          \
-  do {                                                                                                            \
-    if constexpr (Span<D, R, 1>::kOk) {                                                                           \
-      if ((p)->tcg_sym && (p)->stream_nt)                                                                         \
-        hipLaunchKernelGGL((k_tcg_hess_sym<D, R, 1>), dim3((p)->grid_s()), dim3(kBlock), 0, (p)->stream,          \
-                           (p)->sym.dev(), (p)->x1, (p)->S1, (p)->z, (p)->delta, (p)->Hd, (p)->pB(), (p)->nb_zr(), \
-                           (p)->pA(), SIN, SOUT, FIRST, (p)->n, HFLAG, GEN);                                      \
-      else if ((p)->tcg_sym)                                                                                      \
-        hipLaunchKernelGGL((k_tcg_hess_sym<D, R, 0>), dim3((p)->grid_s()), dim3(kBlock), 0, (p)->stream,          \
-                           (p)->sym.dev(), (p)->x1, (p)->S1, (p)->z, (p)->delta, (p)->Hd, (p)->pB(), (p)->nb_zr(), \
-                           (p)->pA(), SIN, SOUT, FIRST, (p)->n, HFLAG, GEN);                                      \
-      else if ((p)->stream_nt && (p)->split == 1)                                                                 \
-        hipLaunchKernelGGL((k_tcg_hess_span<D, R, 1, 1>), dim3((p)->grid_s()), dim3(kBlock), 0, (p)->stream,      \
-                           (p)->Q.dev(), (p)->x1, (p)->S1, (p)->z, (p)->delta, (p)->Hd, (p)->pB(), (p)->nb_zr(),   \
-                           (p)->pA(), SIN, SOUT, FIRST, (p)->n, HFLAG, GEN);                                      \
-      else                                                                                                        \
-      LAUNCH_SPLIT(p, k_tcg_hess_span, (p)->grid_s(), (p)->Q.dev(), (p)->x1, (p)->S1, (p)->z, (p)->delta, (p)->Hd, \
-                   (p)->pB(), (p)->nb_zr(), (p)->pA(), SIN, SOUT, FIRST, (p)->n, HFLAG, GEN);                   \
-    } else                                                                                                        \
-      LAUNCH_SPLIT(p, k_tcg_hess, (p)->grid_s(), (p)->Q.dev(), (p)->x1, (p)->S1, (p)->z, (p)->delta, (p)->Hd,      \
-                   (p)->pB(), (p)->nb_zr(), (p)->pA(), SIN, SOUT, FIRST, (p)->n, HFLAG, GEN);                   \
-  } while (0)
+// f(kernel, Q in the storage that kernel reads) for the instance this handle's state selects
+template <int D, int R, class F>
+int dispatch_tcg_hess(const dpgo_problem_s* p, F&& f) {
+  if constexpr (Span<D, R, 1>::kOk) {
+    if (p->tcg_sym) return f(p->stream_nt ? k_tcg_hess_sym<D, R, 1> : k_tcg_hess_sym<D, R, 0>, p->sym.dev());
+    if (p->stream_nt && p->split == 1) return f(k_tcg_hess_span<D, R, 1, 1>, p->Q.dev());
+    return dispatch_split(p->split, [&](auto Sc) { return f(k_tcg_hess_span<D, R, decltype(Sc)::value>, p->Q.dev()); });
+  } else {
+    return dispatch_split(p->split, [&](auto Sc) { return f(k_tcg_hess<D, R, decltype(Sc)::value>, p->Q.dev()); });
+  }
+}
 
 int launch_tcg_hess_with(dpgo_problem_s* p, const DevState* sin, DevState* sout, int first, unsigned long long* hflag,
                          unsigned gen) {  // (the state slots and the progress word of the caller's choice: kernel probes)
-  DISPATCH(p->d, p->r, LAUNCH_TCG_HESS(p, sin, sout, first, hflag, gen));
+  CHK(dispatch_dr(p->d, p->r, [&](auto Dc, auto Rc) {
+    constexpr int D = decltype(Dc)::value, R = decltype(Rc)::value;
+    return dispatch_tcg_hess<D, R>(p, [&](auto kernel, const auto& Q) {
+      return launch(kernel, p->grid_s(), 0, p->stream, Q, p->x1, p->S1, p->z, p->delta, p->Hd, p->pB(), p->nb_zr(), p->pA(),
+                    sin, sout, first, p->n, hflag, gen);
+    });
+  }));
   HIPC(hipGetLastError());
   return DPGO_OK;
 }
@@ -71,13 +65,21 @@ int launch_tcg_hess(dpgo_problem_s* p, int first) {
   return DPGO_OK;
 }
 
+// the pose tile size is even: the span kernels (and with them the symmetric storage) exist for this pair
+static bool span_ok(int d, int r) {
+  bool ok = false;
+  (void)dispatch_dr(d, r, [&](auto Dc, auto Rc) {
+    ok = Span<decltype(Dc)::value, decltype(Rc)::value, 1>::kOk;
+    return DPGO_OK;
+  });
+  return ok;
+}
+
 // which storage of Q the tCG-step kernel of the coming launches reads (Q does not change inside a solve)
 int resolve_tcg_storage(dpgo_problem_s* p) {
   p->tcg_sym = false;
   p->stream_nt = p->want_stream_nt();
-  bool span = false;
-  DISPATCH(p->d, p->r, { span = Span<D, R, 1>::kOk; });
-  if (!span || !p->sym_wanted()) return DPGO_OK;
+  if (!span_ok(p->d, p->r) || !p->sym_wanted()) return DPGO_OK;
   bool usable = false;
   CHK(sym_ensure(p, &usable));
   p->tcg_sym = usable;
@@ -130,25 +132,37 @@ void persist_release(dpgo_problem_s* p) {
 bool additive_available(dpgo_problem_s* p) {
   return p->persist && !p->persist_failed_once && additive_plan(p).split != 0;
 }
+// f(Int<SPLIT>{}, Int<MT>{}, additive as std::bool_constant) for the k_rtr_persist<D, R, SPLIT, MT, ADD> layout of a launch:
+// the seven that are compiled -- additive (4, 1), (1, 2), (1, 1); plain (4, 1), (4, 2), (1, 1), (1, 2) -- and the only place that
+// turns (lane groups per pose, tiles per workgroup, additive) into one of them
+template <class F>
+int dispatch_persist(int split, int mt, bool additive, F&& f) {
+  if (additive) {
+    if (split == 4) return f(Int<4>{}, Int<1>{}, std::true_type{});
+    return mt == 2 ? f(Int<1>{}, Int<2>{}, std::true_type{}) : f(Int<1>{}, Int<1>{}, std::true_type{});
+  }
+  if (split == 4) return mt == 1 ? f(Int<4>{}, Int<1>{}, std::false_type{}) : f(Int<4>{}, Int<2>{}, std::false_type{});
+  return mt == 1 ? f(Int<1>{}, Int<1>{}, std::false_type{}) : f(Int<1>{}, Int<2>{}, std::false_type{});
+}
 // LDS of one workgroup (gfx950: 160 KiB per CU; every persistent instance runs one workgroup per CU)
 constexpr size_t kPersistLds = 160 * 1024;
+// hipFuncAttributeMaxDynamicSharedMemorySize of a kernel instance as last raised, per device: one counter per instance
+template <auto Kernel>
+std::atomic<int> g_dynamic_lds_set[kMaxDevices];
 // The additive instance of this layout fits one CU with `na` aggregates: its static LDS (as compiled for the handle's
 // (d, r)) plus the (d+1) rows of A_c^-1 per workgroup, (d+1)^2 na doubles.  With two tiles per workgroup the static part
 // grows with (d+1) r; an instance the compiler could not place is refused here, not at the launch.
 bool additive_lds_fits(const dpgo_problem_s* p, int split, int mt, int na) {
   hipFuncAttributes a{};
-  bool ok = false;
-  auto query = [&]() -> int {
-    DISPATCH(p->d, p->r, {
-      const void* f = split == 4 ? reinterpret_cast<const void*>(&k_rtr_persist<D, R, 4, 1, true>)
-                                 : mt == 2 ? reinterpret_cast<const void*>(&k_rtr_persist<D, R, 1, 2, true>)
-                                           : reinterpret_cast<const void*>(&k_rtr_persist<D, R, 1, 1, true>);
-      ok = hipFuncGetAttributes(&a, f) == hipSuccess;
+  const int rc = dispatch_dr(p->d, p->r, [&](auto Dc, auto Rc) {
+    return dispatch_persist(split, mt, true, [&](auto Sc, auto Mc, auto Ac) {
+      HIPC(hipFuncGetAttributes(&a, reinterpret_cast<const void*>(
+                                        &k_rtr_persist<decltype(Dc)::value, decltype(Rc)::value, decltype(Sc)::value,
+                                                       decltype(Mc)::value, decltype(Ac)::value>)));
+      return DPGO_OK;
     });
-    return DPGO_OK;
-  };
-  if (query() != DPGO_OK || !ok) return false;
-  return a.sharedSizeBytes + sizeof(double) * (size_t)p->b * p->b * na <= kPersistLds;
+  });
+  return rc == DPGO_OK && a.sharedSizeBytes + sizeof(double) * (size_t)p->b * p->b * na <= kPersistLds;
 }
 // `free_slots`: what may be reserved.  Alone on the device (share = 1): the lowest-latency layout that fits (4 lane groups
 // per pose while the tiles fit, then one pose per (d+1) lanes).  Sharing the device with `share` concurrently solved
@@ -170,9 +184,7 @@ PersistGeo persist_geometry(const dpgo_problem_s* p, int free_slots, int share, 
   for (auto& c : cand) {
     if (env_split && c[0] != env_split) continue;
     if (env_mt && c[1] != env_mt) continue;
-    const int P = (64 / (p->b * c[0])) * kWaves;
-    const int tiles = std::max(1, (p->n + P - 1) / P);
-    const int wgs = (tiles + c[1] - 1) / c[1];
+    const int wgs = (pose_tiles(p->n, p->b, c[0]) + c[1] - 1) / c[1];
     const int slots = wgs * persist_slots_per_wg(c[0], c[1]);
     if (wgs > kPersistMax || slots > free_slots) continue;
     const PersistGeo g{c[0], c[1], wgs, slots};
@@ -273,39 +285,28 @@ int launch_rtr_persistent(dpgo_problem_s* p, const dpgo_ropt_params* prm, const 
   const double* Glin = p->has_G ? p->G : nullptr;
   // (static + dynamic LDS of the additive instances can exceed 64 KB: the launch attribute is raised to the largest size
   // any handle of the process has asked of that instantiation on that device)
-#define PERSIST_LAUNCH(SP, MT_, ADD_, LDS_)                                                                           \
-  do {                                                                                                                \
-    if ((LDS_) > 0) { /* the attribute belongs to the instantiation and the device: only ever raised */              \
-      static std::atomic<int> hw_[kMaxDevices];                                                                       \
-      auto& h_ = hw_[p->device % kMaxDevices];                                                                        \
-      if ((int)(LDS_) > h_.load()) {                                                                                  \
-        HIPC(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_rtr_persist<D, R, SP, MT_, ADD_>),                   \
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)(LDS_)));                           \
-        int cur_ = h_.load();                                                                                         \
-        while (cur_ < (int)(LDS_) && !h_.compare_exchange_weak(cur_, (int)(LDS_))) {}                                 \
-      }                                                                                                               \
-    }                                                                                                                 \
-    hipLaunchKernelGGL((k_rtr_persist<D, R, SP, MT_, ADD_>), dim3(p->persist_wgs), dim3(kBlock), LDS_, p->stream,     \
-                       p->Q.dev(), p->x1, Glin, dinv, p->x2, p->eta, p->z, p->pgran, salt, p->dstate, p->pctrl, p->n, \
-                       p->hflag, p->gen, poll, ra, add);                                                              \
-  } while (0)
-  DISPATCH(p->d, p->r, {
-    if (additive && p->persist_split == 4) PERSIST_LAUNCH(4, 1, true, lds);
-    else if (additive && p->persist_mt == 2) PERSIST_LAUNCH(1, 2, true, lds);
-    else if (additive) PERSIST_LAUNCH(1, 1, true, lds);
-    else if (p->persist_split == 4 && p->persist_mt == 1) PERSIST_LAUNCH(4, 1, false, 0);
-    else if (p->persist_split == 4) PERSIST_LAUNCH(4, 2, false, 0);
-    else if (p->persist_mt == 1) PERSIST_LAUNCH(1, 1, false, 0);
-    else PERSIST_LAUNCH(1, 2, false, 0);
-  });
-#undef PERSIST_LAUNCH
+  CHK(dispatch_dr(p->d, p->r, [&](auto Dc, auto Rc) {
+    constexpr int D = decltype(Dc)::value, R = decltype(Rc)::value;
+    return dispatch_persist(p->persist_split, p->persist_mt, additive, [&](auto Sc, auto Mc, auto Ac) {
+      constexpr auto kernel = &k_rtr_persist<D, R, decltype(Sc)::value, decltype(Mc)::value, decltype(Ac)::value>;
+      if (lds > 0) {  // the attribute belongs to the instance and the device: only ever raised
+        auto& set = g_dynamic_lds_set<kernel>[p->device % kMaxDevices];
+        if ((int)lds > set.load()) {
+          HIPC(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+          int cur = set.load();
+          while (cur < (int)lds && !set.compare_exchange_weak(cur, (int)lds)) {}
+        }
+      }
+      return launch(kernel, p->persist_wgs, lds, p->stream, p->Q.dev(), p->x1, Glin, dinv, p->x2, p->eta, p->z, p->pgran, salt,
+                    p->dstate, p->pctrl, p->n, p->hflag, p->gen, poll, ra, add);
+    });
+  }));
   {  // the iterate reaches the caller's X only if the launch completed on every participant (k_persist_commit)
     const size_t count = (size_t)p->n * p->T;
     const int grid = (int)std::min<size_t>(1024, (count + kBlock - 1) / kBlock);
     // (p->cur = 0 below: dstate[0] is the record the solve leaves; the commit kernel also writes it and the control block
     // into the host-coherent copies the caller reads after synchronising)
-    hipLaunchKernelGGL(k_persist_commit, dim3(grid), dim3(kBlock), 0, p->stream, p->dstate, p->pctrl, p->x2, p->x1, count,
-                       p->hstate, p->hctrl);
+    launch(k_persist_commit, grid, 0, p->stream, p->dstate, p->pctrl, p->x2, p->x1, count, p->hstate, p->hctrl);
   }
   HIPC(hipGetLastError());
   p->cur = 0;
@@ -749,69 +750,60 @@ int resident_blocks(K kernel, int* out) {
   *out = std::max(1, std::min(kPartialCap, per_cu * cus));
   return DPGO_OK;
 }
+template <class K>
+int lower_to_resident(K kernel, int* cap) {  // *cap = min(*cap, resident count of `kernel`)
+  int c = 0;
+  CHK(resident_blocks(kernel, &c));
+  *cap = std::min(*cap, c);
+  return DPGO_OK;
+}
 int tune_launch_caps(dpgo_problem_s* p) {
-  DISPATCH(p->d, p->r, {
+  // Which instance each cap is read from -- not always the one a launch then picks; the grids were measured with these:
+  CHK(dispatch_dr(p->d, p->r, [&](auto Dc, auto Rc) {
+    constexpr int D = decltype(Dc)::value, R = decltype(Rc)::value;
     if constexpr (Span<D, R, 1>::kOk) {
-      CHK(resident_blocks((k_tcg_update_span<D, R, 0>), &p->cap_u));
-      CHK(resident_blocks((k_tcg_update_span<D, R, 1>), &p->cap_u_ml));
-      if (p->split == 4)
-        CHK(resident_blocks(k_tcg_hess_span<D, R, 4>, &p->cap_h));
-      else if (p->split == 2)
-        CHK(resident_blocks(k_tcg_hess_span<D, R, 2>, &p->cap_h));
-      else
-        CHK(resident_blocks(k_tcg_hess_span<D, R, 1>, &p->cap_h));
+      CHK(resident_blocks(k_tcg_update_span<D, R, 0>, &p->cap_u));
+      CHK(resident_blocks(k_tcg_update_span<D, R, 1>, &p->cap_u_ml));
+      // cap_hs: the non-temporal instance <D, R, 1>, also when <D, R, 0> runs
       CHK(resident_blocks(k_tcg_hess_sym<D, R, 1>, &p->cap_hs));
     } else {
       CHK(resident_blocks(k_tcg_update<D, R>, &p->cap_u));
       p->cap_u_ml = p->cap_u;  // (one kernel for both modes)
-      if (p->split == 4)
-        CHK(resident_blocks(k_tcg_hess<D, R, 4>, &p->cap_h));
-      else if (p->split == 2)
-        CHK(resident_blocks(k_tcg_hess<D, R, 2>, &p->cap_h));
-      else
-        CHK(resident_blocks(k_tcg_hess<D, R, 1>, &p->cap_h));
     }
-  });
-  DISPATCH(p->d, p->r, {
-    if (p->split == 4) {
-      CHK(resident_blocks(k_ml_restrict<D, R, 4, BsrDev>, &p->cap_restrict));
-      CHK(resident_blocks(k_ml_post_ap<D, R, 4>, &p->cap_post));
-    } else if (p->split == 2) {
-      CHK(resident_blocks(k_ml_restrict<D, R, 2, BsrDev>, &p->cap_restrict));
-      CHK(resident_blocks(k_ml_post_ap<D, R, 2>, &p->cap_post));
-    } else {
-      // one pose per D+1 lanes: the smallest count over the variants a cycle may launch (plain / symmetric storage, fp64 /
+    CHK(dispatch_split(p->split, [&](auto Sc) {
+      constexpr int S = decltype(Sc)::value;
+      // cap_h: the span kernel's default-NTS instance of this split, also when the non-temporal <D, R, 1, 1> runs
+      if constexpr (Span<D, R, 1>::kOk)
+        CHK(resident_blocks(k_tcg_hess_span<D, R, S>, &p->cap_h));
+      else
+        CHK(resident_blocks(k_tcg_hess<D, R, S>, &p->cap_h));
+      // cap_restrict / cap_post: the plain-storage fp64 instance of this split ...
+      CHK(resident_blocks(k_ml_restrict<D, R, S, BsrDev>, &p->cap_restrict));
+      CHK(resident_blocks(k_ml_post_ap<D, R, S>, &p->cap_post));
+      return DPGO_OK;
+    }));
+    if (p->split != 4 && p->split != 2) {
+      // ... and at one pose per D+1 lanes only, the smallest count over the variants a cycle may launch (symmetric storage,
       // fp32 copies) -- a grid sized for a variant with more resident workgroups than the launched one leaves part of it
       // waiting for a slot
-      int c = 0;
-      CHK(resident_blocks(k_ml_restrict<D, R, 1, BsrDev>, &p->cap_restrict));
-      CHK(resident_blocks(k_ml_restrict<D, R, 1, BsrSymDev, double, double>, &c));
-      p->cap_restrict = std::min(p->cap_restrict, c);
-      CHK(resident_blocks(k_ml_restrict<D, R, 1, BsrSymDev32, float, float>, &c));
-      p->cap_restrict = std::min(p->cap_restrict, c);
-      CHK(resident_blocks(k_ml_restrict<D, R, 1, BsrSymDev32, float, double>, &c));
-      p->cap_restrict = std::min(p->cap_restrict, c);
-      CHK(resident_blocks(k_ml_post_ap<D, R, 1>, &p->cap_post));
-      CHK(resident_blocks(k_ml_post_ap<D, R, 1, float, float>, &c));
-      p->cap_post = std::min(p->cap_post, c);
-      CHK(resident_blocks(k_ml_post_ap<D, R, 1, float, double>, &c));
-      p->cap_post = std::min(p->cap_post, c);
+      CHK(lower_to_resident(k_ml_restrict<D, R, 1, BsrSymDev, double, double>, &p->cap_restrict));
+      CHK(lower_to_resident(k_ml_restrict<D, R, 1, BsrSymDev32, float, float>, &p->cap_restrict));
+      CHK(lower_to_resident(k_ml_restrict<D, R, 1, BsrSymDev32, float, double>, &p->cap_restrict));
+      CHK(lower_to_resident(k_ml_post_ap<D, R, 1, float, float>, &p->cap_post));
+      CHK(lower_to_resident(k_ml_post_ap<D, R, 1, float, double>, &p->cap_post));
     }
-  });
+    // cap_spmm_sym: the non-temporal instance, also when <D, R, 0> runs; cap_outer_sym: the smaller of k_grad's and k_hess's
+    p->cap_spmm_sym = p->cap_outer_sym = kMaxGrid;
+    CHK(lower_to_resident(k_spmm_sym<D, R, 1>, &p->cap_spmm_sym));
+    CHK(lower_to_resident(k_grad<D, R, 1, BsrSymDev>, &p->cap_outer_sym));
+    CHK(lower_to_resident(k_hess<D, R, 1, BsrSymDev>, &p->cap_outer_sym));
+    return DPGO_OK;
+  }));
   if (options().grid_ml > 0) p->cap_restrict = p->cap_post = std::min(kPartialCap, options().grid_ml);
   // tuning knobs (any value up to the partial-sum capacity is valid)
   if (options().grid_update > 0) p->cap_u = p->cap_u_ml = std::min(kPartialCap, options().grid_update);
   if (options().grid_hess > 0) p->cap_h = std::min(kPartialCap, options().grid_hess);
   if (options().grid_hess_sym > 0) p->cap_hs = std::min(kPartialCap, options().grid_hess_sym);
-  DISPATCH(p->d, p->r, {
-    int c = kMaxGrid;
-    CHK(resident_blocks((k_spmm_sym<D, R, 1>), &c));
-    p->cap_spmm_sym = std::min(kMaxGrid, c);
-    int cg = kMaxGrid, ch = kMaxGrid;
-    CHK(resident_blocks((k_grad<D, R, 1, BsrSymDev>), &cg));
-    CHK(resident_blocks((k_hess<D, R, 1, BsrSymDev>), &ch));
-    p->cap_outer_sym = std::min(kPartialCap, std::min(cg, ch));
-  });
   if (options().grid_outer_sym > 0) p->cap_outer_sym = std::min(kPartialCap, options().grid_outer_sym);
   if (options().grid_spmm_sym > 0) p->cap_spmm_sym = std::min(4096, options().grid_spmm_sym);
   return DPGO_OK;

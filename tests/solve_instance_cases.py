@@ -17,7 +17,7 @@ from dataclasses import dataclass
 import numpy as np
 
 DR = [(2, 2), (2, 3), (2, 4), (2, 5), (3, 3), (3, 4), (3, 5), (3, 6)]  # DPGO_FOR_DR (csrc/host.h)
-LAYOUTS = [(4, 1), (4, 2), (1, 1), (1, 2)]  # (SPLIT, MT) of the plain k_rtr_persist instances (solve.hip, PERSIST_LAUNCH)
+LAYOUTS = [(4, 1), (4, 2), (1, 1), (1, 2)]  # (SPLIT, MT) of the plain k_rtr_persist instances (solve.hip, dispatch_persist)
 PRECONDS = ("jacobi", "none")
 RHO_MARGIN = 0.01  # every rho at least this far from 0.1, 0.25, 0.75 (tests/trust_region_cases.py)
 EDGE = 0.10  # tCG's residual at the step that stops and the one before it; the step before a boundary exit
