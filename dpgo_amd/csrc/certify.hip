@@ -373,6 +373,16 @@ int certify_impl(dpgo_problem_s* p, const double* X, const dpgo_certify_params* 
         M[((size_t)k * 2 + jb) * r * r + ar * r + bq] = s;
       }
     CHK(c.combine({X, K1}, {Z0, Z1}, M));
+    // the reported |C z|: mu is an eigenvalue of a Gram matrix of squares, so sqrt(mu) carries sqrt(round-off) of the
+    // LARGEST |C k| (1e-8 of it: an exactly null t beside a non-stationary X reads 1e-11 scale).  C Z is the same
+    // combination of C K, and its row norms have no such cancellation.
+    CHK(c.combine({CK0, CK1}, {CK0, CK1}, M));
+    std::vector<double> Gz;
+    CHK(c.gram({CK0, CK1}, {{0, 0}, {1, 1}}, Gz));
+    cz = 0.0;
+    for (int q = 0; q < mz; ++q)
+      cz = std::max(cz, std::sqrt(std::max(Gz[(size_t)(q / r) * r * r + (q % r) * r + (q % r)], 0.0)));
+    res->deflation_residual = cz;
   }
   std::vector<const double*> Zb;
   if (nzb >= 1) Zb.push_back(Z0);

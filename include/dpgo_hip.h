@@ -669,7 +669,12 @@ int dpgo_build_G_coupling(int my_id, int d, int n, int m, const int32_t* r1, con
  *                  NUMERICAL, not a lower-bound proof: an eigen-solver can miss a smaller eigenvalue its start block and
  *                  Krylov space never saw (a Cholesky-based proof of C + eta I >= 0 is out of scope).  With X of rank d
  *                  a certified X rounds to the global optimum of the PGO problem (SE-Sync, Thm. 7).
- *   NOT_CONVERGED: neither within max_iterations. */
+ *   NOT_CONVERGED: neither within max_iterations.
+ * Tiny problems: the iteration works on three blocks of r vectors, so with fewer than 3r directions left,
+ * (d+1)n - dim Z < 3r, it stops on a dependent basis after a step or two: NOT_CERTIFIED (with a valid witness) if a Ritz
+ * value was below -eta scale by then, the exact verdict where the start block already spans the complement
+ * ((d+1)n - dim Z = r), NOT_CONVERGED otherwise -- never CERTIFIED without a converged pair; with fewer than r directions
+ * left the start block is rank deficient and the call returns DPGO_ERR_STATE. */
 #define DPGO_CERT_CERTIFIED 0
 #define DPGO_CERT_NOT_CERTIFIED 1
 #define DPGO_CERT_NOT_CONVERGED 2

@@ -82,8 +82,57 @@ def complement_lambda_min_sparse(Cs, Z, scale, seed=0):
     return float(np.min(w))
 
 
-def ring_measurements(oracle, n, d):
-    """n-pose ring, identity measurements, kappa = tau = 1."""
+DENSE_LIMIT = 1500  # (d+1)n up to which the dense route is taken (complement_lambda_min's N x N SVD is too slow well below it)
+
+
+def operator_norm1(Cs):
+    """|C|_1 of a sparse matrix: the size of the operator that the suite's 1e-12 scalar tolerance is relative to."""
+    return float(abs(Cs).sum(axis=0).max())
+
+
+def _complement_dense(Cs, Z):
+    """(I - Z Z^T) C (I - Z Z^T) + |C|_1 Z Z^T: C on Z's complement, span(Z) moved to the top of the spectrum."""
+    Cm = Cs.toarray() if sp.issparse(Cs) else np.asarray(Cs)
+    CZ = Cm @ Z
+    A = Cm - CZ @ Z.T - Z @ CZ.T + Z @ ((Z.T @ CZ) @ Z.T) + np.abs(Cm).sum(axis=0).max() * (Z @ Z.T)
+    return 0.5 * (A + A.T)
+
+
+def lambda_min_dense(Cs, Z, k=1):
+    """The k smallest eigenvalues of C on the orthogonal complement of span(Z) (orthonormal columns), by eigvalsh."""
+    return np.linalg.eigvalsh(_complement_dense(Cs, Z))[:k]
+
+
+def lambda_min_lanczos(Cs, Z, k=1, tol=1e-12, seed=0):
+    """The same by eigsh(which="SA") on the projected operator: no factorisation, no deflation beyond Z -- for a C whose
+    smallest eigenvalue on the complement is well separated (an arbitrary X), any size."""
+    N = Cs.shape[0]
+    top = operator_norm1(Cs)
+
+    def mv(v):
+        v = np.asarray(v).reshape(-1)
+        zv = Z.T @ v
+        u = Cs @ (v - Z @ zv)
+        return u - Z @ (Z.T @ u) + top * (Z @ zv)
+
+    v0 = np.random.default_rng(seed).standard_normal(N)
+    w = spla.eigsh(spla.LinearOperator((N, N), matvec=mv, dtype=np.float64), k=k, which="SA", tol=tol, v0=v0,
+                   return_eigenvectors=False)
+    return np.sort(w)
+
+
+def lambda_min(Cs, Z, k=1):
+    """Dense up to DENSE_LIMIT rows, Lanczos above."""
+    return lambda_min_dense(Cs, Z, k) if Cs.shape[0] <= DENSE_LIMIT else lambda_min_lanczos(Cs, Z, k)
+
+
+def ring_measurements(oracle, n, d, kappa=1.0):
+    """n-pose ring, identity measurements, kappa = tau on every edge (1 unless given)."""
+    if kappa != 1.0:
+        om, n = ring_measurements(oracle, n, d)
+        om.kappa = kappa * om.kappa
+        om.tau = kappa * om.tau
+        return om, n
     m = n
     z = np.zeros(m, dtype=np.int64)
     p1 = np.arange(n, dtype=np.int64)
