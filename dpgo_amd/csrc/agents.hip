@@ -1,4 +1,4 @@
-// agents.hip -- callers either side of the local solve: GNC re-weighting (src/DPGO_robust.cpp, src/PGOAgent.cpp:997-1142), initial guesses (src/DPGO_solver.cpp:220-303), manifold operations (src/manifold/*.cpp), public-pose exchange plans.
+// agents.hip -- callers either side of the local solve: GNC and robust-cost re-weighting (src/DPGO_robust.cpp, src/PGOAgent.cpp:997-1142), initial guesses (src/DPGO_solver.cpp:220-303), manifold operations (src/manifold/*.cpp), public-pose exchange plans.
 #include "host.h"
 
 namespace dpgo_host {
@@ -201,6 +201,84 @@ int dpgo_problem_gnc_reweight(dpgo_problem_t p, const double* X_host, double mu,
   if (p->gnc.n_shared_edges > 0) return fail(DPGO_ERR_STATE, "shared edges need the device flavour (neighbour tiles)");
   CHK(h2d(p, p->x2, X_host));
   return dpgo_problem_gnc_reweight_device(p, p->x2, nullptr, mu, barc, w_tol, update, counts, max_rsq);
+}
+
+
+void dpgo_robust_cost_default(dpgo_robust_cost* c) {
+  if (!c) return;
+  c->type = DPGO_COST_L2;
+  c->mu = 1e-4;
+  c->barc = 5.0;
+  c->huber_threshold = 3.0;
+  c->tls_threshold = 10.0;
+}
+
+
+// The result record of k_edge_robust_finish is read back as a dpgo_reweight_stats
+static_assert(sizeof(RobustStatsDev) == sizeof(dpgo_reweight_stats) && offsetof(dpgo_reweight_stats, inliers) == 0 &&
+                  offsetof(dpgo_reweight_stats, skipped) == 3 * sizeof(int) &&
+                  offsetof(dpgo_reweight_stats, max_rsq) == offsetof(RobustStatsDev, max_rsq) &&
+                  offsetof(dpgo_reweight_stats, cost) == offsetof(RobustStatsDev, cost),
+              "RobustStatsDev mirrors dpgo_reweight_stats");
+static_assert(DPGO_COST_L2 == kCostL2 && DPGO_COST_L1 == kCostL1 && DPGO_COST_TLS == kCostTLS &&
+                  DPGO_COST_HUBER == kCostHuber && DPGO_COST_GM == kCostGM && DPGO_COST_GNC_TLS == kCostGncTls,
+              "cost type numbers of the header and of the kernel");
+
+int dpgo_problem_robust_reweight_device(dpgo_problem_t p, const double* X_dev, const double* nbr_tiles_dev,
+                                        const dpgo_robust_cost* cost, double w_tol, int update, dpgo_reweight_stats* stats) {
+  if (!p) {  // (no handle exists without a device: say so instead of "null handle")
+    int cnt = 0;
+    if (dpgo_device_count(&cnt) != DPGO_OK || cnt <= 0)
+      return fail(DPGO_ERR_HIP, "no HIP device (this library has no CPU fallback)");
+  }
+  CHK(check_ready(p));
+  if (!p->gnc.e_w) return fail(DPGO_ERR_STATE, "re-weightable edges not set");
+  if (!X_dev || !cost || !stats) return fail(DPGO_ERR_INVALID, "null X / cost / stats");
+  if (p->gnc.n_shared_edges > 0 && !nbr_tiles_dev) return fail(DPGO_ERR_INVALID, "shared edges need the neighbour tiles");
+  if (std::isnan(w_tol)) return fail(DPGO_ERR_INVALID, "w_tol is NaN");
+  switch (cost->type) {
+    case DPGO_COST_L2:
+    case DPGO_COST_L1:
+    case DPGO_COST_GM: break;
+    case DPGO_COST_HUBER:
+      if (!(cost->huber_threshold > 0.0)) return fail(DPGO_ERR_INVALID, "Huber threshold must be positive");
+      break;
+    case DPGO_COST_TLS:
+      if (!(cost->tls_threshold > 0.0)) return fail(DPGO_ERR_INVALID, "TLS threshold must be positive");
+      break;
+    case DPGO_COST_GNC_TLS:
+      if (!(cost->mu > 0.0) || !(cost->barc > 0.0)) return fail(DPGO_ERR_INVALID, "GNC mu and barc must be positive");
+      break;
+    default: return fail(DPGO_ERR_INVALID, "unknown robust cost type");
+  }
+  if (!p->gnc.r_partial) CHK(p->gnc.r_partial.alloc(kMaxGrid));
+  if (!p->gnc.r_stats) CHK(p->gnc.r_stats.alloc(1));
+  int g = std::max(1, std::min(kMaxGrid, (p->gnc.em + kBlock - 1) / kBlock));
+  if (options().grid_edges > 0) g = std::min(g, options().grid_edges);
+  const RobustCostDev c{cost->type, cost->mu, cost->barc, cost->huber_threshold, cost->tls_threshold};
+  CHK(dispatch_dr(p->d, p->r, [&](auto D, auto R) {
+    return launch(k_edge_robust<D, R>, g, 0, p->stream, p->gnc.dev(), X_dev, nbr_tiles_dev, c, w_tol, update,
+                  p->gnc.r_partial);
+  }));
+  launch(k_edge_robust_finish, 1, 0, p->stream, p->gnc.r_partial, g, p->gnc.r_stats);
+  HIPC(hipGetLastError());
+  if (update) CHK(refresh_after_weights(p));
+  RobustStatsDev h{};
+  HIPC(hipMemcpyAsync(&h, p->gnc.r_stats, sizeof(h), hipMemcpyDeviceToHost, p->stream));
+  HIPC(hipStreamSynchronize(p->stream));
+  std::memcpy(stats, &h, sizeof(h));
+  return DPGO_OK;
+}
+
+
+int dpgo_problem_robust_reweight(dpgo_problem_t p, const double* X_host, const dpgo_robust_cost* cost, double w_tol,
+                                 int update, dpgo_reweight_stats* stats) {
+  if (!p) return dpgo_problem_robust_reweight_device(p, nullptr, nullptr, cost, w_tol, update, stats);
+  CHK(check_ready(p));
+  if (!X_host) return fail(DPGO_ERR_INVALID, "null X");
+  if (p->gnc.n_shared_edges > 0) return fail(DPGO_ERR_STATE, "shared edges need the device flavour (neighbour tiles)");
+  CHK(h2d(p, p->x2, X_host));
+  return dpgo_problem_robust_reweight_device(p, p->x2, nullptr, cost, w_tol, update, stats);
 }
 
 

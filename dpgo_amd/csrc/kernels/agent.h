@@ -1,4 +1,4 @@
-// kernels/agent.h -- agent-level kernels: public-pose packing, edge residuals + GNC-TLS weights, value rebuild of Q / coupling blocks.
+// kernels/agent.h -- agent-level kernels: public-pose packing, edge residuals + GNC-TLS weights, value rebuild of Q / coupling blocks, edge residuals + any robust cost with statistics.
 // Part of kernels.h (included inside namespace dpgo, in this order: common.h, problem.h, tcg.h, persist.h, multilevel.h, dense.h, manifold.h, rtr.h, agent.h, init.h).
 #pragma once
 
@@ -296,5 +296,178 @@ __global__ __launch_bounds__(kBlock) void k_rebuild_Q(EdgeDev E, const int32_t* 
     }
 #pragma unroll
     for (int q = 0; q < BB; ++q) vals[(size_t)s * BB + q] = base[(size_t)s * BB + q] + sign * acc[q];
+  }
+}
+
+// ================================================================ K10b: edge residuals + any robust cost, with statistics
+// PGOAgent::updateMeasurementWeights (reference src/PGOAgent.cpp:1104-1142) re-weights every non-fixed loop closure with
+// RobustCost::weight (src/DPGO_robust.cpp:54-98) whichever cost type is set; K10 above knows GNC_TLS only and stays as it
+// is.  Same lane layout and the same operation order of the residual (rsq is bitwise K10's); the weight is selected by a
+// cost type that is uniform across the launch.  Type numbers: order of RobustCostParameters::Type
+// (include/DPGO/DPGO_robust.h:24-31).
+constexpr int kCostL2 = 0, kCostL1 = 1, kCostTLS = 2, kCostHuber = 3, kCostGM = 4, kCostGncTls = 5;
+struct RobustCostDev {
+  int type;
+  double mu, barc, huber, tls;
+};
+// what one workgroup of k_edge_robust leaves, and what k_edge_robust_finish sums (n: inliers, outliers, undecided, skipped)
+struct RobustPartial {
+  double max_rsq, cost;
+  int n[4];
+};
+// the result record: field for field dpgo_reweight_stats (include/dpgo_hip.h)
+struct RobustStatsDev {
+  int n[4];
+  double max_rsq, cost;
+};
+
+// Weight of one edge at r = sqrt(rSq0) (src/DPGO_robust.cpp:54-98; GNC_TLS: K10's three branches, expression by expression)
+__device__ __forceinline__ double robust_weight(const RobustCostDev& c, double rSq0) {
+  const double r = sqrt(rSq0);
+  switch (c.type) {
+    case kCostL1: return 1.0 / r;
+    case kCostHuber: return r < c.huber ? 1.0 : c.huber / r;
+    case kCostTLS: return r < c.tls ? 1.0 : 0.0;
+    case kCostGM: {
+      const double a = 1.0 + r * r;
+      return 1.0 / (a * a);
+    }
+    case kCostGncTls: {
+      const double mu = c.mu, barc = c.barc;
+      const double rSq = r * r, bSq = barc * barc;
+      const double upper = (mu + 1.0) / mu * bSq, lower = mu / (mu + 1.0) * bSq;
+      double w;
+      if (rSq >= upper) w = 0.0;
+      else if (rSq <= lower) w = 1.0;
+      else w = sqrt(bSq * mu * (mu + 1.0) / rSq) - mu;
+      return w;
+    }
+    default: return 1.0;  // L2
+  }
+}
+// rho(r) of the cost type, normalised so that rho'(r) / r is the weight above (the reference defines the weights only; these
+// are the functions they belong to, DESIGN.md "Robust costs on the device")
+__device__ __forceinline__ double robust_rho(const RobustCostDev& c, double rSq0) {
+  const double r = sqrt(rSq0);
+  switch (c.type) {
+    case kCostL1: return r;
+    case kCostHuber: return r < c.huber ? 0.5 * (r * r) : c.huber * r - 0.5 * (c.huber * c.huber);
+    case kCostTLS: return 0.5 * fmin(r * r, c.tls * c.tls);
+    case kCostGM: return (r * r) / (2.0 * (1.0 + r * r));
+    case kCostGncTls: {
+      const double mu = c.mu, rSq = r * r, bSq = c.barc * c.barc;
+      const double upper = (mu + 1.0) / mu * bSq, lower = mu / (mu + 1.0) * bSq;
+      if (rSq >= upper) return 0.5 * bSq;
+      if (rSq <= lower) return 0.5 * rSq;
+      return c.barc * r * sqrt(mu * (mu + 1.0)) - 0.5 * (mu * (bSq + rSq));
+    }
+    default: return 0.5 * (r * r);  // L2
+  }
+}
+
+template <int D, int R>
+__global__ __launch_bounds__(kBlock) void k_edge_robust(EdgeDev E, const double* __restrict__ X,
+                                                        const double* __restrict__ nbr, RobustCostDev cost, double w_tol,
+                                                        int update_weights, RobustPartial* __restrict__ partial) {
+  constexpr int B = D + 1, T = B * R;
+  __shared__ double red[kWaves * 5];
+  __shared__ double redmax[kWaves];
+  double mx = 0.0;
+  double acc[5] = {0.0, 0.0, 0.0, 0.0, 0.0};  // sum of the cost terms; inliers, outliers, undecided, skipped (exact in fp64)
+  for (int e = blockIdx.x * kBlock + threadIdx.x; e < E.m; e += gridDim.x * kBlock) {
+    const int role = E.role[e];
+    const double* __restrict__ xi = (role == 2) ? nbr + (size_t)E.slot[e] * T : X + (size_t)E.p1[e] * T;
+    const double* __restrict__ xj = (role == 1) ? nbr + (size_t)E.slot[e] * T : X + (size_t)E.p2[e] * T;
+    const double* __restrict__ Rm = E.Rm + (size_t)e * D * D;
+    const double* __restrict__ tv = E.t + (size_t)e * D;
+    double rot = 0.0, tr = 0.0;
+#pragma unroll
+    for (int a = 0; a < R; ++a) {
+#pragma unroll
+      for (int c = 0; c < D; ++c) {
+        double v = -xj[c * R + a];
+#pragma unroll
+        for (int k = 0; k < D; ++k) v = fma(xi[k * R + a], Rm[k * D + c], v);
+        rot = fma(v, v, rot);
+      }
+      double u = xj[D * R + a] - xi[D * R + a];
+#pragma unroll
+      for (int k = 0; k < D; ++k) u = fma(-xi[k * R + a], tv[k], u);
+      tr = fma(u, u, tr);
+    }
+    const double rSq0 = E.kappa[e] * rot + E.tau[e] * tr;
+    E.rsq[e] = rSq0;
+    mx = fmax(mx, rSq0);
+    double w = E.weight[e];
+    if (E.fixed[e]) {
+      if (role != 2) acc[0] += w * (0.5 * rSq0);
+      continue;
+    }
+    bool skipped = false;
+    if (update_weights) {
+      const double wn = robust_weight(cost, rSq0);
+      // a weight that is not finite (L1 at r = 0: the reference stores inf and loses Q) is never stored
+      if (__builtin_isfinite(wn)) {
+        w = wn;
+        E.weight[e] = w;
+      } else {
+        skipped = true;
+      }
+    }
+    if (role != 2) {  // a shared edge is counted by the agent that owns its source pose
+      acc[0] += robust_rho(cost, rSq0);
+      if (skipped) acc[4] += 1.0;
+      else if (w < w_tol) acc[2] += 1.0;
+      else if (w > 1.0 - w_tol) acc[1] += 1.0;
+      else acc[3] += 1.0;
+    }
+  }
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) mx = fmax(mx, __shfl_xor(mx, o));
+  if ((threadIdx.x & 63) == 0) redmax[threadIdx.x >> 6] = mx;
+  block_allreduce<5>(acc, red);  // (its barriers also order redmax)
+  if (threadIdx.x == 0) {
+    double m = redmax[0];
+#pragma unroll
+    for (int w = 1; w < kWaves; ++w) m = fmax(m, redmax[w]);
+    RobustPartial out;
+    out.max_rsq = m;
+    out.cost = acc[0];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) out.n[k] = (int)acc[1 + k];
+    partial[blockIdx.x] = out;
+  }
+}
+
+// One workgroup sums the records of k_edge_robust's workgroups: lane t takes records t, t + kBlock, .. in index order, then
+// the fixed tree of block_allreduce -- the same bits for the same grid.  The kernel boundary in front of it is the only
+// synchronisation between the workgroups.
+static __global__ __launch_bounds__(kBlock) void k_edge_robust_finish(const RobustPartial* __restrict__ partial, int count,
+                                                                      RobustStatsDev* __restrict__ out) {
+  __shared__ double red[kWaves * 5];
+  __shared__ double redmax[kWaves];
+  double mx = 0.0;
+  double acc[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
+  for (int i = threadIdx.x; i < count; i += kBlock) {
+    const RobustPartial p = partial[i];
+    mx = fmax(mx, p.max_rsq);
+    acc[0] += p.cost;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) acc[1 + k] += (double)p.n[k];
+  }
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) mx = fmax(mx, __shfl_xor(mx, o));
+  if ((threadIdx.x & 63) == 0) redmax[threadIdx.x >> 6] = mx;
+  block_allreduce<5>(acc, red);
+  if (threadIdx.x == 0) {
+    double m = redmax[0];
+#pragma unroll
+    for (int w = 1; w < kWaves; ++w) m = fmax(m, redmax[w]);
+    RobustStatsDev s;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) s.n[k] = (int)acc[1 + k];
+    s.max_rsq = m;
+    s.cost = acc[0];
+    *out = s;
   }
 }

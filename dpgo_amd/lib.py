@@ -57,6 +57,20 @@ class CertifyResultC(C.Structure):
                 ("deflation_residual", C.c_double), ("elapsedMs", C.c_double)]
 
 
+COST_L2, COST_L1, COST_TLS, COST_HUBER, COST_GM, COST_GNC_TLS = range(6)  # DPGO_COST_*
+COST_TYPES = {"L2": COST_L2, "L1": COST_L1, "TLS": COST_TLS, "Huber": COST_HUBER, "GM": COST_GM, "GNC_TLS": COST_GNC_TLS}
+
+
+class RobustCostC(C.Structure):
+    _fields_ = [("type", C.c_int), ("mu", C.c_double), ("barc", C.c_double), ("huber_threshold", C.c_double),
+                ("tls_threshold", C.c_double)]
+
+
+class ReweightStatsC(C.Structure):
+    _fields_ = [("inliers", C.c_int), ("outliers", C.c_int), ("undecided", C.c_int), ("skipped", C.c_int),
+                ("max_rsq", C.c_double), ("cost", C.c_double)]
+
+
 CERT_CERTIFIED, CERT_NOT_CERTIFIED, CERT_NOT_CONVERGED = 0, 1, 2
 CERT_STATUS = ["CERTIFIED", "NOT_CERTIFIED", "NOT_CONVERGED"]
 
@@ -89,6 +103,9 @@ SIGNATURES = {
     "dpgo_problem_set_reweightable_edges_ex": ([_P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P], _I),
     "dpgo_problem_gnc_reweight_device": ([_P, _P, _P, _D, _D, _D, _I, C.POINTER(C.c_int * 3), C.POINTER(_D)], _I),
     "dpgo_problem_gnc_reweight": ([_P, _P, _D, _D, _D, _I, C.POINTER(C.c_int * 3), C.POINTER(_D)], _I),
+    "dpgo_robust_cost_default": ([C.POINTER(RobustCostC)], None),
+    "dpgo_problem_robust_reweight_device": ([_P, _P, _P, C.POINTER(RobustCostC), _D, _I, C.POINTER(ReweightStatsC)], _I),
+    "dpgo_problem_robust_reweight": ([_P, _P, C.POINTER(RobustCostC), _D, _I, C.POINTER(ReweightStatsC)], _I),
     "dpgo_problem_set_edge_weights": ([_P, _P], _I),
     "dpgo_problem_get_edge_weights": ([_P, _P, _P], _I),
     "dpgo_problem_get_Q_values": ([_P, _P], _I),

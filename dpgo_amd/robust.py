@@ -364,3 +364,106 @@ class DistributedGNC:
         """{agent id: (positions in that agent's pose_graph.measurements(), weights)} of the local agents."""
         return {a: (ag.problem.reweightable_index, ag.problem.getEdgeWeights()[0])
                 for a, ag in self.cluster.agents.items()}
+
+
+class DistributedRobustPGO:
+    """Synchronous distributed robust PGO over an RBCDCluster for ANY cost type, after the reference's agent protocol:
+      * start as PGOAgent::initializeRobustOptimization (src/PGOAgent.cpp:1048-1060): RobustCost::reset, loop-closure
+        weights 1;
+      * global iterations (= colour phases) until PGOAgent::shouldUpdateMeasurementWeights (:997-1045) says so; then every
+        agent re-weights ALL its non-fixed loop closures, private and shared, from its iterate and the exchanged public
+        poses (updateMeasurementWeights, :1104-1142; on the device: dpgo_problem_robust_reweight_device), followed by
+        RobustCost::update and a status reset; at most robustOptNumWeightUpdates times;
+      * then on to PGOAgent::shouldTerminate (:846-878).  L2 never re-weights.
+    Both endpoints of a shared edge evaluate the same residual on the same poses and agree on its weight without a
+    message.  The global counts and the global robust cost sum rho(r_e) (this project's addition: the reference has no
+    such read-out) are one small all-reduce per weight update.  DistributedGNC keeps its own mu initialisation."""
+
+    def __init__(self, cluster, robust_params: Optional[RobustCostParameters] = None, agent_params=None):
+        from dataclasses import replace
+        from .agent import PGOAgentParameters
+        self.params = robust_params or RobustCostParameters("Huber")
+        if self.params.costType not in L.COST_TYPES:  # (before anything touches the device)
+            raise ValueError("unknown robust cost type %r (one of %s)" % (self.params.costType, ", ".join(L.COST_TYPES)))
+        self.cluster = cluster
+        self.cost = RobustCost(self.params)
+        self.agent_params = replace(agent_params or PGOAgentParameters(), robust=self.params.costType != "L2")
+        self.iteration = 0
+        self.weight_updates = 0
+        self.inner_counts = []
+        for agent in cluster.agents.values():
+            agent.problem.setReweightableEdges(include_shared=True)
+            agent.enable_status(self.agent_params)
+
+    _allreduce = DistributedGNC._allreduce  # (the same three routes: single process, library communicator, torch.distributed)
+
+    def reweight_all(self, update: bool):
+        """Every local agent's dpgo_problem_robust_reweight_device at the current cost, then the global sums: returns a
+        ReweightStats of the whole team."""
+        from .solver import ReweightStats
+        self.cluster.exchange(None)  # everyone's public poses are current
+        sums, mx = np.zeros(5), 0.0
+        for agent in self.cluster.agents.values():
+            st = agent.problem.robustReweightDevice(agent.X, agent.nbr if agent.has_neighbours else None, self.cost, 1e-8,
+                                                    update)
+            sums += [st.inliers, st.outliers, st.undecided, st.skipped, st.cost]
+            mx = max(mx, st.max_rsq)
+        sums = self._allreduce(sums, "sum")
+        mx = float(self._allreduce([mx], "max")[0])
+        return ReweightStats(int(sums[0]), int(sums[1]), int(sums[2]), int(sums[3]), mx, float(sums[4]))
+
+    def _after_update(self) -> None:  # PGOAgent::updateMeasurementWeights (:1119-1126)
+        self.weight_updates += 1
+        self.cost.update()
+        for agent in self.cluster.agents.values():
+            agent.weight_update_count = self.weight_updates
+            agent.lc_weights = agent.loop_closure_weights()
+            agent.status.readyToTerminate = False
+            agent.status.relativeChange = 0.0
+            agent.status.iterationNumber = 0  # mTeamStatus.clear()
+
+    def run(self, on_update=None):
+        """Returns info = {costType, updates, history[], inner_iterations[], iterations, robust_cost, cost, gradnorm};
+        history[k] = {mu, inliers, outliers, undecided, skipped, max_rsq, cost} of weight update k, cost = the global
+        robust cost at the iterate the weights were computed from.  on_update(record), if given, is called after every
+        weight update (all ranks).  The iterates stay on the agents."""
+        from .agent import should_terminate, should_update_measurement_weights
+        c, prm = self.cluster, self.agent_params
+        self.cost.reset()
+        for agent in c.agents.values():
+            agent.problem.setEdgeWeights(np.ones(len(agent.problem.reweightable_index)))
+            agent.weight_update_count = 0
+        info = dict(costType=self.params.costType, updates=0, history=[])
+        inner, latest = 0, 0
+        while True:
+            colour = self.iteration % c.plan.num_colours
+            self.iteration += 1
+            inner += 1
+            c.phase(colour, self.iteration)
+            team = c.team_status()
+            if should_update_measurement_weights(prm, self.weight_updates, inner, latest, team, c.plan.num_agents):
+                mu = self.cost.mu
+                st = self.reweight_all(update=True)
+                self._after_update()
+                record = dict(mu=mu, inliers=st.inliers, outliers=st.outliers, undecided=st.undecided, skipped=st.skipped,
+                              max_rsq=st.max_rsq, cost=st.cost)
+                info["history"].append(record)
+                info["updates"] = self.weight_updates
+                self.inner_counts.append(inner)
+                inner, latest = 0, self.iteration
+                if on_update is not None:
+                    on_update(record)
+                continue
+            if should_terminate(self.iteration, prm, self.weight_updates, team, c.plan.num_agents):
+                break
+        info["inner_iterations"] = list(self.inner_counts)
+        info["iterations"] = self.iteration
+        info["robust_cost"] = self.reweight_all(update=False).cost
+        f, gn = c.central_cost_and_gradnorm()
+        info["cost"], info["gradnorm"] = 2 * f, gn
+        return info
+
+    def weights(self):
+        """{agent id: (positions in that agent's pose_graph.measurements(), weights)} of the local agents."""
+        return {a: (ag.problem.reweightable_index, ag.problem.getEdgeWeights()[0])
+                for a, ag in self.cluster.agents.items()}

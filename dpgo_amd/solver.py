@@ -345,6 +345,26 @@ class PoseGraph:
 
 
 # --------------------------------------------------------------------------- QuadraticProblem
+@dataclass
+class ReweightStats:
+    """dpgo_reweight_stats: counts among the non-fixed edges an agent counts, largest squared residual, robust cost."""
+    inliers: int = 0
+    outliers: int = 0
+    undecided: int = 0
+    skipped: int = 0
+    max_rsq: float = 0.0
+    cost: float = 0.0
+
+
+def robust_cost_to_c(cost) -> "L.RobustCostC":
+    """dpgo_robust_cost of a dpgo_amd.robust.RobustCost (type, current mu, thresholds); ValueError for an unknown type."""
+    p = cost.mParams
+    if p.costType not in L.COST_TYPES:
+        raise ValueError("unknown robust cost type %r (one of %s)" % (p.costType, ", ".join(L.COST_TYPES)))
+    return L.RobustCostC(L.COST_TYPES[p.costType], float(cost.mu), float(p.GNCBarc), float(p.HuberThreshold),
+                         float(p.TLSThreshold))
+
+
 class QuadraticProblem:
     """DPGO::QuadraticProblem: f(X) = 0.5 <Q, X^T X> + <X, G> on (St(d,r) x R^r)^n.
 
@@ -705,6 +725,18 @@ class QuadraticProblem:
             self._h, L.ptr(X_dev), L.ptr(nbr_tiles_dev) if nbr_tiles_dev is not None else None, float(mu),
             float(barc), float(w_tol), int(update), C.byref(counts), C.byref(mx)))
         return tuple(counts), mx.value
+
+    def robustReweightDevice(self, X_dev, nbr_tiles_dev, cost, w_tol: float = 1e-8, update: bool = True) -> "ReweightStats":
+        """The same for any cost type (dpgo_problem_robust_reweight_device): `cost` is a dpgo_amd.robust.RobustCost, whose
+        type, current mu and thresholds select RobustCost::weight (src/DPGO_robust.cpp:54-98).  Returns the counts among
+        the non-fixed edges this agent counts, the largest squared residual and the robust cost sum rho(r_e); an edge
+        whose new weight would not be finite keeps its weight and is counted as skipped."""
+        c = robust_cost_to_c(cost)
+        out = L.ReweightStatsC()
+        L.check(self._lib.dpgo_problem_robust_reweight_device(
+            self._h, L.ptr(X_dev), L.ptr(nbr_tiles_dev) if nbr_tiles_dev is not None else None, C.byref(c), float(w_tol),
+            int(update), C.byref(out)))
+        return ReweightStats(out.inliers, out.outliers, out.undecided, out.skipped, out.max_rsq, out.cost)
 
     def pullEdgeWeights(self) -> None:
         """Write the device's current GNC weights of the registered edges back into the pose graph's measurements (the

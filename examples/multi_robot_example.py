@@ -5,6 +5,10 @@ acceleration (:170-255), one line per iteration in the reference's format, then 
 the frame of robot 0's first pose (the global anchor, :249-254) is written as CSV (PGOLogger::logTrajectory format).
 
   python examples/multi_robot_example.py 5 data/smallGrid3D.g2o [--out-dir /tmp/traj] [--no-acceleration]
+
+--robust-cost {L1,Huber,TLS,GM,GNC_TLS} runs the reference's robust agent protocol instead (coloured schedule, weight
+updates by PGOAgent::shouldUpdateMeasurementWeights, dpgo_amd.robust.DistributedRobustPGO) and prints the global robust
+cost of every weight update.
 """
 import argparse
 import os
@@ -23,6 +27,10 @@ def main():
     ap.add_argument("--out-dir", default=None)
     ap.add_argument("--certify", action="store_true",
                     help="certify the assembled global iterate on one central handle (QuadraticProblem.certify)")
+    ap.add_argument("--robust-cost", choices=["L1", "Huber", "TLS", "GM", "GNC_TLS"], default=None,
+                    help="robust agent protocol with this cost: weights re-computed on the device between blocks of iterations")
+    ap.add_argument("--weight-updates", type=int, default=10, help="robustOptNumWeightUpdates")
+    ap.add_argument("--inner-iterations", type=int, default=30, help="robustOptInnerIters")
     args = ap.parse_args()
     print("Multi-robot pose graph optimization example. ")
     if args.num_robots <= 0:
@@ -43,14 +51,30 @@ def main():
     plan = ExchangePlan(graphs)
     agents = {a: DeviceAgent(graphs, plan, a, X0[ranges[a][0]:ranges[a][1]], dpgo_amd.ROptParameters())
               for a in range(args.num_robots)}
-    if not args.no_acceleration:
-        for ag in agents.values():
-            ag.enable_acceleration(args.num_robots)
-    cluster = RBCDCluster(plan, agents)
-    print("Running %d iterations..." % args.iterations)
-    out = cluster.run_greedy(max_iters=args.iterations, gradnorm_stop=0.1)
-    for it, (rob, (cost, gn)) in enumerate(zip(out["selected"], out["trace"])):
-        print("Iter = %d | robot = %d | cost = %.5g | gradnorm = %.5g" % (it, rob, cost, gn))
+    if args.robust_cost:
+        from dpgo_amd.agent import PGOAgentParameters
+        from dpgo_amd.robust import DistributedRobustPGO, RobustCostParameters
+        cluster = RBCDCluster(plan, agents)
+        driver = DistributedRobustPGO(cluster, RobustCostParameters(args.robust_cost),
+                                      PGOAgentParameters(robustOptNumWeightUpdates=args.weight_updates,
+                                                         robustOptInnerIters=args.inner_iterations,
+                                                         maxNumIters=args.iterations))
+        print("Running the robust protocol (%s), at most %d iterations..." % (args.robust_cost, args.iterations))
+        info = driver.run(on_update=lambda h: print(
+            "Weight update | mu = %.4g | inliers = %d | outliers = %d | undecided = %d | skipped = %d | robust cost = %.6g" % (
+                h["mu"], h["inliers"], h["outliers"], h["undecided"], h["skipped"], h["cost"])))
+        print("Terminated after %d iterations, %d weight updates (inner iterations %s) | robust cost = %.6g | "
+              "weighted cost = %.6g | gradnorm = %.5g" % (info["iterations"], info["updates"], info["inner_iterations"],
+                                                          info["robust_cost"], info["cost"], info["gradnorm"]))
+    else:
+        if not args.no_acceleration:
+            for ag in agents.values():
+                ag.enable_acceleration(args.num_robots)
+        cluster = RBCDCluster(plan, agents)
+        print("Running %d iterations..." % args.iterations)
+        out = cluster.run_greedy(max_iters=args.iterations, gradnorm_stop=0.1)
+        for it, (rob, (cost, gn)) in enumerate(zip(out["selected"], out["trace"])):
+            print("Iter = %d | robot = %d | cost = %.5g | gradnorm = %.5g" % (it, rob, cost, gn))
     if args.certify:
         X = np.concatenate([agents[a].X.cpu().numpy() for a in range(args.num_robots)])  # tiles [n, d+1, r]
         pg = dpgo_amd.PoseGraph(0, r, d)

@@ -209,6 +209,45 @@ int dpgo_problem_gnc_reweight(dpgo_problem_t h, const double* X_host, double mu,
 int dpgo_problem_set_edge_weights(dpgo_problem_t h, const double* weight_host);   /* + rebuild Q, preconditioner */
 int dpgo_problem_get_edge_weights(dpgo_problem_t h, double* weight_host, double* rsq_host /* may be NULL */);
 
+/* ---- any robust cost on the device: PGOAgent::updateMeasurementWeights (src/PGOAgent.cpp:1104-1142) applies
+ * RobustCost::weight (src/DPGO_robust.cpp:54-98) of whichever RobustCostParameters::Type is set; the gnc entries
+ * above know GNC_TLS only.  Same edge registration, same refresh after an update. */
+#define DPGO_COST_L2 0   /* order of RobustCostParameters::Type, include/DPGO/DPGO_robust.h:24-31 */
+#define DPGO_COST_L1 1
+#define DPGO_COST_TLS 2
+#define DPGO_COST_HUBER 3
+#define DPGO_COST_GM 4
+#define DPGO_COST_GNC_TLS 5
+typedef struct dpgo_robust_cost {
+  int type;                /* DPGO_COST_* */
+  double mu, barc;         /* GNC_TLS: current mu, threshold (GNCBarc) */
+  double huber_threshold;  /* Huber */
+  double tls_threshold;    /* TLS */
+} dpgo_robust_cost;
+/* inliers (w > 1 - w_tol) / outliers (w < w_tol) / undecided / skipped among the non-fixed edges whose source pose this
+ * agent owns; a skipped edge is in none of the other three.  max_rsq: over all registered edges.  cost: sum over the same
+ * counted edges of rho(r_e) of the selected type (r^2/2, r, Huber: r^2/2 or c r - c^2/2, TLS: min(r^2, c^2)/2,
+ * GM: r^2 / (2 (1 + r^2)), GNC_TLS: the surrogate at mu), so that rho'(r)/r is the weight function, plus w_e r_e^2 / 2 of
+ * the fixed edges -- the quantity an IRLS loop monitors.  The reference defines the weights only. */
+typedef struct dpgo_reweight_stats {
+  int inliers, outliers, undecided, skipped;
+  double max_rsq, cost;
+} dpgo_reweight_stats;
+void dpgo_robust_cost_default(dpgo_robust_cost* c); /* L2, mu 1e-4, barc 5, Huber 3, TLS 10 (DPGO_robust.h:49-57) */
+/* Residuals as dpgo_problem_gnc_reweight_device (rsq is bitwise the same); if update != 0 every non-fixed weight becomes
+ * RobustCost::weight(sqrt(rSq)) of cost->type and Q's values, the coupling values and the preconditioner are rebuilt.
+ * Deviation from the reference: a weight that is not finite (L1 at a zero residual) is not stored -- the edge keeps its
+ * weight and is counted as skipped.  update == 0 changes nothing but rsq; counts and cost then describe the stored
+ * weights.  Only the result record crosses to the host.  DPGO_ERR_INVALID before any launch for an unknown type, a null or
+ * NaN argument, thresholds / mu / barc of the selected type that are not positive, missing neighbour tiles with shared
+ * edges registered; DPGO_ERR_STATE without registered edges. */
+int dpgo_problem_robust_reweight_device(dpgo_problem_t h, const double* X_dev, const double* nbr_tiles_dev,
+                                        const dpgo_robust_cost* cost, double w_tol, int update,
+                                        dpgo_reweight_stats* stats);
+/* Host-pointer flavour (X_host: r x (d+1)n column-major; private edges only, as the gnc flavour). */
+int dpgo_problem_robust_reweight(dpgo_problem_t h, const double* X_host, const dpgo_robust_cost* cost, double w_tol,
+                                 int update, dpgo_reweight_stats* stats);
+
 /* Q's current values (nnzb blocks, same order as set_Q_bsr) -- they change on the device under GNC re-weighting. */
 int dpgo_problem_get_Q_values(dpgo_problem_t h, double* vals_host);
 /* Multilevel (aggregation multigrid) preconditioner, precond = DPGO_PRECOND_MULTILEVEL (what DPGO_PRECOND_AUTO, the

@@ -384,6 +384,7 @@ class PoseGraph {
 
 // DPGO::QuadraticProblem: f(X) = 0.5 <Q, X^T X> + <X, G>.  Owns the device handle; unlike the reference
 // (which rebuilds the problem every iteration, src/PGOAgent.cpp:968) keep it alive next to the PoseGraph.
+class RobustCost;
 class QuadraticProblem {
  public:
   // host_linear_term = false: G is not taken from PoseGraph::linearMatrix() on the host but built on the device from
@@ -426,6 +427,20 @@ class QuadraticProblem {
   // constructG on the device from the neighbour tile buffer (device pointer, slot order of setCouplingFromPoseGraph)
   void updateLinearMatrixFromNeighbors(const double* nbr_tiles_dev) {
     check(dpgo_problem_update_G_from_neighbors_device(h_, nbr_tiles_dev));
+  }
+  // ---- re-weighting on the device for any robust cost (PGOAgent::updateMeasurementWeights, src/PGOAgent.cpp:1104-1142)
+  // Registers the pose graph's PRIVATE edges (measurements() order) as re-weightable at their current weights and
+  // fixedWeight flags; returns their number.
+  int setReweightableEdges();
+  // dpgo_problem_robust_reweight at a host iterate X (r x (d+1)n): residuals, and if `update` the non-fixed weights become
+  // cost.weight(residual) with Q and the preconditioner rebuilt on the device.  A weight that would not be finite is not
+  // stored (stats.skipped).  Defined below RobustCost.
+  dpgo_reweight_stats robustReweight(const Matrix& X, const RobustCost& cost, double w_tol = 1e-8, bool update = true);
+  // weights and squared residuals (of the last re-weighting) of the registered edges
+  void getEdgeWeights(std::vector<double>& weight, std::vector<double>& rsq) const {
+    weight.assign((size_t)reweightable_, 0.0);
+    rsq.assign((size_t)reweightable_, 0.0);
+    check(dpgo_problem_get_edge_weights(h_, weight.data(), rsq.data()));
   }
   // Explicit setup of the multilevel preconditioner for the CURRENT Q (the analogue of
   // PoseGraph::constructPreconditioner, src/PoseGraph.cpp:598-613).  Optional: a solve with
@@ -554,6 +569,7 @@ class QuadraticProblem {
   bool host_G_ = true;
   dpgo_problem_t h_ = nullptr;
   unsigned long q_version_ = (unsigned long)-1;
+  int reweightable_ = 0;  // edges registered by setReweightableEdges
 };
 
 // DPGO::QuadraticOptimizer (src/QuadraticOptimizer.cpp)
@@ -1102,12 +1118,52 @@ class RobustCost {
     mu_ *= params_.GNCMuStep;
   }
   double mu() const { return mu_; }
+  const RobustCostParameters& params() const { return params_; }
 
  private:
   RobustCostParameters params_;
   double mu_;
   unsigned iteration_ = 0;
 };
+
+inline int QuadraticProblem::setReweightableEdges() {
+  refresh();
+  const auto& ms = pose_graph_->measurements();
+  const unsigned d = dimension();
+  std::vector<int32_t> p1, p2;
+  std::vector<double> R, t, kappa, tau, w;
+  std::vector<uint8_t> fixed;
+  for (const auto& m : ms) {
+    if (m.r1 != m.r2) continue;
+    p1.push_back((int32_t)m.p1);
+    p2.push_back((int32_t)m.p2);
+    for (unsigned a = 0; a < d; ++a)
+      for (unsigned b = 0; b < d; ++b) R.push_back(m.R(a, b));
+    for (unsigned a = 0; a < d; ++a) t.push_back(m.t(a, 0));
+    kappa.push_back(m.kappa);
+    tau.push_back(m.tau);
+    w.push_back(m.weight);
+    fixed.push_back(m.fixedWeight ? 1 : 0);
+  }
+  check(dpgo_problem_set_reweightable_edges(h_, (int)p1.size(), p1.data(), p2.data(), R.data(), t.data(), kappa.data(),
+                                            tau.data(), w.data(), fixed.data()));
+  reweightable_ = (int)p1.size();
+  return reweightable_;
+}
+inline dpgo_reweight_stats QuadraticProblem::robustReweight(const Matrix& X, const RobustCost& cost, double w_tol,
+                                                            bool update) {
+  const RobustCostParameters& p = cost.params();
+  dpgo_robust_cost c;
+  dpgo_robust_cost_default(&c);
+  c.type = (int)p.costType;  // (the enum and DPGO_COST_* share the reference's order)
+  c.mu = cost.mu();
+  c.barc = p.GNCBarc;
+  c.huber_threshold = p.HuberThreshold;
+  c.tls_threshold = p.TLSThreshold;
+  dpgo_reweight_stats stats{};
+  check(dpgo_problem_robust_reweight(h_, X.data(), &c, w_tol, update ? 1 : 0, &stats));
+  return stats;
+}
 
 // DPGO::solvePGO / solveRobustPGO (include/DPGO/DPGO_solver.h:100-123, src/DPGO_solver.cpp:305-412).  T0 is
 // required here (the reference falls back to its SPQR-based chordal initialisation, which is outside the path).
