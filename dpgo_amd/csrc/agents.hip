@@ -131,7 +131,6 @@ int dpgo_problem_set_reweightable_edges_ex(dpgo_problem_t p, int m, const int32_
   CHK(upload(p->gnc.c_edge, cedge.data(), cedge.size(), p->stream));
   CHK(upload(p->gnc.c_kind, ckind.data(), ckind.size(), p->stream));
   CHK(p->gnc.e_rsq.alloc(m > 0 ? m : 1));
-  CHK(p->gnc.e_counts.alloc(4));
   CHK(p->gnc.q_base.alloc((size_t)nnzb * p->b * p->b));
   // base = Q(current weights) - sum of the listed edges' contributions at those weights
   CHK(rebuild_Q_from_weights(p, p->Q.vals, -1.0, p->gnc.q_base));
@@ -156,6 +155,37 @@ int dpgo_problem_set_reweightable_edges(dpgo_problem_t p, int m, const int32_t* 
 }
 
 
+// The result record of k_edge_robust_finish is read back as a dpgo_reweight_stats
+static_assert(sizeof(RobustStatsDev) == sizeof(dpgo_reweight_stats) && offsetof(dpgo_reweight_stats, inliers) == 0 &&
+                  offsetof(dpgo_reweight_stats, skipped) == 3 * sizeof(int) &&
+                  offsetof(dpgo_reweight_stats, max_rsq) == offsetof(RobustStatsDev, max_rsq) &&
+                  offsetof(dpgo_reweight_stats, cost) == offsetof(RobustStatsDev, cost),
+              "RobustStatsDev mirrors dpgo_reweight_stats");
+static_assert(DPGO_COST_L2 == kCostL2 && DPGO_COST_L1 == kCostL1 && DPGO_COST_TLS == kCostTLS &&
+                  DPGO_COST_HUBER == kCostHuber && DPGO_COST_GM == kCostGM && DPGO_COST_GNC_TLS == kCostGncTls,
+              "cost type numbers of the header and of the kernel");
+
+// What both re-weighting entries do once their arguments are checked: k_edge_robust over the registered edges, its
+// workgroups' records summed by k_edge_robust_finish, the values of Q / coupling / preconditioner rebuilt if the weights
+// changed, and the one result record read back.
+static int reweight_on_stream(dpgo_problem_t p, const double* X_dev, const double* nbr, const RobustCostDev& c,
+                              double w_tol, int update, RobustStatsDev* out) {
+  if (!p->gnc.r_partial) CHK(p->gnc.r_partial.alloc(kMaxGrid));
+  if (!p->gnc.r_stats) CHK(p->gnc.r_stats.alloc(1));
+  int g = std::max(1, std::min(kMaxGrid, (p->gnc.em + kBlock - 1) / kBlock));
+  if (options().grid_edges > 0) g = std::min(g, options().grid_edges);
+  CHK(dispatch_dr(p->d, p->r, [&](auto D, auto R) {
+    return launch(k_edge_robust<D, R>, g, 0, p->stream, p->gnc.dev(), X_dev, nbr, c, w_tol, update, p->gnc.r_partial);
+  }));
+  launch(k_edge_robust_finish, 1, 0, p->stream, p->gnc.r_partial, g, p->gnc.r_stats);
+  HIPC(hipGetLastError());
+  if (update) CHK(refresh_after_weights(p));
+  HIPC(hipMemcpyAsync(out, p->gnc.r_stats, sizeof(*out), hipMemcpyDeviceToHost, p->stream));
+  HIPC(hipStreamSynchronize(p->stream));
+  return DPGO_OK;
+}
+
+
 int dpgo_problem_gnc_reweight_device(dpgo_problem_t p, const double* X_dev, const double* nbr_tiles_dev, double mu,
                                      double barc, double w_tol, int update, int counts[3], double* max_rsq) {
   CHK(check_ready(p));
@@ -163,33 +193,15 @@ int dpgo_problem_gnc_reweight_device(dpgo_problem_t p, const double* X_dev, cons
   if (!X_dev) return fail(DPGO_ERR_INVALID, "null X");
   if (p->gnc.n_shared_edges > 0 && !nbr_tiles_dev) return fail(DPGO_ERR_INVALID, "shared edges need the neighbour tiles");
   if (update && !(mu > 0.0)) return fail(DPGO_ERR_INVALID, "GNC mu must be positive");
-  HIPC(hipMemsetAsync(p->gnc.e_counts, 0, sizeof(int) * 4, p->stream));
-  const int g = std::max(1, std::min(kMaxGrid, (p->gnc.em + kBlock - 1) / kBlock));
-  CHK(dispatch_dr(p->d, p->r, [&](auto D, auto R) {
-    return launch(k_edge_weights<D, R>, g, 0, p->stream, p->gnc.dev(), X_dev, nbr_tiles_dev, mu, barc, w_tol, update,
-                  p->gnc.e_counts);
-  }));
-  HIPC(hipGetLastError());
-  if (update) CHK(refresh_after_weights(p));
-  int h[4] = {0, 0, 0, 0};
-  HIPC(hipMemcpyAsync(h, p->gnc.e_counts, sizeof(int) * 4, hipMemcpyDeviceToHost, p->stream));
-  std::vector<double> rs;
-  if (max_rsq) {
-    rs.resize(p->gnc.em > 0 ? p->gnc.em : 1, 0.0);
-    if (p->gnc.em > 0)
-      HIPC(hipMemcpyAsync(rs.data(), p->gnc.e_rsq, sizeof(double) * p->gnc.em, hipMemcpyDeviceToHost, p->stream));
-  }
-  HIPC(hipStreamSynchronize(p->stream));
+  // (without an update mu and barc reach the record's cost only, which this entry does not return)
+  RobustStatsDev h{};
+  CHK(reweight_on_stream(p, X_dev, nbr_tiles_dev, RobustCostDev{kCostGncTls, mu, barc, 0.0, 0.0}, w_tol, update, &h));
   if (counts) {
-    counts[0] = h[0];
-    counts[1] = h[1];
-    counts[2] = h[2];
+    counts[0] = h.n[0];
+    counts[1] = h.n[1];
+    counts[2] = h.n[2] + h.n[3];  // an edge whose weight was not stored (skipped) is not decided either
   }
-  if (max_rsq) {
-    double mx = 0.0;
-    for (int e = 0; e < p->gnc.em; ++e) mx = std::max(mx, rs[e]);
-    *max_rsq = mx;
-  }
+  if (max_rsq) *max_rsq = h.max_rsq;
   return DPGO_OK;
 }
 
@@ -213,16 +225,6 @@ void dpgo_robust_cost_default(dpgo_robust_cost* c) {
   c->tls_threshold = 10.0;
 }
 
-
-// The result record of k_edge_robust_finish is read back as a dpgo_reweight_stats
-static_assert(sizeof(RobustStatsDev) == sizeof(dpgo_reweight_stats) && offsetof(dpgo_reweight_stats, inliers) == 0 &&
-                  offsetof(dpgo_reweight_stats, skipped) == 3 * sizeof(int) &&
-                  offsetof(dpgo_reweight_stats, max_rsq) == offsetof(RobustStatsDev, max_rsq) &&
-                  offsetof(dpgo_reweight_stats, cost) == offsetof(RobustStatsDev, cost),
-              "RobustStatsDev mirrors dpgo_reweight_stats");
-static_assert(DPGO_COST_L2 == kCostL2 && DPGO_COST_L1 == kCostL1 && DPGO_COST_TLS == kCostTLS &&
-                  DPGO_COST_HUBER == kCostHuber && DPGO_COST_GM == kCostGM && DPGO_COST_GNC_TLS == kCostGncTls,
-              "cost type numbers of the header and of the kernel");
 
 int dpgo_problem_robust_reweight_device(dpgo_problem_t p, const double* X_dev, const double* nbr_tiles_dev,
                                         const dpgo_robust_cost* cost, double w_tol, int update, dpgo_reweight_stats* stats) {
@@ -251,21 +253,10 @@ int dpgo_problem_robust_reweight_device(dpgo_problem_t p, const double* X_dev, c
       break;
     default: return fail(DPGO_ERR_INVALID, "unknown robust cost type");
   }
-  if (!p->gnc.r_partial) CHK(p->gnc.r_partial.alloc(kMaxGrid));
-  if (!p->gnc.r_stats) CHK(p->gnc.r_stats.alloc(1));
-  int g = std::max(1, std::min(kMaxGrid, (p->gnc.em + kBlock - 1) / kBlock));
-  if (options().grid_edges > 0) g = std::min(g, options().grid_edges);
-  const RobustCostDev c{cost->type, cost->mu, cost->barc, cost->huber_threshold, cost->tls_threshold};
-  CHK(dispatch_dr(p->d, p->r, [&](auto D, auto R) {
-    return launch(k_edge_robust<D, R>, g, 0, p->stream, p->gnc.dev(), X_dev, nbr_tiles_dev, c, w_tol, update,
-                  p->gnc.r_partial);
-  }));
-  launch(k_edge_robust_finish, 1, 0, p->stream, p->gnc.r_partial, g, p->gnc.r_stats);
-  HIPC(hipGetLastError());
-  if (update) CHK(refresh_after_weights(p));
   RobustStatsDev h{};
-  HIPC(hipMemcpyAsync(&h, p->gnc.r_stats, sizeof(h), hipMemcpyDeviceToHost, p->stream));
-  HIPC(hipStreamSynchronize(p->stream));
+  CHK(reweight_on_stream(p, X_dev, nbr_tiles_dev,
+                         RobustCostDev{cost->type, cost->mu, cost->barc, cost->huber_threshold, cost->tls_threshold}, w_tol,
+                         update, &h));
   std::memcpy(stats, &h, sizeof(h));
   return DPGO_OK;
 }

@@ -235,7 +235,7 @@ struct Bsr {
   X(grid_outer_sym,    "DPGO_GRID_OUTER_SYM",     0,  "launch cap of k_grad / k_hess on the symmetric storage (0: resident count)")  \
   X(grid_spmm_sym,     "DPGO_GRID_SPMM_SYM",      0,  "launch cap of k_spmm_sym (0: resident count, at most 1024)")                  \
   X(grid_ml,           "DPGO_GRID_ML",            0,  "launch cap of the level-0 restriction / post-smoothing (0: resident count)")  \
-  X(grid_edges,        "DPGO_GRID_EDGES",         0,  "launch cap of k_edge_robust (0: 1024)")                                       \
+  X(grid_edges,        "DPGO_GRID_EDGES",         0,  "launch cap of k_edge_robust, GNC and robust re-weighting alike (0: 1024)")    \
   X(persist,           "DPGO_PERSIST",           -1,  "one-launch solve (k_rtr_persist) off / on whatever the size: 0 / 1")          \
   X(persist_max_poses, "DPGO_PERSIST_MAX_POSES",  0,  "largest block the one-launch solve takes (0: every block it can hold)")       \
   X(persist_split,     "DPGO_PERSIST_SPLIT",      0,  "lane groups per pose of the one-launch solve: 1, 4 (0: by size)")             \
@@ -520,8 +520,7 @@ struct dpgo_problem_s {
     DevBuf<uint8_t> g_kind;
     DevBuf<double> c_base;
     int n_shared_edges = 0;
-    DevBuf<int> e_counts;
-    // k_edge_robust's per-workgroup records and k_edge_robust_finish's result (allocated by the first robust re-weighting)
+    // k_edge_robust's per-workgroup records and k_edge_robust_finish's result (allocated by the first re-weighting)
     DevBuf<RobustPartial> r_partial;
     DevBuf<RobustStatsDev> r_stats;
     EdgeDev dev() const {

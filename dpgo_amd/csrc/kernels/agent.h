@@ -1,4 +1,4 @@
-// kernels/agent.h -- agent-level kernels: public-pose packing, edge residuals + GNC-TLS weights, value rebuild of Q / coupling blocks, edge residuals + any robust cost with statistics.
+// kernels/agent.h -- agent-level kernels: public-pose packing, value rebuild of Q / coupling blocks, edge residuals + robust-cost weights (GNC-TLS among them) with statistics.
 // Part of kernels.h (included inside namespace dpgo, in this order: common.h, problem.h, tcg.h, persist.h, multilevel.h, dense.h, manifold.h, rtr.h, agent.h, init.h).
 #pragma once
 
@@ -171,12 +171,7 @@ __global__ __launch_bounds__(kBlock) void k_build_dinv(BsrDev Q, double shift, d
 }
 
 
-// ================================================================ K10: edge residuals + GNC-TLS weights
-// One lane per (re-weightable) edge e = (i -> j): squared residual of computeMeasurementError
-// (reference src/DPGO_utils.cpp:501-507), rSq = kappa |Y_i R - Y_j|_F^2 + tau |p_j - p_i - Y_i t|^2, then
-// RobustCost::weight for GNC_TLS (src/DPGO_robust.cpp:80-92, eq. (14) of the GNC paper) unless the edge has a
-// fixed weight.  counts[0..2] = inliers (w > 1 - tol) / outliers (w < tol) / undecided among the non-fixed edges
-// (integer atomics: exact and order-independent).
+// The registered (re-weightable) edges of a handle: what K9 and K10 below read, and the weights / residuals K10 writes
 struct EdgeDev {
   const int32_t* p1;
   const int32_t* p2;
@@ -191,55 +186,6 @@ struct EdgeDev {
   double* rsq;
   int m;
 };
-
-template <int D, int R>
-__global__ __launch_bounds__(kBlock) void k_edge_weights(EdgeDev E, const double* __restrict__ X,
-                                                         const double* __restrict__ nbr, double mu, double barc,
-                                                         double w_tol, int update_weights, int* __restrict__ counts) {
-  constexpr int B = D + 1, T = B * R;
-  for (int e = blockIdx.x * kBlock + threadIdx.x; e < E.m; e += gridDim.x * kBlock) {
-    // shared edges (PGOAgent::computeMeasurementResidual, src/PGOAgent.cpp:1048-1102): the pose owned by the
-    // neighbour comes from the public-pose buffer
-    const int role = E.role[e];
-    const double* __restrict__ xi = (role == 2) ? nbr + (size_t)E.slot[e] * T : X + (size_t)E.p1[e] * T;
-    const double* __restrict__ xj = (role == 1) ? nbr + (size_t)E.slot[e] * T : X + (size_t)E.p2[e] * T;
-    const double* __restrict__ Rm = E.Rm + (size_t)e * D * D;
-    const double* __restrict__ tv = E.t + (size_t)e * D;
-    double rot = 0.0, tr = 0.0;
-#pragma unroll
-    for (int a = 0; a < R; ++a) {
-#pragma unroll
-      for (int c = 0; c < D; ++c) {
-        double v = -xj[c * R + a];
-#pragma unroll
-        for (int k = 0; k < D; ++k) v = fma(xi[k * R + a], Rm[k * D + c], v);
-        rot = fma(v, v, rot);
-      }
-      double u = xj[D * R + a] - xi[D * R + a];
-#pragma unroll
-      for (int k = 0; k < D; ++k) u = fma(-xi[k * R + a], tv[k], u);
-      tr = fma(u, u, tr);
-    }
-    const double rSq0 = E.kappa[e] * rot + E.tau[e] * tr;
-    E.rsq[e] = rSq0;
-    if (!E.fixed[e]) {
-      double w = E.weight[e];
-      if (update_weights) {
-        const double r = sqrt(rSq0), rSq = r * r, bSq = barc * barc;
-        const double upper = (mu + 1.0) / mu * bSq, lower = mu / (mu + 1.0) * bSq;
-        if (rSq >= upper) w = 0.0;
-        else if (rSq <= lower) w = 1.0;
-        else w = sqrt(bSq * mu * (mu + 1.0) / rSq) - mu;
-        E.weight[e] = w;
-      }
-      if (counts && role != 2) {  // a shared edge is counted by the agent that owns its source pose
-        if (w < w_tol) atomicAdd(&counts[1], 1);
-        else if (w > 1.0 - w_tol) atomicAdd(&counts[0], 1);
-        else atomicAdd(&counts[2], 1);
-      }
-    }
-  }
-}
 
 // ================================================================ K9: rebuild the values of Q from edge weights
 // Gather form of constructConnectionLaplacianSE (reference src/DPGO_utils.cpp:272-344): the block-CSR pattern
@@ -299,12 +245,15 @@ __global__ __launch_bounds__(kBlock) void k_rebuild_Q(EdgeDev E, const int32_t* 
   }
 }
 
-// ================================================================ K10b: edge residuals + any robust cost, with statistics
-// PGOAgent::updateMeasurementWeights (reference src/PGOAgent.cpp:1104-1142) re-weights every non-fixed loop closure with
-// RobustCost::weight (src/DPGO_robust.cpp:54-98) whichever cost type is set; K10 above knows GNC_TLS only and stays as it
-// is.  Same lane layout and the same operation order of the residual (rsq is bitwise K10's); the weight is selected by a
-// cost type that is uniform across the launch.  Type numbers: order of RobustCostParameters::Type
-// (include/DPGO/DPGO_robust.h:24-31).
+// ================================================================ K10: edge residuals + any robust cost, with statistics
+// One lane per (re-weightable) edge e = (i -> j): squared residual of computeMeasurementError
+// (reference src/DPGO_utils.cpp:501-507), rSq = kappa |Y_i R - Y_j|_F^2 + tau |p_j - p_i - Y_i t|^2; for a shared edge
+// (PGOAgent::computeMeasurementResidual, src/PGOAgent.cpp:1048-1102) the pose owned by the neighbour comes from the
+// public-pose buffer.  Then, unless the edge has a fixed weight, RobustCost::weight (src/DPGO_robust.cpp:54-98) of whichever
+// cost type is set, as PGOAgent::updateMeasurementWeights (src/PGOAgent.cpp:1104-1142) applies it; the type is uniform
+// across the launch.  Inliers (w > 1 - tol) / outliers (w < tol) / undecided / skipped are counted among the non-fixed
+// edges, a shared edge by the agent that owns its source pose.  Both re-weighting entries (GNC and robust) launch this
+// kernel.  Type numbers: order of RobustCostParameters::Type (include/DPGO/DPGO_robust.h:24-31).
 constexpr int kCostL2 = 0, kCostL1 = 1, kCostTLS = 2, kCostHuber = 3, kCostGM = 4, kCostGncTls = 5;
 struct RobustCostDev {
   int type;
@@ -321,7 +270,7 @@ struct RobustStatsDev {
   double max_rsq, cost;
 };
 
-// Weight of one edge at r = sqrt(rSq0) (src/DPGO_robust.cpp:54-98; GNC_TLS: K10's three branches, expression by expression)
+// Weight of one edge at r = sqrt(rSq0) (src/DPGO_robust.cpp:54-98; GNC_TLS: src/DPGO_robust.cpp:80-92, eq. (14) of the GNC paper)
 __device__ __forceinline__ double robust_weight(const RobustCostDev& c, double rSq0) {
   const double r = sqrt(rSq0);
   switch (c.type) {

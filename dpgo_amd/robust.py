@@ -6,7 +6,7 @@ Mirrors (names, defaults, semantics) of the reference:
 
 The reference's solveRobustPGO rebuilds a PoseGraph (Q, preconditioner) for every GNC outer iteration;
 here Q's block pattern is fixed and only its VALUES are rebuilt on the device from the edge weights
-(dpgo_problem_gnc_reweight_device: residual kernel K10 + value rebuild K9), X never leaves HBM.
+(dpgo_problem_gnc_reweight_device: residual / weight kernel K10 = k_edge_robust + value rebuild K9), X never leaves HBM.
 """
 from __future__ import annotations
 
@@ -238,7 +238,49 @@ def solveRobustPGO(mutable_measurements: RelativeSEMeasurements, num_poses: int,
     return X.cpu().numpy(), info
 
 
-class DistributedGNC:
+class _DistributedReweighting:
+    """What the two synchronous drivers below share.  Needs: cluster, iteration, weight_updates."""
+
+    def _allreduce(self, values, op: str):
+        c = self.cluster
+        if c.world == 1:
+            return np.asarray(values, dtype=np.float64)
+        import torch
+        dev = getattr(next(iter(c.agents.values())), "device", "cpu")
+        if getattr(c, "comm", None) is not None:  # library-owned RCCL communicator
+            t = torch.tensor(values, dtype=torch.float64, device=dev)
+            c.comm.allreduce(t, 1 if op == "max" else 0, torch.cuda.current_stream().cuda_stream)
+            return t.cpu().numpy()
+        import torch.distributed as dist
+        t = torch.tensor(values, dtype=torch.float64, device="cpu" if c.stage else dev)
+        dist.all_reduce(t, op=dist.ReduceOp.MAX if op == "max" else dist.ReduceOp.SUM)
+        return t.cpu().numpy()
+
+    def _phase(self):
+        """One global iteration (= colour phase); returns the team status after it."""
+        c = self.cluster
+        colour = self.iteration % c.plan.num_colours
+        self.iteration += 1
+        c.phase(colour, self.iteration)
+        return c.team_status()
+
+    def _reset_status(self) -> None:
+        """The agents' status after weight update number self.weight_updates (PGOAgent::updateMeasurementWeights,
+        src/PGOAgent.cpp:1119-1126)."""
+        for agent in self.cluster.agents.values():
+            agent.weight_update_count = self.weight_updates
+            agent.lc_weights = agent.loop_closure_weights()
+            agent.status.readyToTerminate = False
+            agent.status.relativeChange = 0.0
+            agent.status.iterationNumber = 0  # mTeamStatus.clear()
+
+    def weights(self):
+        """{agent id: (positions in that agent's pose_graph.measurements(), weights)} of the local agents."""
+        return {a: (ag.problem.reweightable_index, ag.problem.getEdgeWeights()[0])
+                for a, ag in self.cluster.agents.items()}
+
+
+class DistributedGNC(_DistributedReweighting):
     """Synchronous distributed GNC-TLS over an RBCDCluster (BASELINE configs[4]).
 
     Assembled from the reference's per-agent pieces -- the in-tree library never drives them itself, the
@@ -279,21 +321,6 @@ class DistributedGNC:
                 agent.enable_status(self.agent_params)
                 agent.lc_weights = agent.loop_closure_weights()
 
-    def _allreduce(self, values, op: str):
-        c = self.cluster
-        if c.world == 1:
-            return np.asarray(values, dtype=np.float64)
-        import torch
-        dev = getattr(next(iter(c.agents.values())), "device", "cpu")
-        if getattr(c, "comm", None) is not None:  # library-owned RCCL communicator
-            t = torch.tensor(values, dtype=torch.float64, device=dev)
-            c.comm.allreduce(t, 1 if op == "max" else 0, torch.cuda.current_stream().cuda_stream)
-            return t.cpu().numpy()
-        import torch.distributed as dist
-        t = torch.tensor(values, dtype=torch.float64, device="cpu" if c.stage else dev)
-        dist.all_reduce(t, op=dist.ReduceOp.MAX if op == "max" else dist.ReduceOp.SUM)
-        return t.cpu().numpy()
-
     def _reweight_all(self, mu: float, update: bool):
         self.cluster.exchange(None)  # everyone's public poses are current
         counts, mx = np.zeros(3), 0.0
@@ -304,11 +331,6 @@ class DistributedGNC:
             mx = max(mx, m)
         counts = self._allreduce(counts, "sum")
         mx = float(self._allreduce([mx], "max")[0])
-        if update and self.agent_params is not None:  # PGOAgent::updateMeasurementWeights (:1119-1125)
-            for agent in self.cluster.agents.values():
-                agent.lc_weights = agent.loop_closure_weights()
-                agent.status.readyToTerminate = False
-                agent.status.relativeChange = 0.0
         return tuple(int(v) for v in counts), mx
 
     def _sweeps(self) -> None:
@@ -319,15 +341,11 @@ class DistributedGNC:
         from .agent import should_update_measurement_weights
         c, prm = self.cluster, self.agent_params
         for agent in c.agents.values():
-            agent.weight_update_count = self.weight_updates
-            agent.status.iterationNumber = 0  # mTeamStatus.clear() after a weight update (:1124)
+            agent.status.iterationNumber = 0  # every block starts from a cleared team status, the first and the last too
         inner, latest = 0, self.iteration
         while True:
-            colour = self.iteration % c.plan.num_colours
-            self.iteration += 1
             inner += 1
-            c.phase(colour, self.iteration)
-            team = c.team_status()
+            team = self._phase()
             # (the cap on the NUMBER of updates is run()'s loop bound, so the count passed here is 0)
             if should_update_measurement_weights(prm, 0, inner, latest, team, c.plan.num_agents):
                 break
@@ -350,6 +368,8 @@ class DistributedGNC:
                 info["history"].append(dict(mu=mu, inliers=n_in, outliers=n_out, undecided=n_und))
                 info["updates"] = it + 1
                 self.weight_updates = it + 1
+                if self.agent_params is not None:
+                    self._reset_status()
                 if n_und == 0:
                     break
                 mu = p.GNCMuStep * mu
@@ -360,13 +380,8 @@ class DistributedGNC:
         info["cost"], info["gradnorm"] = 2 * f, gn
         return info
 
-    def weights(self):
-        """{agent id: (positions in that agent's pose_graph.measurements(), weights)} of the local agents."""
-        return {a: (ag.problem.reweightable_index, ag.problem.getEdgeWeights()[0])
-                for a, ag in self.cluster.agents.items()}
 
-
-class DistributedRobustPGO:
+class DistributedRobustPGO(_DistributedReweighting):
     """Synchronous distributed robust PGO over an RBCDCluster for ANY cost type, after the reference's agent protocol:
       * start as PGOAgent::initializeRobustOptimization (src/PGOAgent.cpp:1048-1060): RobustCost::reset, loop-closure
         weights 1;
@@ -395,8 +410,6 @@ class DistributedRobustPGO:
             agent.problem.setReweightableEdges(include_shared=True)
             agent.enable_status(self.agent_params)
 
-    _allreduce = DistributedGNC._allreduce  # (the same three routes: single process, library communicator, torch.distributed)
-
     def reweight_all(self, update: bool):
         """Every local agent's dpgo_problem_robust_reweight_device at the current cost, then the global sums: returns a
         ReweightStats of the whole team."""
@@ -412,16 +425,6 @@ class DistributedRobustPGO:
         mx = float(self._allreduce([mx], "max")[0])
         return ReweightStats(int(sums[0]), int(sums[1]), int(sums[2]), int(sums[3]), mx, float(sums[4]))
 
-    def _after_update(self) -> None:  # PGOAgent::updateMeasurementWeights (:1119-1126)
-        self.weight_updates += 1
-        self.cost.update()
-        for agent in self.cluster.agents.values():
-            agent.weight_update_count = self.weight_updates
-            agent.lc_weights = agent.loop_closure_weights()
-            agent.status.readyToTerminate = False
-            agent.status.relativeChange = 0.0
-            agent.status.iterationNumber = 0  # mTeamStatus.clear()
-
     def run(self, on_update=None):
         """Returns info = {costType, updates, history[], inner_iterations[], iterations, robust_cost, cost, gradnorm};
         history[k] = {mu, inliers, outliers, undecided, skipped, max_rsq, cost} of weight update k, cost = the global
@@ -436,15 +439,14 @@ class DistributedRobustPGO:
         info = dict(costType=self.params.costType, updates=0, history=[])
         inner, latest = 0, 0
         while True:
-            colour = self.iteration % c.plan.num_colours
-            self.iteration += 1
             inner += 1
-            c.phase(colour, self.iteration)
-            team = c.team_status()
+            team = self._phase()
             if should_update_measurement_weights(prm, self.weight_updates, inner, latest, team, c.plan.num_agents):
                 mu = self.cost.mu
                 st = self.reweight_all(update=True)
-                self._after_update()
+                self.weight_updates += 1
+                self.cost.update()
+                self._reset_status()
                 record = dict(mu=mu, inliers=st.inliers, outliers=st.outliers, undecided=st.undecided, skipped=st.skipped,
                               max_rsq=st.max_rsq, cost=st.cost)
                 info["history"].append(record)
@@ -462,8 +464,3 @@ class DistributedRobustPGO:
         f, gn = c.central_cost_and_gradnorm()
         info["cost"], info["gradnorm"] = 2 * f, gn
         return info
-
-    def weights(self):
-        """{agent id: (positions in that agent's pose_graph.measurements(), weights)} of the local agents."""
-        return {a: (ag.problem.reweightable_index, ag.problem.getEdgeWeights()[0])
-                for a, ag in self.cluster.agents.items()}

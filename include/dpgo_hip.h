@@ -200,7 +200,10 @@ int dpgo_problem_set_reweightable_edges_ex(dpgo_problem_t h, int m, const int32_
  * become RobustCost::weight(sqrt(rSq)) for GNC_TLS with the given mu and barc (src/DPGO_robust.cpp:80-92) and
  * Q's values, the coupling values and the preconditioner are rebuilt on the device.
  * counts[3] = {inliers, outliers, undecided} among non-fixed edges whose source pose this agent owns
- * (w_tol as in DPGO_solver.cpp:340).  max_rsq (optional) = max residual over all edges (muInit, :358). */
+ * (w_tol as in DPGO_solver.cpp:340).  max_rsq (optional) = max residual over all edges (muInit, :358).
+ * A weight that is not finite (the residual of a NaN iterate) is not stored: the edge keeps its weight and is counted as
+ * undecided, so Q stays finite.  Runs the kernel of dpgo_problem_robust_reweight_device below (DPGO_GRID_EDGES caps its
+ * launch); only its 32-byte result record crosses to the host. */
 int dpgo_problem_gnc_reweight_device(dpgo_problem_t h, const double* X_dev, const double* nbr_tiles_dev, double mu,
                                      double barc, double w_tol, int update, int counts[3], double* max_rsq);
 /* Host-pointer flavour of dpgo_problem_gnc_reweight_device (X_host: r x (d+1)n column-major; private edges only). */
@@ -211,7 +214,7 @@ int dpgo_problem_get_edge_weights(dpgo_problem_t h, double* weight_host, double*
 
 /* ---- any robust cost on the device: PGOAgent::updateMeasurementWeights (src/PGOAgent.cpp:1104-1142) applies
  * RobustCost::weight (src/DPGO_robust.cpp:54-98) of whichever RobustCostParameters::Type is set; the gnc entries
- * above know GNC_TLS only.  Same edge registration, same refresh after an update. */
+ * above are its GNC_TLS case with their own arguments and checks.  Same edge registration, kernel and refresh. */
 #define DPGO_COST_L2 0   /* order of RobustCostParameters::Type, include/DPGO/DPGO_robust.h:24-31 */
 #define DPGO_COST_L1 1
 #define DPGO_COST_TLS 2
@@ -238,9 +241,9 @@ void dpgo_robust_cost_default(dpgo_robust_cost* c); /* L2, mu 1e-4, barc 5, Hube
  * RobustCost::weight(sqrt(rSq)) of cost->type and Q's values, the coupling values and the preconditioner are rebuilt.
  * Deviation from the reference: a weight that is not finite (L1 at a zero residual) is not stored -- the edge keeps its
  * weight and is counted as skipped.  update == 0 changes nothing but rsq; counts and cost then describe the stored
- * weights.  Only the result record crosses to the host.  DPGO_ERR_INVALID before any launch for an unknown type, a null or
- * NaN argument, thresholds / mu / barc of the selected type that are not positive, missing neighbour tiles with shared
- * edges registered; DPGO_ERR_STATE without registered edges. */
+ * weights.  Only the result record crosses to the host; DPGO_GRID_EDGES caps the launch.  DPGO_ERR_INVALID before any
+ * launch for an unknown type, a null or NaN argument, thresholds / mu / barc of the selected type that are not positive,
+ * missing neighbour tiles with shared edges registered; DPGO_ERR_STATE without registered edges. */
 int dpgo_problem_robust_reweight_device(dpgo_problem_t h, const double* X_dev, const double* nbr_tiles_dev,
                                         const dpgo_robust_cost* cost, double w_tol, int update,
                                         dpgo_reweight_stats* stats);

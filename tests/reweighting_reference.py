@@ -1,4 +1,4 @@
-"""np.longdouble restatement of the GNC re-weighting path (kernels/agent.h: K10 k_edge_weights, K9 k_rebuild_Q; agents.hip:
+"""np.longdouble restatement of the GNC re-weighting path (kernels/agent.h: K10 k_edge_robust, K9 k_rebuild_Q; agents.hip:
 refresh_after_weights), used by tests/test_reweighting_*.py, with a-priori bounds for the device's fp64 results.  Nothing here
 calls the oracle's fp64 code.
 
@@ -105,7 +105,7 @@ def rsq_bound(mag, d, r):
 
 
 def tls_weight_fp64(rsq, mu, barc):
-    """The GNC-TLS weight as k_edge_weights and the reference library evaluate it, in fp64 and in their order of
+    """The GNC-TLS weight as k_edge_robust and the reference library evaluate it, in fp64 and in their order of
     operations: r = sqrt(rsq), rSq = r r, >= upper -> 0, <= lower -> 1, else sqrt(bSq mu (mu + 1) / rSq) - mu."""
     rsq = np.asarray(rsq, dtype=np.float64)
     mu, barc = np.float64(mu), np.float64(barc)

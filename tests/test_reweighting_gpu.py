@@ -1,4 +1,4 @@
-"""GNC re-weighting on the device, kernel by kernel: the residual / weight kernel k_edge_weights (K10) and the values-only
+"""GNC re-weighting on the device, kernel by kernel: the residual / weight kernel k_edge_robust (K10) and the values-only
 rebuild k_rebuild_Q (K9, for Q and for the coupling blocks) against the longdouble restatement of reweighting_reference.py
 within its a-priori bounds (derived there, not fitted), and every derived copy of Q -- block-Jacobi factors, symmetric
 storage, its fp32 copies, the hierarchy -- after a weight change against a fresh handle built from the new values.
@@ -120,7 +120,7 @@ _CACHE = {}
 
 
 def _graph257(oracle, d):
-    """_random_graph on 257 poses: 424 edges (two workgroups of k_edge_weights, the second ragged), a hub pose with 40
+    """_random_graph on 257 poses: 424 edges (two workgroups of k_edge_robust, the second ragged), a hub pose with 40
     edges in both orientations, odometry fixed and the rest free."""
     if ("g", d) not in _CACHE:
         om, T, hub = _random_graph(oracle, d, 257, 128, 40, seed=4100 + d)
@@ -184,7 +184,7 @@ def _drive_edge_kernel(case, oracle, h, ed, meas, fixed, iterates, d, r, counted
 
 @pytest.mark.parametrize("d,r", DR)
 def test_edge_residuals_and_tls_weights_match_longdouble(oracle, d, r):
-    """k_edge_weights<d, r> through dpgo_problem_gnc_reweight_device on 257 poses / 424 edges, on a single edge and on an
+    """k_edge_robust<d, r> through dpgo_problem_gnc_reweight_device on 257 poses / 424 edges, on a single edge and on an
     empty registration: rsq of every edge (fixed ones too) within c_rsq u mag of the longdouble residual, max_rsq bitwise
     the largest device rsq, the weights of the three GNC-TLS branches from the device's own rsq, fixed weights kept
     bitwise, integer counts at w_tol = 1e-8 and 0.25, nothing changed by update = 0; the exactly representable threshold
@@ -242,6 +242,47 @@ def test_edge_residuals_and_tls_weights_match_longdouble(oracle, d, r):
                 assert counts == _expected_counts(w, ~fixed1, 1e-8)
                 if (mu, barc) == (0.125, 1.0):
                     assert ref.tls_thresholds(mu, barc)[1] == 9.0 and w[0] == 0.0 and counts == (0, 1, 0)
+        finally:
+            h.close()
+
+
+@pytest.mark.parametrize("d,r", [(3, 5), (2, 2)])
+def test_nan_pose_keeps_the_weights_of_its_edges_and_Q_finite(oracle, d, r):
+    """One pose's translation row is NaN in an otherwise random iterate (257 poses / 424 edges): the residuals of its edges
+    are NaN, no GNC-TLS weight can be computed for them, and dpgo_problem_gnc_reweight_device(update = 1) does not store
+    one -- those edges keep their weights bitwise and are counted as undecided, so that the three counts still sum to the
+    number of free edges; every other free edge gets its weight as usual, max_rsq is the largest finite residual, and
+    the rebuilt Q is finite everywhere."""
+    om, T, hub, Qb = _graph257(oracle, d)
+    fixed = om.fixed.copy()
+    free = ~fixed
+    degree = np.bincount(np.r_[om.p1[free], om.p2[free]], minlength=257)
+    pose = int(next(i for i in range(257) if i != hub and degree[i] >= 2))
+    at_pose = (om.p1 == pose) | (om.p2 == pose)
+    assert (free & at_pose).sum() >= 2 and (fixed & at_pose).any() and (free & ~at_pose).sum() >= 10
+    X = _iterates(oracle, T, d, r, 7 + r)[1][1].copy()
+    rsq_ref = np.asarray(ref.residuals(om, X)[0], dtype=np.float64)  # (the edges away from the pose do not see the NaN)
+    mu, barc = ref.tls_parameters_for(rsq_ref[free & ~at_pose])
+    X[pose, d, :] = np.nan
+    w0 = np.where(fixed, 1.0, np.random.default_rng(90 + d).uniform(0.2, 0.9, om.m))
+    tag = "d%d r%d nan pose" % (d, r)
+    with library_options({}) as lib:
+        h = Handle(lib, Qb, r, d)
+        try:
+            ed = Edges(h, om, np.ones(om.m), fixed)
+            assert ed.set(w0) == 0
+            rc, counts, mx = ed.reweight(device_input(X, guard_of(d, r)), mu, barc, update=True)
+            assert rc == 0, tag
+            w_dev, rsq_dev = ed.get()
+            assert np.array_equal(np.isnan(rsq_dev), at_pose) and np.isfinite(rsq_dev[~at_pose]).all(), tag
+            assert sum(counts) == int(free.sum()), (tag, counts)
+            assert np.array_equal(_bits(w_dev[at_pose]), _bits(w0[at_pose])), tag
+            away = ~at_pose
+            _check_weights(tag, rsq_dev[away], w_dev[away], w0[away], fixed[away], mu, barc)
+            inl, out, und = _expected_counts(w_dev, free & away, 1e-8)
+            assert counts == (inl, out, und + int((free & at_pose).sum())), (tag, counts)
+            assert _bits([mx])[0] == _bits([np.nanmax(rsq_dev)])[0], tag
+            assert np.isfinite(_q_values(h, Qb.nnzb)).all(), tag
         finally:
             h.close()
 
@@ -390,7 +431,7 @@ def test_values_only_rebuild_matches_longdouble(oracle, d, r):
 
 
 def test_grid_370x370_runs_every_trip_of_the_grid_stride_loops(oracle):
-    """273 060 edges and 683 020 blocks on 136 900 poses (d = r = 2): the launch cap holds 262 144 lanes, so k_edge_weights
+    """273 060 edges and 683 020 blocks on 136 900 poses (d = r = 2): the launch cap holds 262 144 lanes, so k_edge_robust
     takes a second trip of its grid-stride loop and k_rebuild_Q a third; residuals, weights, counts, rebuilt values and
     the product as on the small graphs."""
     d = r = 2

@@ -103,7 +103,7 @@ def _drive(case, ed, meas, fixed, iterates, d, r, w0=None, types=TYPES, grid=Non
         rsq_ref, mag = ref.residuals(meas, X)
         rsq_bound = ref.rsq_bound(mag, d, r)
         rsq_ref64 = np.asarray(rsq_ref, dtype=np.float64)
-        # what K10 leaves on the same handle
+        # what the GNC entry leaves on the same handle
         rcode, _, mx10 = ed.reweight(Xd, 1.0, 1.0, update=False, nbr=nbr)
         assert rcode == 0
         _, rsq10 = ed.get()
@@ -120,7 +120,7 @@ def _drive(case, ed, meas, fixed, iterates, d, r, w0=None, types=TYPES, grid=Non
             assert rcode == 0, tag
             w_same, rsq_dev = ed.get()
             assert np.array_equal(_bits(w_same), _bits(wb)), tag  # update = 0: no weight changes
-            assert np.array_equal(_bits(rsq_dev), _bits(rsq10)), tag  # the residual is bitwise K10's
+            assert np.array_equal(_bits(rsq_dev), _bits(rsq10)), tag  # the residual is bitwise the GNC entry's
             assert _bits([st0.max_rsq])[0] == _bits([rsq_dev.max() if len(rsq_dev) else 0.0])[0] == _bits([mx10])[0], tag
             assert _counts(st0) == _expected_counts(wb, free & counted_all, 1e-8) and st0.skipped == 0, tag
             _check_cost(tag, "cost", st0.cost, cost, rsq_ref, rsq_bound, wb, fixed, counted_all, grid)
@@ -144,7 +144,7 @@ def _drive(case, ed, meas, fixed, iterates, d, r, w0=None, types=TYPES, grid=Non
 def test_every_cost_type_matches_longdouble(oracle, d, r):
     """k_edge_robust<d, r> on 257 poses / 424 edges (two workgroups, the second ragged; hub pose; odometry fixed, with
     weights that are not 1) near the truth and at a random iterate, all six cost types with thresholds at quantiles of the
-    residuals: rsq bitwise k_edge_weights', max_rsq bitwise its maximum, weights from the device's own rsq within k EPS w,
+    residuals: rsq bitwise the GNC entry's, max_rsq bitwise its maximum, weights from the device's own rsq within k EPS w,
     saturated values exact, fixed weights kept bitwise, counts at w_tol 1e-8 and 0.25, the cost within its bound of the
     longdouble sum, nothing but rsq changed by update = 0."""
     om, T, hub, Qb = _graph257(oracle, d)
