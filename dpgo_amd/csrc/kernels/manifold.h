@@ -85,11 +85,88 @@ __global__ __launch_bounds__(kBlock) void k_retract(const double* __restrict__ X
   }
 }
 
+// ================================================================ one-sided Jacobi (shared by K5 and K12)
+// Hestenes' one-sided Jacobi on the D columns a[p][0..N) of an N x D block M, held in registers: the columns of a pair
+// (p, q) are rotated by the angle taken from their own dot products (Golub & Van Loan, Matrix Computations, 4th ed.,
+// Alg. 8.6.3 applied to columns) until every pair is orthogonal to kJacobiTol relative to the pair's norms.  On return
+// a = M V = U diag(sigma): the column norms are the singular values, the normalised columns are U, and V (the product
+// of the plane rotations, so det V = +1) is accumulated from the identity.  Nothing here forms M^T M, so the factors
+// lose eps kappa(M) where the Gram route M (M^T M)^-1/2 lost eps kappa(M)^2.
+// The block is first scaled by a power of two (exact) so that its largest entry lies in [1, 2): the dot products can
+// then neither overflow nor underflow, and a column whose squared norm falls below kJacobiZero (sigma below 1e-90
+// sigma_max) is numerically zero: it is left alone here and contributes nothing to U V^T (jacobi_inv_norms).
+constexpr double kJacobiTol = 0x1p-50;    // 4 eps: below the round-off of an N-term dot product nothing is gained
+constexpr double kJacobiZero = 0x1p-600;  // on the squared norm of a column of the scaled block
+constexpr int kJacobiSweeps = 30;         // (convergence is quadratic; the bound guarantees termination)
+template <int D, int N>
+__device__ __forceinline__ void jacobi_columns(double (&a)[D][N], double (&V)[D][D]) {
+  double mx = 0.0;
+#pragma unroll
+  for (int p = 0; p < D; ++p)
+#pragma unroll
+    for (int k = 0; k < N; ++k) mx = fmax(mx, fabs(a[p][k]));
+  const int ex = (mx > 0.0 && mx < INFINITY) ? -ilogb(mx) : 0;
+#pragma unroll
+  for (int p = 0; p < D; ++p) {
+#pragma unroll
+    for (int k = 0; k < N; ++k) a[p][k] = ldexp(a[p][k], ex);
+#pragma unroll
+    for (int q = 0; q < D; ++q) V[p][q] = (p == q) ? 1.0 : 0.0;
+  }
+  for (int sweep = 0; sweep < kJacobiSweeps; ++sweep) {
+    bool rotated = false;
+#pragma unroll
+    for (int p = 0; p < D; ++p)
+#pragma unroll
+      for (int q = p + 1; q < D; ++q) {
+        double al = 0.0, be = 0.0, ga = 0.0;
+#pragma unroll
+        for (int k = 0; k < N; ++k) {
+          al = fma(a[p][k], a[p][k], al);
+          be = fma(a[q][k], a[q][k], be);
+          ga = fma(a[p][k], a[q][k], ga);
+        }
+        if (al > kJacobiZero && be > kJacobiZero && fabs(ga) > kJacobiTol * (sqrt(al) * sqrt(be))) {
+          rotated = true;
+          const double zeta = (be - al) / (2.0 * ga);
+          const double t = (zeta >= 0.0 ? 1.0 : -1.0) / (fabs(zeta) + sqrt(zeta * zeta + 1.0));
+          const double cs = 1.0 / sqrt(t * t + 1.0), sn = t * cs;
+#pragma unroll
+          for (int k = 0; k < N; ++k) {
+            const double x = a[p][k], y = a[q][k];
+            a[p][k] = cs * x - sn * y;
+            a[q][k] = sn * x + cs * y;
+          }
+#pragma unroll
+          for (int k = 0; k < D; ++k) {
+            const double x = V[k][p], y = V[k][q];
+            V[k][p] = cs * x - sn * y;
+            V[k][q] = sn * x + cs * y;
+          }
+        }
+      }
+    if (!rotated) break;
+  }
+}
+// nrm2[k] = |a_k|^2 and inv[k] = 1 / |a_k| of the columns jacobi_columns left; inv = 0 for a numerically zero column
+template <int D, int N>
+__device__ __forceinline__ void jacobi_inv_norms(const double (&a)[D][N], double (&nrm2)[D], double (&inv)[D]) {
+#pragma unroll
+  for (int p = 0; p < D; ++p) {
+    double s = 0.0;
+#pragma unroll
+    for (int k = 0; k < N; ++k) s = fma(a[p][k], a[p][k], s);
+    nrm2[p] = s;
+    inv[p] = s > kJacobiZero ? 1.0 / sqrt(s) : 0.0;
+  }
+}
+
 // ================================================================ K5: polar projection
 // LiftedSEManifold::project (src/manifold/LiftedSEManifold.cpp:34-45; JacobiSVD U V^T,
 // src/DPGO_utils.cpp:480-486).  out = polar( a*A + b*Bm + c*Cm ) per pose when project != 0:
-// U V^T = M (M^T M)^{-1/2}; the D x D symmetric eigenproblem is solved by cyclic Jacobi sweeps
-// in registers.  One lane per pose column; every lane c < D of a pose repeats the small solve.
+// U V^T = sum_k (a_k / |a_k|) v_k^T from the one-sided Jacobi of the r x d block itself (jacobi_columns); a column
+// of norm 0 contributes 0, so a rank-deficient block maps to a finite partial isometry.  One lane per pose column;
+// every lane c < D of a pose repeats the small factorisation on the LDS copy of the tile and writes its own column.
 template <int D, int R>
 __global__ __launch_bounds__(kBlock) void k_axpby_project(double a, const double* __restrict__ A, double b,
                                                           const double* __restrict__ Bm, double c,
@@ -119,84 +196,24 @@ __global__ __launch_bounds__(kBlock) void k_axpby_project(double a, const double
     wave_sync();
     if (ok) {
       if (project && L.c < D) {
-        // C = M^T M (D x D), eigen-decompose C = W diag(lam) W^T, out col c = sum_a M[:,a] * F[a][c],
-        // F = W diag(lam^-1/2) W^T.
-        double Cmat[D][D], W[D][D];
+        double col[D][R], V[D][D], nrm2[D], inv[D];
 #pragma unroll
         for (int p = 0; p < D; ++p)
 #pragma unroll
-          for (int q = 0; q < D; ++q) {
-            double s = 0.0;
+          for (int k = 0; k < R; ++k) col[p][k] = ms[p * R + k];
+        jacobi_columns<D, R>(col, V);
+        jacobi_inv_norms<D, R>(col, nrm2, inv);
+        // out column c = sum_k u_k V[c][k]
 #pragma unroll
-            for (int k = 0; k < R; ++k) s = fma(ms[p * R + k], ms[q * R + k], s);
-            Cmat[p][q] = s;
-            W[p][q] = (p == q) ? 1.0 : 0.0;
-          }
-        for (int sweep = 0; sweep < 12; ++sweep) {
-          double offn = 0.0;
-#pragma unroll
-          for (int p = 0; p < D; ++p)
-#pragma unroll
-            for (int q = p + 1; q < D; ++q) offn += Cmat[p][q] * Cmat[p][q];
-          double dn = 0.0;
-#pragma unroll
-          for (int p = 0; p < D; ++p) dn += Cmat[p][p] * Cmat[p][p];
-          if (offn <= 1e-32 * dn) break;
-#pragma unroll
-          for (int p = 0; p < D; ++p)
-#pragma unroll
-            for (int q = p + 1; q < D; ++q) {
-              const double apq = Cmat[p][q];
-              if (apq != 0.0) {
-                const double th = (Cmat[q][q] - Cmat[p][p]) / (2.0 * apq);
-                const double t = (th >= 0.0 ? 1.0 : -1.0) / (fabs(th) + sqrt(th * th + 1.0));
-                const double cs = 1.0 / sqrt(t * t + 1.0), sn = t * cs;
-#pragma unroll
-                for (int k = 0; k < D; ++k) {
-                  const double ckp = Cmat[k][p], ckq = Cmat[k][q];
-                  Cmat[k][p] = cs * ckp - sn * ckq;
-                  Cmat[k][q] = sn * ckp + cs * ckq;
-                }
-#pragma unroll
-                for (int k = 0; k < D; ++k) {
-                  const double cpk = Cmat[p][k], cqk = Cmat[q][k];
-                  Cmat[p][k] = cs * cpk - sn * cqk;
-                  Cmat[q][k] = sn * cpk + cs * cqk;
-                }
-#pragma unroll
-                for (int k = 0; k < D; ++k) {
-                  const double wkp = W[k][p], wkq = W[k][q];
-                  W[k][p] = cs * wkp - sn * wkq;
-                  W[k][q] = sn * wkp + cs * wkq;
-                }
-              }
-            }
-        }
-        // singular values are clamped at 1e-14 sigma_max: a rank-deficient block (which the reference's SVD maps to
-        // SOME finite U V^T) stays finite here too instead of dividing by zero
-        double lmax = 0.0;
-#pragma unroll
-        for (int k = 0; k < D; ++k) lmax = fmax(lmax, Cmat[k][k]);
-        const double lfloor = fmax(1e-28 * lmax, 1e-300);
-        double F[D];  // column c of F
+        for (int k = 0; k < R; ++k) m[k] = 0.0;
 #pragma unroll
         for (int p = 0; p < D; ++p) {
-          double s = 0.0;
+          double vcp = 0.0;
 #pragma unroll
-          for (int k = 0; k < D; ++k) {
-            double wck = 0.0;
+          for (int cc = 0; cc < D; ++cc) vcp = (cc == L.c) ? V[cc][p] : vcp;
+          const double f = vcp * inv[p];
 #pragma unroll
-            for (int cc = 0; cc < D; ++cc) wck = (cc == L.c) ? W[cc][k] : wck;
-            s += W[p][k] * wck / sqrt(fmax(Cmat[k][k], lfloor));
-          }
-          F[p] = s;
-        }
-#pragma unroll
-        for (int k = 0; k < R; ++k) {
-          double s = 0.0;
-#pragma unroll
-          for (int p = 0; p < D; ++p) s = fma(ms[p * R + k], F[p], s);
-          m[k] = s;
+          for (int k = 0; k < R; ++k) m[k] = fma(col[p][k], f, m[k]);
         }
       }
       store_col<R>(out + off, m);
@@ -210,9 +227,11 @@ __global__ __launch_bounds__(kBlock) void k_axpby_project(double a, const double
 //   T_i = [ projectToRotationGroup(Ya^T Y_i) | Ya^T p_i - t0 ],  t0 = Ya^T pa,
 // anchor (Ya, pa) = the global anchor, or pose 0 of X (local frame).  projectToRotationGroup
 // (src/DPGO_utils.cpp:464-478: U V^T, last column of U negated when det U det V < 0) is evaluated as
-// M V diag(s_k / sigma_k) V^T from the eigen-decomposition M^T M = V diag(sigma^2) V^T (cyclic Jacobi), with
-// s_k = -1 on the SMALLEST singular value when det M < 0.  One lane per pose; output tiles [n][d+1][d]
-// (= the reference's d x (d+1)n column-major Matrix).
+// sum_k s_k u_k v_k^T from the one-sided Jacobi of M = Ya^T Y_i itself (jacobi_columns: M V = U diag(sigma)).  The
+// sign comes from the orthogonal factors, which are well conditioned however small sigma_min is: det V = +1 by
+// construction (a product of plane rotations), so s_k = -1 on the SMALLEST column norm when det U < 0.  A column of
+// norm 0 contributes 0.  One lane per pose; output tiles [n][d+1][d] (= the reference's d x (d+1)n column-major
+// Matrix).
 struct AnchorArg {
   double v[4 * 6];  // (d+1) x r tile, same layout as a pose tile of X
   int use;          // 0: take pose 0 of X
@@ -253,84 +272,35 @@ __global__ __launch_bounds__(kBlock) void k_round(const double* __restrict__ X, 
       for (int k = 0; k < R; ++k) s = fma(Ya[a][k], x[D * R + k], s);
       tt[a] = s - t0[a];
     }
-    double det;
-    if constexpr (D == 2) {
-      det = M[0][0] * M[1][1] - M[0][1] * M[1][0];
-    } else {
-      det = M[0][0] * (M[1][1] * M[2][2] - M[1][2] * M[2][1]) - M[0][1] * (M[1][0] * M[2][2] - M[1][2] * M[2][0]) +
-            M[0][2] * (M[1][0] * M[2][1] - M[1][1] * M[2][0]);
-    }
-    double C[D][D], W[D][D];
+    // columns of M, factored in place: col[b] = M[:, b] -> sigma_b u_b
+    double col[D][D], V[D][D], nrm2[D], inv[D];
 #pragma unroll
-    for (int p = 0; p < D; ++p)
+    for (int b = 0; b < D; ++b)
 #pragma unroll
-      for (int q = 0; q < D; ++q) {
-        double s = 0.0;
-#pragma unroll
-        for (int a = 0; a < D; ++a) s = fma(M[a][p], M[a][q], s);
-        C[p][q] = s;
-        W[p][q] = (p == q) ? 1.0 : 0.0;
-      }
-    for (int sweep = 0; sweep < 16; ++sweep) {
-      double offn = 0.0, dn = 0.0;
-#pragma unroll
-      for (int p = 0; p < D; ++p) {
-        dn += C[p][p] * C[p][p];
-#pragma unroll
-        for (int q = p + 1; q < D; ++q) offn += C[p][q] * C[p][q];
-      }
-      if (offn <= 1e-32 * dn) break;
-#pragma unroll
-      for (int p = 0; p < D; ++p)
-#pragma unroll
-        for (int q = p + 1; q < D; ++q) {
-          const double apq = C[p][q];
-          if (apq != 0.0) {
-            const double th = (C[q][q] - C[p][p]) / (2.0 * apq);
-            const double t = (th >= 0.0 ? 1.0 : -1.0) / (fabs(th) + sqrt(th * th + 1.0));
-            const double cs = 1.0 / sqrt(t * t + 1.0), sn = t * cs;
-#pragma unroll
-            for (int k = 0; k < D; ++k) {
-              const double ckp = C[k][p], ckq = C[k][q];
-              C[k][p] = cs * ckp - sn * ckq;
-              C[k][q] = sn * ckp + cs * ckq;
-            }
-#pragma unroll
-            for (int k = 0; k < D; ++k) {
-              const double cpk = C[p][k], cqk = C[q][k];
-              C[p][k] = cs * cpk - sn * cqk;
-              C[q][k] = sn * cpk + cs * cqk;
-            }
-#pragma unroll
-            for (int k = 0; k < D; ++k) {
-              const double wkp = W[k][p], wkq = W[k][q];
-              W[k][p] = cs * wkp - sn * wkq;
-              W[k][q] = sn * wkp + cs * wkq;
-            }
-          }
-        }
-    }
+      for (int a = 0; a < D; ++a) col[b][a] = M[a][b];
+    jacobi_columns<D, D>(col, V);
+    jacobi_inv_norms<D, D>(col, nrm2, inv);
     int kmin = 0;
 #pragma unroll
-    for (int k = 1; k < D; ++k) kmin = (C[k][k] < C[kmin][kmin]) ? k : kmin;
-    double sc[D];
+    for (int k = 1; k < D; ++k) kmin = (nrm2[k] < nrm2[kmin]) ? k : kmin;
 #pragma unroll
-    for (int k = 0; k < D; ++k) {
-      const double lam = C[k][k] > 0.0 ? C[k][k] : 0.0;
-      const double inv = lam > 0.0 ? 1.0 / sqrt(lam) : 0.0;
-      sc[k] = (det < 0.0 && k == kmin) ? -inv : inv;
+    for (int k = 0; k < D; ++k)
+#pragma unroll
+      for (int a = 0; a < D; ++a) col[k][a] *= inv[k];
+    double det;  // of U: +-1 up to round-off (0 when a column is numerically zero: nothing is flipped then)
+    if constexpr (D == 2) {
+      det = col[0][0] * col[1][1] - col[0][1] * col[1][0];
+    } else {
+      det = col[0][0] * (col[1][1] * col[2][2] - col[1][2] * col[2][1]) -
+            col[0][1] * (col[1][0] * col[2][2] - col[1][2] * col[2][0]) +
+            col[0][2] * (col[1][0] * col[2][1] - col[1][1] * col[2][0]);
     }
-    // F = W diag(sc) W^T ; Rot = M F
-    double F[D][D];
+    if (det < 0.0) {
 #pragma unroll
-    for (int p = 0; p < D; ++p)
+      for (int k = 0; k < D; ++k)
 #pragma unroll
-      for (int q = 0; q < D; ++q) {
-        double s = 0.0;
-#pragma unroll
-        for (int k = 0; k < D; ++k) s = fma(W[p][k] * sc[k], W[q][k], s);
-        F[p][q] = s;
-      }
+        for (int a = 0; a < D; ++a) col[k][a] = (k == kmin) ? -col[k][a] : col[k][a];
+    }
     double* __restrict__ o = T + (size_t)i * B * D;
 #pragma unroll
     for (int c = 0; c < D; ++c)
@@ -338,7 +308,7 @@ __global__ __launch_bounds__(kBlock) void k_round(const double* __restrict__ X, 
       for (int a = 0; a < D; ++a) {
         double s = 0.0;
 #pragma unroll
-        for (int p = 0; p < D; ++p) s = fma(M[a][p], F[p][c], s);
+        for (int k = 0; k < D; ++k) s = fma(col[k][a], V[c][k], s);  // Rot(a, c) = sum_k u_k(a) V(c, k)
         o[c * D + a] = s;
       }
 #pragma unroll

@@ -1186,7 +1186,17 @@ def chordal_initialization(meas: Measurements, n: int):
     Rm = rvec.reshape(n - 1, d, d)  # [i, c, l]
     for i in range(1, n):
         Rch[i] = project_to_rotation_group(Rm[i - 1].T)
-    # translations: B1 (:367-389), B2 (:394-407)
+    T = np.zeros((n, d + 1, d))
+    T[:, :d, :] = np.swapaxes(Rch, 1, 2)
+    T[:, d, :] = recover_translations(meas, n, Rch)
+    return T
+
+
+def recover_translations(meas: Measurements, n: int, Rch):
+    """recoverTranslations (src/DPGO_utils.cpp:435-462) with B1 (:367-389) and B2 (:394-407): the translations [n, d]
+    that minimise sum tau |t_j - t_i - R_i t_ij|^2 for GIVEN rotations Rch [n, d, d], t_0 = 0."""
+    d, m = meas.d, meas.m
+    d2 = d * d
     st = np.sqrt(meas.tau)
     rows, cols, vals = [], [], []
     for l in range(d):
@@ -1208,10 +1218,7 @@ def chordal_initialization(meas: Measurements, n: int):
     tred = -spla.splu(A).solve(B1red.T @ c)
     t = np.zeros((n, d))
     t[1:] = tred.reshape(n - 1, d)
-    T = np.zeros((n, d + 1, d))
-    T[:, :d, :] = np.swapaxes(Rch, 1, 2)
-    T[:, d, :] = t
-    return T
+    return t
 
 
 def measurement_error(meas: Measurements, X):

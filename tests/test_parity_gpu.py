@@ -236,7 +236,7 @@ def test_one_launch_solve_does_not_depend_on_timing(oracle, name, precond):
 def test_polar_projection_of_rank_deficient_blocks_is_finite(oracle):
     """LiftedSEManifold::project on blocks without full column rank (a zero block, a rank-1 block, a block with two
     parallel columns): the reference's JacobiSVD U V^T (src/DPGO_utils.cpp:480-486) stays finite there; so does the
-    device's M (M^T M)^-1/2 (singular values clamped at 1e-14 sigma_max).  Full-rank blocks next to them are exact."""
+    device's one-sided Jacobi (a column of norm 0 contributes 0).  Full-rank blocks next to them are exact."""
     import dpgo_amd
     d, r, n = 3, 5, 40
     rng = np.random.default_rng(12)
