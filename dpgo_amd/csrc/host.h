@@ -226,6 +226,7 @@ struct Bsr {
   X(spmm_symmetric,    "DPGO_SPMM_SYMMETRIC",    -1,  "symmetric storage of Q for blocks beyond the Infinity Cache: 0 / 1")          \
   X(stream_nt,         "DPGO_STREAM_NT",         -1,  "non-temporal single-use operands in the tCG-step kernels: 0 / 1")             \
   X(outer_sym,         "DPGO_OUTER_SYM",          1,  "outer RTR iteration (k_grad / k_hess) reads the symmetric copy when tCG does") \
+  X(rho_exact,         "DPGO_RHO_EXACT",          0,  "rho test from a fresh H eta (k_hess, one more pass over Q) instead of tCG's residual: reference path") \
   X(tile_walk,         "DPGO_TILE_WALK",          1,  "symmetric-storage kernels walk each XCD's tiles breadth-first over the tile graph (0: index order)") \
   X(tcg_ahead,         "DPGO_TCG_AHEAD",          0,  "iterations the just-in-time feed stays ahead (0: 2 multilevel / 4 otherwise)") \
   X(grid_update,       "DPGO_GRID_UPDATE",        0,  "launch cap of k_tcg_update (0: resident count)")                              \
@@ -717,7 +718,7 @@ int launch_grad(dpgo_problem_s* p, const double* X, double* RG, double* S, doubl
 int launch_hess(dpgo_problem_s* p, const double* X, const double* S, const double* V, const double* Gdot,
                 double* HV, double* partials, const DevState* st, int check_tcg, bool sym = false);
 int launch_retract(dpgo_problem_s* p, const double* X, const double* eta, double scale, double* X2,
-                   const DevState* st);
+                   const DevState* st, const double* rho_r = nullptr, const double* rho_g = nullptr);
 int launch_rtr_update(dpgo_problem_s* p);
 int launch_precond(dpgo_problem_s* p, const double* X, const double* V, const double* dinv, double* Z);
 int launch_rtr_begin(dpgo_problem_s* p, double tol, double Delta0, double Dmax, int max_inner, int tiny);

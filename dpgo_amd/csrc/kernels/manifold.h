@@ -52,15 +52,23 @@ __global__ __launch_bounds__(kBlock) void k_precond(const double* __restrict__ X
 // X2 = R_X(scale * eta): Stiefel factor = Q of the thin QR of Y + eta with diag(R) > 0 (modified
 // Gram-Schmidt; ROPTLIB Stiefel::qfRetraction), Euclidean factor p + eta.  Each lane c < D rebuilds
 // q_0..q_c from the LDS tile (identical arithmetic in all lanes of the pose).
-template <int D, int R>
+// RHO (the RTR step, scale = 1): eta is tCG's iterate, `r` its residual and `g` the gradient it started from.  tCG keeps
+// r = g + H eta (k_tcg_update: r = g, then r += alpha H delta beside eta += alpha delta, boundary step included), so the two
+// sums of the rho test come from the eta column this kernel loads anyway, without a pass over Q:
+// partials: [0] <eta, r - g> = <eta, H eta>   [1] <eta, g>   (what k_hess writes for V = eta, Gdot = g; k_rtr_update)
+template <int D, int R, bool RHO = false>
 __global__ __launch_bounds__(kBlock) void k_retract(const double* __restrict__ X, const double* __restrict__ eta,
                                                     double scale, double* __restrict__ X2,
-                                                    const DevState* __restrict__ st, int n) {
+                                                    const DevState* __restrict__ st, int n,
+                                                    const double* __restrict__ r, const double* __restrict__ g,
+                                                    double* __restrict__ partials) {
   using GEO = Geo<D, R>;
   __shared__ double sm[kWaves][GEO::G][GEO::T];
+  __shared__ double red[kWaves * kNP];  // (RHO only)
   if (st && st->rtr_stop) return;
   const LaneId L = lane_id<D>();
   const int ntiles = (n + GEO::P - 1) / GEO::P;
+  [[maybe_unused]] double part[2] = {0.0, 0.0};
   const TileIter ti_ = tile_iter(ntiles);
   for (int tile = ti_.first; tile < ti_.last; tile += ti_.step) {
     const int i = tile * GEO::P + L.wave * GEO::G + L.g;
@@ -72,6 +80,16 @@ __global__ __launch_bounds__(kBlock) void k_retract(const double* __restrict__ X
       double x[R], e[R];
       load_col<R>(X + off, x);
       load_col<R>(eta + off, e);
+      if constexpr (RHO) {
+        double rc[R], gc[R];
+        load_col<R>(r + off, rc);
+        load_col<R>(g + off, gc);
+#pragma unroll
+        for (int k = 0; k < R; ++k) {
+          part[0] = fma(e[k], rc[k] - gc[k], part[0]);
+          part[1] = fma(e[k], gc[k], part[1]);
+        }
+      }
 #pragma unroll
       for (int k = 0; k < R; ++k) a[k] = fma(scale, e[k], x[k]);
       store_col<R>(as + L.c * R, a);
@@ -83,6 +101,7 @@ __global__ __launch_bounds__(kBlock) void k_retract(const double* __restrict__ X
     }
     wave_sync();
   }
+  if constexpr (RHO) store_partials<2>(part, partials, red);
 }
 
 // ================================================================ one-sided Jacobi (shared by K5 and K12)

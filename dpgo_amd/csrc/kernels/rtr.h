@@ -4,23 +4,34 @@
 
 // ================================================================ K7c: RTR acceptance test
 // ROPTLIB SolversTR::Run, tail of one outer iteration: rho = (f1 - f2) / -(<eta,g> + 0.5 <eta,H eta>),
-// radius update, acceptance (rho > 0.1, or the tiny-decrease clause), and on acceptance
-// x1 <- x2, g1 <- g2, S1 <- S2.
-// pe: k_grad partials at x2;  ph: k_hess partials for V = eta, Gdot = g1.
+// radius update, acceptance (rho > 0.1, or the tiny-decrease clause), and on acceptance x1 <- x2.
+// The iterate stays in x1 (it may be the caller's buffer); the gradient and S are not moved on acceptance: the host
+// exchanges the roles of (g1, S1) and (g2, S2) behind EVERY launch of this kernel (rtr_outer_iteration), so all the
+// kernel owes is that the pair the host calls (g1, S1) afterwards -- (g2, S2) here -- holds the current point's values:
+// the trial point's after an acceptance (nothing to do), and a copy of (g1, S1) after a rejection or when the solve
+// had already stopped.
+// pe: k_grad partials at x2;  ph: [<eta, H eta>, <eta, g1>] from k_retract (or k_hess for V = eta, Gdot = g1).
 template <int D, int R>
 __global__ __launch_bounds__(kBlock) void k_rtr_update(double* __restrict__ x1, const double* __restrict__ x2,
-                                                       double* __restrict__ g1, const double* __restrict__ g2,
-                                                       double* __restrict__ S1, const double* __restrict__ S2,
+                                                       const double* __restrict__ g1, double* __restrict__ g2,
+                                                       const double* __restrict__ S1, double* __restrict__ S2,
                                                        const double* __restrict__ pe, int nb_e,
                                                        const double* __restrict__ ph, int nb_h,
                                                        const DevState* __restrict__ sin, DevState* __restrict__ sout,
                                                        int n) {
   using GEO = Geo<D, R>;
   __shared__ double red[kWaves * kNP];
+  const size_t total = (size_t)n * GEO::T, totS = (size_t)n * D * D;
+  const size_t stride = (size_t)gridDim.x * kBlock, e0 = (size_t)blockIdx.x * kBlock + threadIdx.x;
+  auto keep = [&]() {  // the current point does not move: its gradient and S follow the host's exchange
+    for (size_t e = e0; e < total; e += stride) g2[e] = g1[e];
+    for (size_t e = e0; e < totS; e += stride) S2[e] = S1[e];
+  };
   DevState st;
   load_state(st, sin);
   if (st.rtr_stop) {
     if (blockIdx.x == 0 && threadIdx.x == 0) store_state(sout, st);
+    keep();
     return;
   }
   double e3[3], h2[2];
@@ -50,15 +61,11 @@ __global__ __launch_bounds__(kBlock) void k_rtr_update(double* __restrict__ x1, 
     st.rtr_stop = (ngf2 < st.tol) ? 1 : 0;
   }
   if (blockIdx.x == 0 && threadIdx.x == 0) store_state(sout, st);
-  if (!accept) return;
-  const size_t total = (size_t)n * GEO::T;
-  const size_t stride = (size_t)gridDim.x * kBlock;
-  for (size_t e = (size_t)blockIdx.x * kBlock + threadIdx.x; e < total; e += stride) {
-    x1[e] = x2[e];
-    g1[e] = g2[e];
+  if (!accept) {
+    keep();
+    return;
   }
-  const size_t totS = (size_t)n * D * D;
-  for (size_t e = (size_t)blockIdx.x * kBlock + threadIdx.x; e < totS; e += stride) S1[e] = S2[e];
+  for (size_t e = e0; e < total; e += stride) x1[e] = x2[e];
 }
 
 // RTR start: f1, |g1| from k_grad partials at x1; initial radius; stop test.

@@ -664,14 +664,19 @@ void k_tcg_update_span(const double* __restrict__ X, const double* __restrict__ 
     const size_t base = (size_t)p0 * GEO::T;
     dbl2* eta2 = reinterpret_cast<dbl2*>(eta + base);
     if (mode == 1) {  // workgroup-uniform: eta += tau * delta, then tCG stops
+      // (r += tau * H delta with it: r = g + H eta holds at every exit of tCG, which is what the rho test reads, k_retract)
+      dbl2* r2 = reinterpret_cast<dbl2*>(r + base);
 #pragma unroll
       for (int it = 0; it < SPN::NIT; ++it) {
         const int pc = lane + 64 * it;
         if (2 * pc < valid) {
-          dbl2 e = ev[it];
+          dbl2 e = ev[it], rr = rv[it];
           e.x = fma(tau, dv[it].x, e.x);
           e.y = fma(tau, dv[it].y, e.y);
+          rr.x = fma(tau, hv[it].x, rr.x);
+          rr.y = fma(tau, hv[it].y, rr.y);
           eta2[pc] = e;
+          r2[pc] = rr;
         }
       }
     } else {
@@ -761,7 +766,7 @@ void k_tcg_update_span(const double* __restrict__ X, const double* __restrict__ 
 // ================================================================ K7a: tCG residual / iterate update
 // ROPTLIB SolversTR::tCG_TR, first half of one inner iteration (and, with first = 1, its
 // initialisation r = g, eta = 0, z = P(r)):
-//   d_Hd (from k_hess partials) -> alpha, e_Pe';  boundary / negative curvature -> eta += tau*delta, stop
+//   d_Hd (from k_hess partials) -> alpha, e_Pe';  boundary / negative curvature -> eta += tau*delta, r += tau*Hd, stop
 //   else eta += alpha*delta; r += alpha*Hd; z = P(r);  partials: [0] <r,r>  [1] <z,r>
 template <int D, int R>
 __global__ __launch_bounds__(kBlock, DPGO_LB_UPDATE) void k_tcg_update(const double* __restrict__ X, const double* __restrict__ g,
@@ -804,12 +809,19 @@ __global__ __launch_bounds__(kBlock, DPGO_LB_UPDATE) void k_tcg_update(const dou
     const size_t off = (size_t)i * GEO::T + L.c * R;
     if (mode == 1) {  // workgroup-uniform
       if (ok) {
-        double e[R], dl[R];
+        // (r += tau * H delta with it: r = g + H eta holds at every exit of tCG, which is what the rho test reads)
+        double e[R], dl[R], hd[R], rr[R];
         load_col<R>(eta + off, e);
         load_col<R>(delta + off, dl);
+        load_col<R>(Hd + off, hd);
+        load_col<R>(r + off, rr);
 #pragma unroll
-        for (int a = 0; a < R; ++a) e[a] = fma(tau, dl[a], e[a]);
+        for (int a = 0; a < R; ++a) {
+          e[a] = fma(tau, dl[a], e[a]);
+          rr[a] = fma(tau, hd[a], rr[a]);
+        }
         store_col<R>(eta + off, e);
+        store_col<R>(r + off, rr);
       }
       continue;
     }

@@ -273,18 +273,27 @@ int launch_hess(dpgo_problem_s* p, const double* X, const double* S, const doubl
 }
 
 int launch_retract(dpgo_problem_s* p, const double* X, const double* eta, double scale, double* X2,
-                   const DevState* st) {
-  // (no partial sums, 50 VGPRs: not bound to the update kernel's grid -- at most DPGO_GRID_RETRACT workgroups, 1 024 by default; 512 / 1 024 / 1 563 measured 259.4 / 261.4 / 260.0 it/s)
-  const int gr = std::min(pose_tiles(p->n, p->b), options().grid_retract > 0 ? options().grid_retract : kMaxGrid);
+                   const DevState* st, const double* rho_r, const double* rho_g) {
+  // (50 VGPRs, 64 with the rho test's sums: not bound to the update kernel's grid -- at most DPGO_GRID_RETRACT workgroups, 1 024 by default; 512 / 1 024 / 1 563 measured 259.4 / 261.4 / 260.0 it/s)
+  int gr = std::min(pose_tiles(p->n, p->b), options().grid_retract > 0 ? options().grid_retract : kMaxGrid);
+  // rho_r, rho_g (the RTR step: tCG's residual and the gradient it started from): the rho test's two sums go to pH(), one
+  // entry per workgroup, and launch_rtr_update is told the grid as after launch_hess
+  const bool rho = rho_r && rho_g;
+  if (rho) {
+    if (scale != 1.0) return fail(DPGO_ERR_STATE, "the rho-test sums of k_retract belong to the full step (scale 1)");
+    gr = std::min(gr, kPartialCap);
+    p->nb_hess = gr;
+  }
   CHK(dispatch_dr(p->d, p->r, [&](auto D, auto R) {
-    return launch(k_retract<D, R>, gr, 0, p->stream, X, eta, scale, X2, st, p->n);
+    if (rho) return launch(k_retract<D, R, true>, gr, 0, p->stream, X, eta, scale, X2, st, p->n, rho_r, rho_g, p->pH());
+    return launch(k_retract<D, R, false>, gr, 0, p->stream, X, eta, scale, X2, st, p->n, nullptr, nullptr, nullptr);
   }));
   HIPC(hipGetLastError());
   return DPGO_OK;
 }
 
 int launch_rtr_update(dpgo_problem_s* p) {
-  // (the partial sums of the last k_grad / k_hess launch: their grids, launch_grad / launch_hess)
+  // (the partial sums of the last k_grad launch and of the last k_retract / k_hess launch that wrote pH(): their grids)
   const int ge = p->nb_grad > 0 ? p->nb_grad : p->grid_s(), gh = p->nb_hess > 0 ? p->nb_hess : p->grid_s();
   CHK(dispatch_dr(p->d, p->r, [&](auto D, auto R) {
     return launch(k_rtr_update<D, R>, p->grid_flat(), 0, p->stream, p->x1, p->x2, p->g1, p->g2, p->S1, p->S2, p->pE(), ge,
@@ -292,6 +301,11 @@ int launch_rtr_update(dpgo_problem_s* p) {
   }));
   HIPC(hipGetLastError());
   p->cur ^= 1;
+  // the other half of the kernel's contract: whatever it decides, the pair it called (g2, S2) holds the current point's
+  // gradient and S when it is done -- every later launch finds them under the names g1, S1.  (Both pairs are the handle's
+  // own buffers and nothing keeps their addresses across launches.)
+  std::swap(p->g1, p->g2);
+  std::swap(p->S1, p->S2);
   return DPGO_OK;
 }
 

@@ -410,12 +410,19 @@ int rtr_outer_iteration(dpgo_problem_s* p, const dpgo_ropt_params* prm, const do
   }
   if (!done) CHK(launch_tcg_hess(p, 0));  // max_inner iterations enqueued, not (yet known to be) finished: last prologue
   if (p->saw_rtr_stop) return DPGO_OK;  // the previous outer iteration already met the stop test
-  CHK(launch_retract(p, p->x1, p->eta, 1.0, p->x2, p->dstate + p->cur));
+  // rho test: <eta, H eta> and <eta, g1> from tCG's own residual, r = g1 + H eta at every exit of tCG (k_tcg_update; nothing
+  // between tCG and here writes r: the cycle only reads it), summed by the retraction from the eta it loads anyway.
+  // DPGO_RHO_EXACT=1: from a fresh H eta instead, one more pass over Q (the reference path of the tests).
+  const bool rho_exact = options().rho_exact != 0;
+  CHK(launch_retract(p, p->x1, p->eta, 1.0, p->x2, p->dstate + p->cur, rho_exact ? nullptr : p->rr.get(),
+                     rho_exact ? nullptr : p->g1.get()));
   CHK(launch_grad(p, p->x2, p->g2, p->S2, nullptr, p->dstate + p->cur, p->tcg_sym && outer_sym_enabled()));
   cnt.spmm += 1;
-  CHK(launch_hess(p, p->x1, p->S1, p->eta, p->g1, p->Hd, p->pH(), p->dstate + p->cur, 0, p->tcg_sym && outer_sym_enabled()));
-  cnt.spmm += 1;
-  CHK(launch_rtr_update(p));
+  if (rho_exact) {
+    CHK(launch_hess(p, p->x1, p->S1, p->eta, p->g1, p->Hd, p->pH(), p->dstate + p->cur, 0, p->tcg_sym && outer_sym_enabled()));
+    cnt.spmm += 1;
+  }
+  CHK(launch_rtr_update(p));  // (exchanges the roles of g1 / g2 and S1 / S2)
   if (poll_at_end) CHK(poll_state(p));
   return DPGO_OK;
 }

@@ -123,7 +123,10 @@ typedef struct dpgo_ropt_result {
   int rtr_iterations;     /* outer iterations executed */
   int rtr_accepted;       /* outer iterations accepted */
   int tcg_iterations;     /* Hessian-vector products inside tCG (all outer iterations) */
-  int spmm_count;         /* Q*X block-SpMM launches in this call */
+  int spmm_count;         /* Q*X block-SpMM launches in this call.  Multi-launch scheme: 1 + rtr_iterations +
+                             tcg_iterations (the gradient at the start, the gradient at every trial point, tCG's products;
+                             the rho test reads tCG's residual -- with DPGO_RHO_EXACT=1 it costs one more per outer
+                             iteration).  One-launch solve: 1 + 2 * rtr_iterations + tcg_iterations. */
   int latest_step_accepted;
   int precond_used;       /* DPGO_PRECOND_* this call ran (what DPGO_PRECOND_AUTO resolved to) */
 } dpgo_ropt_result;
