@@ -760,7 +760,8 @@ int dpgo_manifold_retract(int r, int d, int n, const double* X, const double* et
   HIPC(hipMemcpy(x, X, vb, hipMemcpyHostToDevice));
   HIPC(hipMemcpy(v, eta, vb, hipMemcpyHostToDevice));
   CHK(dispatch_dr(d, r, [&](auto D, auto R) {
-    return launch(k_retract<D, R>, tiles_grid(d, n), 0, nullptr, x, v, scale, o, nullptr, n, nullptr, nullptr, nullptr);
+    return launch(k_retract<D, R>, tiles_grid(d, n), 0, nullptr, x, v, scale, o, nullptr, n, nullptr, nullptr, nullptr, nullptr,
+                  nullptr, nullptr);
   }));
   HIPC(hipGetLastError());
   HIPC(hipMemcpy(out, o, vb, hipMemcpyDeviceToHost));

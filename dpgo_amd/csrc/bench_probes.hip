@@ -38,6 +38,10 @@ int dpgo_bench_hess_rotating(dpgo_problem_t p, int nsets, int reps, int warmup, 
   // handle's own and exchanged back before the launch helper's result is looked at: the handle never keeps a copy, a set
   // never keeps the handle's buffer, whichever way this function is left
   CHK(resolve_tcg_storage(p));
+  // the instance the timed loop launches: on the direction ring a solve has left, the deferred one -- the pushed state
+  // record (tcg_j = 0, first = 0) makes it read slot 0 and write slot 1, and every set brings two slots of its own
+  CHK(tcg_dirs_ensure(p, 2, /*may_alloc=*/false));
+  const bool ring = p->dirs_on;
   const bool symq = p->tcg_sym;  // the kernel reads the symmetric copy: that is what rotates
   auto& SY = p->sym;
   const size_t nvals = (size_t)p->Q.nnzb * p->b * p->b, nu = (size_t)SY.nu, nl = (size_t)std::max(1, SY.nl);
@@ -69,7 +73,8 @@ int dpgo_bench_hess_rotating(dpgo_problem_t p, int nsets, int reps, int warmup, 
     dup(st.x1, p->x1, nvec);
     dup(st.S1, p->S1, (size_t)p->n * p->d * p->d);
     dup(st.z, p->z, nvec);
-    dup(st.delta, p->delta, nvec);
+    if (ring) dup(st.delta, p->dirs, 2 * nvec);
+    else dup(st.delta, p->delta, nvec);
     dup(st.Hd, p->Hd, nvec);
   }
   auto exchange = [&](Set& st) {
@@ -86,7 +91,7 @@ int dpgo_bench_hess_rotating(dpgo_problem_t p, int nsets, int reps, int warmup, 
     p->x1 = p->x1_buf;
     std::swap(p->S1, st.S1);
     std::swap(p->z, st.z);
-    std::swap(p->delta, st.delta);
+    std::swap(ring ? p->dirs : p->delta, st.delta);
     std::swap(p->Hd, st.Hd);
   };
   int rc = ok ? DPGO_OK : fail(DPGO_ERR_HIP, "hipMalloc failed for the rotating buffer sets");
@@ -228,6 +233,7 @@ int dpgo_bench_hess(dpgo_problem_t p, int reps, int warmup, double* avg_ms) {
   CHK(check_ready(p));
   if (reps <= 0 || !avg_ms) return fail(DPGO_ERR_INVALID, "bad arguments");
   CHK(resolve_tcg_storage(p));
+  CHK(tcg_dirs_ensure(p, 2, /*may_alloc=*/false));  // (the mode of the timed loop: slots 0 and 1 of the ring it left)
   // a state in which the tCG-step kernel never takes an early exit
   std::memset(p->hstate, 0, sizeof(DevState));
   p->hstate->z_r = 1.0;
@@ -300,6 +306,7 @@ int dpgo_bench_iteration_kernels(dpgo_problem_t p, int reps, int warmup, double 
   if (reps <= 0 || !out_ms) return fail(DPGO_ERR_INVALID, "bad arguments");
   for (int q = 0; q < 5; ++q) out_ms[q] = 0.0;
   CHK(resolve_tcg_storage(p));
+  CHK(tcg_dirs_ensure(p, 2, /*may_alloc=*/false));  // (the mode of the timed loop: step length 0 of the ring it left)
   // a state in which no kernel takes an early exit (as dpgo_bench_hess); alpha = z_r / d_Hd stays finite
   std::memset(p->hstate, 0, sizeof(DevState));
   p->hstate->z_r = 1.0;

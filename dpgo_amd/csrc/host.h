@@ -227,6 +227,8 @@ struct Bsr {
   X(stream_nt,         "DPGO_STREAM_NT",         -1,  "non-temporal single-use operands in the tCG-step kernels: 0 / 1")             \
   X(outer_sym,         "DPGO_OUTER_SYM",          1,  "outer RTR iteration (k_grad / k_hess) reads the symmetric copy when tCG does") \
   X(rho_exact,         "DPGO_RHO_EXACT",          0,  "rho test from a fresh H eta (k_hess, one more pass over Q) instead of tCG's residual: reference path") \
+  X(tcg_dirs,          "DPGO_TCG_DIRS",           1,  "multi-launch tCG keeps its directions and k_retract sums eta once (0: eta += alpha delta every iteration: reference path)") \
+  X(tcg_dirs_max_mb,   "DPGO_TCG_DIRS_MAX_MB", 4096,  "largest direction ring (RTR_tCG_iterations pose vectors) a solve may hold; beyond it the solve runs the reference path") \
   X(tile_walk,         "DPGO_TILE_WALK",          1,  "symmetric-storage kernels walk each XCD's tiles breadth-first over the tile graph (0: index order)") \
   X(tcg_ahead,         "DPGO_TCG_AHEAD",          0,  "iterations the just-in-time feed stays ahead (0: 2 multilevel / 4 otherwise)") \
   X(grid_update,       "DPGO_GRID_UPDATE",        0,  "launch cap of k_tcg_update (0: resident count)")                              \
@@ -312,6 +314,13 @@ struct dpgo_problem_s {
   DevBuf<double> x1_buf, x2, g1, g2, eta, delta, Hd, rr, z, S1, S2;
   // the iterate the kernels run on: x1_buf, or -- borrowed for the duration of a device solve -- the caller's buffer
   double* x1 = nullptr;
+  // tCG's kept directions (kernels/tcg.h, DEF): a ring of dirs_cap pose vectors and the step lengths that go with them
+  // (dirs_coef: count, then one per slot).  Allocated by the first multi-launch RTR solve that runs deferred, grown when a
+  // later solve has a larger tCG budget (tcg_dirs_ensure).  dirs_on: the mode of the current / last such solve, decided
+  // once per solve on the host; every launch of the solve follows it.
+  DevBuf<double> dirs, dirs_coef;
+  int dirs_cap = 0;
+  bool dirs_on = false;
   // multilevel (aggregation multigrid) preconditioner: levels[0] = the pose level ... levels.back() = the dense level
   struct MlLevel {
     int n = 0;      // nodes
@@ -718,7 +727,7 @@ int launch_grad(dpgo_problem_s* p, const double* X, double* RG, double* S, doubl
 int launch_hess(dpgo_problem_s* p, const double* X, const double* S, const double* V, const double* Gdot,
                 double* HV, double* partials, const DevState* st, int check_tcg, bool sym = false);
 int launch_retract(dpgo_problem_s* p, const double* X, const double* eta, double scale, double* X2,
-                   const DevState* st, const double* rho_r = nullptr, const double* rho_g = nullptr);
+                   const DevState* st, const double* rho_r = nullptr, const double* rho_g = nullptr, bool from_dirs = false);
 int launch_rtr_update(dpgo_problem_s* p);
 int launch_precond(dpgo_problem_s* p, const double* X, const double* V, const double* dinv, double* Z);
 int launch_rtr_begin(dpgo_problem_s* p, double tol, double Delta0, double Dmax, int max_inner, int tiny);
@@ -769,6 +778,7 @@ int launch_tcg_hess(dpgo_problem_s* p, int first);
 int launch_tcg_hess_with(dpgo_problem_s* p, const DevState* sin, DevState* sout, int first, unsigned long long* hflag,
                          unsigned gen);
 int resolve_tcg_storage(dpgo_problem_s* p);
+int tcg_dirs_ensure(dpgo_problem_s* p, int max_inner, bool may_alloc = true);
 int persist_capacity(int device);
 bool persist_reserve(dpgo_problem_s* p, int slots, int limit);
 void persist_release(dpgo_problem_s* p);

@@ -56,30 +56,107 @@ __global__ __launch_bounds__(kBlock) void k_precond(const double* __restrict__ X
 // r = g + H eta (k_tcg_update: r = g, then r += alpha H delta beside eta += alpha delta, boundary step included), so the two
 // sums of the rho test come from the eta column this kernel loads anyway, without a pass over Q:
 // partials: [0] <eta, r - g> = <eta, H eta>   [1] <eta, g>   (what k_hess writes for V = eta, Gdot = g; k_rtr_update)
-template <int D, int R, bool RHO = false>
+// DEF (the RTR step of a solve that kept tCG's directions, kernels/tcg.h): eta is not loaded but formed here, in registers,
+// from the K = coef[0] directions of the ring `dirs` (slot k = n * T doubles) and their step lengths coef[1 + k], in the
+// order of the iterations and starting from +0 -- the bits of the running sum it replaces -- with the loads of
+// kDirsInFlight slots requested before the first of them is used.  The sum is element-wise, so with an even tile size it
+// runs in span layout (lane-linear 16-byte pieces of the wave's G poses, as the span kernels of tCG; the slots are read
+// once: non-temporal loads) and reaches the lanes' (pose, column) layout through the LDS tile; odd tile sizes sum column
+// by column.  `eta` is not read.  `eta_out` (null: nobody asks): eta for whoever reads tCG's iterate after the step -- the
+// DPGO_RHO_EXACT tail, which applies H to it.
+constexpr int kDirsInFlight = 4;
+template <int D, int R, bool RHO = false, bool DEF = false>
 __global__ __launch_bounds__(kBlock) void k_retract(const double* __restrict__ X, const double* __restrict__ eta,
                                                     double scale, double* __restrict__ X2,
                                                     const DevState* __restrict__ st, int n,
                                                     const double* __restrict__ r, const double* __restrict__ g,
-                                                    double* __restrict__ partials) {
+                                                    double* __restrict__ partials, const double* __restrict__ dirs,
+                                                    const double* __restrict__ coef, double* __restrict__ eta_out) {
   using GEO = Geo<D, R>;
-  __shared__ double sm[kWaves][GEO::G][GEO::T];
+  using SPN = Span<D, R, 1>;
+  constexpr bool kSpanSum = DEF && SPN::kOk;
+  __shared__ __attribute__((aligned(16))) double sm[kWaves][GEO::G][GEO::T];
   __shared__ double red[kWaves * kNP];  // (RHO only)
   if (st && st->rtr_stop) return;
   const LaneId L = lane_id<D>();
   const int ntiles = (n + GEO::P - 1) / GEO::P;
   [[maybe_unused]] double part[2] = {0.0, 0.0};
+  [[maybe_unused]] int ndirs = 0;
+  if constexpr (DEF) ndirs = (int)coef[0];
+  [[maybe_unused]] const size_t slot = (size_t)n * GEO::T;
   const TileIter ti_ = tile_iter(ntiles);
   for (int tile = ti_.first; tile < ti_.last; tile += ti_.step) {
     const int i = tile * GEO::P + L.wave * GEO::G + L.g;
     const bool ok = (L.g < GEO::G) && (i < n);
     const size_t off = (size_t)i * GEO::T + L.c * R;
     double* as = ok ? &sm[L.wave][L.g][0] : nullptr;
+    if constexpr (kSpanSum) {  // wave-cooperative: the wave's span of eta into its LDS tile
+      const int lane = threadIdx.x & 63;
+      const int p0 = tile * GEO::P + L.wave * GEO::G;
+      const int npose = (n - p0) < GEO::G ? (n - p0) : GEO::G;
+      const int valid = npose > 0 ? npose * GEO::T : 0;
+      const size_t base = (size_t)p0 * GEO::T;
+      dbl2 e2[SPN::NIT];
+#pragma unroll
+      for (int it = 0; it < SPN::NIT; ++it) e2[it].x = e2[it].y = 0.0;
+      for (int k0 = 0; k0 < ndirs; k0 += kDirsInFlight) {
+        dbl2 dv[kDirsInFlight][SPN::NIT];
+#pragma unroll
+        for (int q = 0; q < kDirsInFlight; ++q)
+          if (k0 + q < ndirs) {
+            const dbl2* d2 = reinterpret_cast<const dbl2*>(dirs + (size_t)(k0 + q) * slot + base);
+#pragma unroll
+            for (int it = 0; it < SPN::NIT; ++it)
+              if (2 * (lane + 64 * it) < valid) dv[q][it] = ld_stream<1>(d2 + lane + 64 * it);
+          }
+#pragma unroll
+        for (int q = 0; q < kDirsInFlight; ++q)
+          if (k0 + q < ndirs) {
+            const double c = coef[1 + k0 + q];
+#pragma unroll
+            for (int it = 0; it < SPN::NIT; ++it)
+              if (2 * (lane + 64 * it) < valid) {
+                e2[it].x = fma(c, dv[q][it].x, e2[it].x);
+                e2[it].y = fma(c, dv[q][it].y, e2[it].y);
+              }
+          }
+      }
+#pragma unroll
+      for (int it = 0; it < SPN::NIT; ++it) {
+        const int pc = lane + 64 * it;
+        if (2 * pc < valid) {
+          reinterpret_cast<dbl2*>(&sm[L.wave][0][0])[pc] = e2[it];
+          if (eta_out) st_stream<1>(reinterpret_cast<dbl2*>(eta_out + base) + pc, e2[it]);
+        }
+      }
+      wave_sync();
+    }
     double a[R];
     if (ok) {
       double x[R], e[R];
       load_col<R>(X + off, x);
-      load_col<R>(eta + off, e);
+      if constexpr (kSpanSum) {
+        load_col<R>(as + L.c * R, e);  // (this lane's column of the tile: overwritten below by the same lane)
+      } else if constexpr (DEF) {
+#pragma unroll
+        for (int k = 0; k < R; ++k) e[k] = 0.0;
+        for (int k0 = 0; k0 < ndirs; k0 += kDirsInFlight) {
+          double dl[kDirsInFlight][R];
+#pragma unroll
+          for (int q = 0; q < kDirsInFlight; ++q)
+            if (k0 + q < ndirs) load_col<R>(dirs + (size_t)(k0 + q) * slot + off, dl[q]);
+#pragma unroll
+          for (int q = 0; q < kDirsInFlight; ++q)
+            if (k0 + q < ndirs) {
+              const double c = coef[1 + k0 + q];
+#pragma unroll
+              for (int k = 0; k < R; ++k) e[k] = fma(c, dl[q][k], e[k]);
+            }
+        }
+        if (eta_out) store_col<R>(eta_out + off, e);
+      } else {
+        load_col<R>(eta + off, e);
+      }
       if constexpr (RHO) {
         double rc[R], gc[R];
         load_col<R>(r + off, rc);

@@ -91,7 +91,31 @@ __device__ __forceinline__ int tcg_update_prologue(DevState& st, const double* _
   return 0;
 }
 
-template <int D, int R, int SPLIT>
+// ---------------------------------------------------------------- kept directions (DEF = 1)
+// Nothing inside a tCG run reads the iterate eta: the trust-region norms come from the scalar recurrences above and the rho
+// test reads eta once, in k_retract.  A solve whose direction ring fits (host: tcg_dirs_ensure) therefore keeps the
+// directions instead of summing them every iteration:
+//  * the Hessian-step kernels read delta_{k-1} from slot k-1 of the ring and write delta_k to slot k (`delta` is the ring,
+//    a slot is n * T doubles), k = the iteration index the prologue has just computed (0 with `first`, else st.tcg_j): the
+//    same bytes as the in-place update, and a launch that exits early touches nothing.  k < max_inner <= slots of the ring;
+//  * the update kernels load neither delta nor eta and store no eta; the thread that stores the state record also stores
+//    this iteration's step length (alpha, or tau on the boundary step) and the number of steps so far into `coef`:
+//    coef[0] = count (0 from the initialisation), coef[1 + j] = step length of iteration j;
+//  * k_retract folds eta = fma(c_{K-1}, delta_{K-1}, ... fma(c_0, delta_0, +0)) while it loads its tile: the same fused
+//    multiply-adds in the same order on the same operands as the running sum, so every bit of eta is the same.
+template <int DEF>
+__device__ __forceinline__ void tcg_store_coef(double* __restrict__ coef, const DevState& st, int mode, double alpha, double tau) {
+  if constexpr (DEF) {
+    if (mode == 2) {
+      coef[0] = 0.0;
+    } else {
+      coef[1 + st.tcg_j] = (mode == 1) ? tau : alpha;
+      coef[0] = (double)(st.tcg_j + 1);
+    }
+  }
+}
+
+template <int D, int R, int SPLIT, int DEF = 0>
 __global__ __launch_bounds__(kBlock, DPGO_LB_HESS) void k_tcg_hess(BsrDev Q, const double* __restrict__ X,
                                                      const double* __restrict__ S, const double* __restrict__ z,
                                                      double* __restrict__ delta, double* __restrict__ Hd,
@@ -120,6 +144,10 @@ __global__ __launch_bounds__(kBlock, DPGO_LB_HESS) void k_tcg_hess(BsrDev Q, con
     publish_progress(hflag, gen, st);
   }
   if (!go) return;
+  // (DEF: slot k of the ring receives delta_k, slot k - 1 holds delta_{k-1})
+  double* dout = delta;
+  if constexpr (DEF) dout = delta + (size_t)(first ? 0 : st.tcg_j) * ((size_t)n * GEO::T);
+  const double* din = (DEF && !first) ? dout - (size_t)n * GEO::T : dout;
 
   const LaneId L = lane_id<D, SPLIT>();
   const int ntiles = (n + GEO::P - 1) / GEO::P;
@@ -144,7 +172,7 @@ __global__ __launch_bounds__(kBlock, DPGO_LB_HESS) void k_tcg_hess(BsrDev Q, con
         for (int a = 0; a < D; ++a) srow[a] = S[(size_t)i * D * D + L.c * D + a];
       }
       if (!first) {
-        load_col<R>(delta + off, dl);
+        load_col<R>(din + off, dl);
         load_col<R>(Hd + off, hd);
       }
     }
@@ -183,7 +211,7 @@ __global__ __launch_bounds__(kBlock, DPGO_LB_HESS) void k_tcg_hess(BsrDev Q, con
       }
 #pragma unroll
       for (int a = 0; a < R; ++a) part[0] = fma(dl[a], hd[a], part[0]);
-      store_col<R>(delta + off, dl);
+      store_col<R>(dout + off, dl);
       store_col<R>(Hd + off, hd);
     }
     wave_sync();
@@ -197,7 +225,7 @@ __global__ __launch_bounds__(kBlock, DPGO_LB_HESS) void k_tcg_hess(BsrDev Q, con
 //  * the FIRST tile's global loads (row pointer, column indices, vector pieces) are issued before the scalar
 //    prologue (state record + partial-sum reduction), so the two dependent-latency chains overlap -- this is
 //    what matters for small blocks (multi-GPU strong scaling), where a kernel is a chain of ~15 memory latencies.
-template <int D, int R, int SPLIT, int NTS = 0>
+template <int D, int R, int SPLIT, int NTS = 0, int DEF = 0>
 __global__ __launch_bounds__(kBlock) void k_tcg_hess_span(BsrDev Q, const double* __restrict__ X,
                                                           const double* __restrict__ S, const double* __restrict__ z,
                                                           double* __restrict__ delta, double* __restrict__ Hd,
@@ -224,6 +252,10 @@ __global__ __launch_bounds__(kBlock) void k_tcg_hess_span(BsrDev Q, const double
   double srow[D];
   int p0 = 0, valid = 0, i = 0;
   bool okp = false, ok = false;
+  // (DEF: the ring slots this launch reads and writes follow from the prologue: the first tile's piece of delta_{k-1} is
+  // requested behind it -- an early-exit launch must not touch the ring, its tcg_j may equal the number of slots)
+  const double* din = DEF ? nullptr : delta;
+  double* dout = delta;
   auto prefetch = [&](int tile) {
     p0 = tile * GEO::P + L.wave * GEO::G;
     const int npose = (n - p0) < GEO::G ? (n - p0) : GEO::G;
@@ -235,7 +267,6 @@ __global__ __launch_bounds__(kBlock) void k_tcg_hess_span(BsrDev Q, const double
     const size_t base = (size_t)p0 * GEO::T;
     const dbl2* X2 = reinterpret_cast<const dbl2*>(X + base);
     const dbl2* z2 = reinterpret_cast<const dbl2*>(z + base);
-    const dbl2* d2 = reinterpret_cast<const dbl2*>(delta + base);
     const dbl2* h2 = reinterpret_cast<const dbl2*>(Hd + base);
 #pragma unroll
     for (int it = 0; it < SPN::NIT; ++it) {
@@ -244,7 +275,7 @@ __global__ __launch_bounds__(kBlock) void k_tcg_hess_span(BsrDev Q, const double
         xv[it] = ld_stream<NTS>(X2 + pc);
         zv[it] = z2[pc];
         if (!first) {
-          dv[it] = ld_stream<NTS>(d2 + pc);
+          if (!DEF || din) dv[it] = ld_stream<NTS>(reinterpret_cast<const dbl2*>(din + base) + pc);
           hv[it] = ld_stream<NTS>(h2 + pc);
         }
       }
@@ -286,6 +317,20 @@ __global__ __launch_bounds__(kBlock) void k_tcg_hess_span(BsrDev Q, const double
   }
   if (!go) return;
   DPGO_STAMP(0, 2);
+  if constexpr (DEF) {
+    dout = delta + (size_t)(first ? 0 : st.tcg_j) * ((size_t)n * GEO::T);
+    if (!first) {
+      din = dout - (size_t)n * GEO::T;
+      if (have) {
+        const dbl2* d2 = reinterpret_cast<const dbl2*>(din + (size_t)p0 * GEO::T);
+#pragma unroll
+        for (int it = 0; it < SPN::NIT; ++it) {
+          const int pc = lane + 64 * it;
+          if (2 * pc < valid) dv[it] = ld_stream<NTS>(d2 + pc);
+        }
+      }
+    }
+  }
 
   double part[1] = {0.0};
   while (have) {
@@ -322,7 +367,7 @@ __global__ __launch_bounds__(kBlock) void k_tcg_hess_span(BsrDev Q, const double
     wave_sync();
     {
       const size_t base = (size_t)p0 * GEO::T;
-      dbl2* d2 = reinterpret_cast<dbl2*>(delta + base);
+      dbl2* d2 = reinterpret_cast<dbl2*>(dout + base);
       dbl2* h2 = reinterpret_cast<dbl2*>(Hd + base);
 #pragma unroll
       for (int it = 0; it < SPN::NIT; ++it) {
@@ -368,7 +413,7 @@ __global__ __launch_bounds__(kBlock) void k_tcg_hess_span(BsrDev Q, const double
 // delivers to 512 resident workgroups, not by one wave's chain of round trips: delta / H delta requested in front of the
 // gather (37.4..37.7 us), a three-stage pipeline over the tiles (row extents two tiles ahead, indices + own X, z, S one tile
 // ahead: tile 7 us, launch 37.4..38.0 us), the previous kernel's partial sums requested in front of the first tile.
-template <int D, int R, int NTS>
+template <int D, int R, int NTS, int DEF = 0>
 __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(DPGO_SYM_WAVES, DPGO_SYM_WAVES))) void k_tcg_hess_sym(BsrSymDev Q, const double* __restrict__ X,
                                                           const double* __restrict__ S, const double* __restrict__ z,
                                                           double* __restrict__ delta, double* __restrict__ Hd,
@@ -452,6 +497,10 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(DPGO_SYM
     publish_progress(hflag, gen, st);
   }
   if (!go) return;
+  // (DEF: slot k of the ring receives delta_k, slot k - 1 holds delta_{k-1})
+  double* dout = delta;
+  if constexpr (DEF) dout = delta + (size_t)(first ? 0 : st.tcg_j) * ((size_t)n * GEO::T);
+  const double* din = (DEF && !first) ? dout - (size_t)n * GEO::T : dout;
   DPGO_STAMP(0, 2);
   DPGO_STAMP_ENTRY;
   DPGO_STAMP_AT(1);
@@ -478,7 +527,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(DPGO_SYM
     dbl2 dv[SPN::NIT], hv[SPN::NIT];
     if (!first) {
       const size_t base = (size_t)p0 * GEO::T;
-      const dbl2* d2 = reinterpret_cast<const dbl2*>(delta + base);
+      const dbl2* d2 = reinterpret_cast<const dbl2*>(din + base);
       const dbl2* h2 = reinterpret_cast<const dbl2*>(Hd + base);
 #pragma unroll
       for (int it = 0; it < SPN::NIT; ++it) {
@@ -513,7 +562,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(DPGO_SYM
     DPGO_STAMP_TILE(4);
     {
       const size_t base = (size_t)p0 * GEO::T;
-      dbl2* d2 = reinterpret_cast<dbl2*>(delta + base);
+      dbl2* d2 = reinterpret_cast<dbl2*>(dout + base);
       dbl2* h2 = reinterpret_cast<dbl2*>(Hd + base);
 #pragma unroll
       for (int it = 0; it < SPN::NIT; ++it) {
@@ -563,7 +612,10 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(DPGO_SYM
 #ifndef DPGO_UPDATE_WAVES_ML
 #define DPGO_UPDATE_WAVES_ML 3
 #endif
-template <int D, int R, int ML = 0>
+// DEF = 1 (kept directions, see above k_tcg_hess): delta and eta are not touched (null), the step length goes to `coef`.
+// (3, 5): the multilevel instance drops from 147 to 119 VGPRs; it stays at DPGO_UPDATE_WAVES_ML waves -- a fourth workgroup
+// per CU does not fit the LDS (4 x 41 088 bytes), and the grid, hence the order of the partial sums, is the reference's.
+template <int D, int R, int ML = 0, int DEF = 0>
 __global__ __launch_bounds__(kBlock)
     __attribute__((amdgpu_waves_per_eu(ML ? DPGO_UPDATE_WAVES_ML : (DPGO_UPDATE_WAVES ? DPGO_UPDATE_WAVES : 1),
                                        ML ? DPGO_UPDATE_WAVES_ML : (DPGO_UPDATE_WAVES ? DPGO_UPDATE_WAVES : 8))))
@@ -576,7 +628,8 @@ void k_tcg_update_span(const double* __restrict__ X, const double* __restrict__ 
                                                             double* __restrict__ pout, const DevState* __restrict__ sin,
                                                             DevState* __restrict__ sout, int first, int n,
                                                             unsigned long long* hflag, unsigned gen,
-                                                            double ml_omega, float* __restrict__ z32 = nullptr) {
+                                                            double ml_omega, double* __restrict__ coef,
+                                                            float* __restrict__ z32 = nullptr) {
   // ml_omega > 0 (fused multilevel preconditioner): z receives the pre-smoothing step w Dinv r, unprojected -- into z32
   // instead, rounded to fp32, when the cycle keeps its internal vectors in that storage (kernel-uniform)
   using GEO = Geo<D, R>;
@@ -606,8 +659,8 @@ void k_tcg_update_span(const double* __restrict__ X, const double* __restrict__ 
     const size_t base = (size_t)p0 * GEO::T;
     const dbl2* X2 = reinterpret_cast<const dbl2*>(X + base);
     const dbl2* g2 = reinterpret_cast<const dbl2*>(g + base);
-    const dbl2* e2 = reinterpret_cast<const dbl2*>(eta + base);
-    const dbl2* d2 = reinterpret_cast<const dbl2*>(delta + base);
+    [[maybe_unused]] const dbl2* e2 = reinterpret_cast<const dbl2*>(eta + base);
+    [[maybe_unused]] const dbl2* d2 = reinterpret_cast<const dbl2*>(delta + base);
     const dbl2* h2 = reinterpret_cast<const dbl2*>(Hd + base);
     const dbl2* r2 = reinterpret_cast<const dbl2*>(r + base);
 #pragma unroll
@@ -620,8 +673,10 @@ void k_tcg_update_span(const double* __restrict__ X, const double* __restrict__ 
         if (first) {
           rv[it] = g2[pc];
         } else {
-          ev[it] = e2[pc];
-          dv[it] = d2[pc];
+          if constexpr (!DEF) {
+            ev[it] = e2[pc];
+            dv[it] = d2[pc];
+          }
           hv[it] = h2[pc];
           rv[it] = r2[pc];
         }
@@ -655,6 +710,7 @@ void k_tcg_update_span(const double* __restrict__ X, const double* __restrict__ 
   const int mode = tcg_update_prologue(st, pin, nb_in, first, red, alpha, tau, &praw);
   if (blockIdx.x == 0 && threadIdx.x == 0) {
     store_state(sout, st);
+    tcg_store_coef<DEF>(coef, st, mode, alpha, tau);
     publish_progress(hflag, gen, st);
   }
 
@@ -662,7 +718,7 @@ void k_tcg_update_span(const double* __restrict__ X, const double* __restrict__ 
   double part[2] = {0.0, 0.0};
   while (have) {
     const size_t base = (size_t)p0 * GEO::T;
-    dbl2* eta2 = reinterpret_cast<dbl2*>(eta + base);
+    [[maybe_unused]] dbl2* eta2 = reinterpret_cast<dbl2*>(eta + base);
     if (mode == 1) {  // workgroup-uniform: eta += tau * delta, then tCG stops
       // (r += tau * H delta with it: r = g + H eta holds at every exit of tCG, which is what the rho test reads, k_retract)
       dbl2* r2 = reinterpret_cast<dbl2*>(r + base);
@@ -670,12 +726,15 @@ void k_tcg_update_span(const double* __restrict__ X, const double* __restrict__ 
       for (int it = 0; it < SPN::NIT; ++it) {
         const int pc = lane + 64 * it;
         if (2 * pc < valid) {
-          dbl2 e = ev[it], rr = rv[it];
-          e.x = fma(tau, dv[it].x, e.x);
-          e.y = fma(tau, dv[it].y, e.y);
+          dbl2 rr = rv[it];
+          if constexpr (!DEF) {
+            dbl2 e = ev[it];
+            e.x = fma(tau, dv[it].x, e.x);
+            e.y = fma(tau, dv[it].y, e.y);
+            eta2[pc] = e;
+          }
           rr.x = fma(tau, hv[it].x, rr.x);
           rr.y = fma(tau, hv[it].y, rr.y);
-          eta2[pc] = e;
           r2[pc] = rr;
         }
       }
@@ -688,17 +747,21 @@ void k_tcg_update_span(const double* __restrict__ X, const double* __restrict__ 
           if (!ml_mode) reinterpret_cast<dbl2*>(ys)[pc] = xv[it];
           dbl2 rr = rv[it];
           if (mode == 2) {
-            dbl2 zero;
-            zero.x = 0.0;
-            zero.y = 0.0;
-            eta2[pc] = zero;
+            if constexpr (!DEF) {
+              dbl2 zero;
+              zero.x = 0.0;
+              zero.y = 0.0;
+              eta2[pc] = zero;
+            }
           } else {
-            dbl2 e = ev[it];
-            e.x = fma(alpha, dv[it].x, e.x);
-            e.y = fma(alpha, dv[it].y, e.y);
+            if constexpr (!DEF) {
+              dbl2 e = ev[it];
+              e.x = fma(alpha, dv[it].x, e.x);
+              e.y = fma(alpha, dv[it].y, e.y);
+              eta2[pc] = e;
+            }
             rr.x = fma(alpha, hv[it].x, rr.x);
             rr.y = fma(alpha, hv[it].y, rr.y);
-            eta2[pc] = e;
           }
           r2[pc] = rr;
           reinterpret_cast<dbl2*>(rs)[pc] = rr;
@@ -768,7 +831,7 @@ void k_tcg_update_span(const double* __restrict__ X, const double* __restrict__ 
 // initialisation r = g, eta = 0, z = P(r)):
 //   d_Hd (from k_hess partials) -> alpha, e_Pe';  boundary / negative curvature -> eta += tau*delta, r += tau*Hd, stop
 //   else eta += alpha*delta; r += alpha*Hd; z = P(r);  partials: [0] <r,r>  [1] <z,r>
-template <int D, int R>
+template <int D, int R, int DEF = 0>
 __global__ __launch_bounds__(kBlock, DPGO_LB_UPDATE) void k_tcg_update(const double* __restrict__ X, const double* __restrict__ g,
                                                        const double* __restrict__ dinv,
                                                        const double* __restrict__ delta,
@@ -777,7 +840,8 @@ __global__ __launch_bounds__(kBlock, DPGO_LB_UPDATE) void k_tcg_update(const dou
                                                        const double* __restrict__ pin, int nb_in,
                                                        double* __restrict__ pout, const DevState* __restrict__ sin,
                                                        DevState* __restrict__ sout, int first, int n,
-                                                       unsigned long long* hflag, unsigned gen, double ml_omega) {
+                                                       unsigned long long* hflag, unsigned gen, double ml_omega,
+                                                       double* __restrict__ coef) {
   // generic layout (odd tile size); even tile sizes run k_tcg_update_span
   using GEO = Geo<D, R>;
   __shared__ __attribute__((aligned(16))) double sm[kWaves][3][GEO::G][GEO::T];
@@ -796,6 +860,7 @@ __global__ __launch_bounds__(kBlock, DPGO_LB_UPDATE) void k_tcg_update(const dou
   const int mode = tcg_update_prologue(st, pin, nb_in, first, red, alpha, tau);  // 0: step, 1: boundary step, 2: init
   if (blockIdx.x == 0 && threadIdx.x == 0) {
     store_state(sout, st);
+    tcg_store_coef<DEF>(coef, st, mode, alpha, tau);
     publish_progress(hflag, gen, st);
   }
 
@@ -810,17 +875,19 @@ __global__ __launch_bounds__(kBlock, DPGO_LB_UPDATE) void k_tcg_update(const dou
     if (mode == 1) {  // workgroup-uniform
       if (ok) {
         // (r += tau * H delta with it: r = g + H eta holds at every exit of tCG, which is what the rho test reads)
-        double e[R], dl[R], hd[R], rr[R];
-        load_col<R>(eta + off, e);
-        load_col<R>(delta + off, dl);
+        double hd[R], rr[R];
+        if constexpr (!DEF) {
+          double e[R], dl[R];
+          load_col<R>(eta + off, e);
+          load_col<R>(delta + off, dl);
+#pragma unroll
+          for (int a = 0; a < R; ++a) e[a] = fma(tau, dl[a], e[a]);
+          store_col<R>(eta + off, e);
+        }
         load_col<R>(Hd + off, hd);
         load_col<R>(r + off, rr);
 #pragma unroll
-        for (int a = 0; a < R; ++a) {
-          e[a] = fma(tau, dl[a], e[a]);
-          rr[a] = fma(tau, hd[a], rr[a]);
-        }
-        store_col<R>(eta + off, e);
+        for (int a = 0; a < R; ++a) rr[a] = fma(tau, hd[a], rr[a]);
         store_col<R>(r + off, rr);
       }
       continue;
@@ -838,22 +905,26 @@ __global__ __launch_bounds__(kBlock, DPGO_LB_UPDATE) void k_tcg_update(const dou
       }
       if (mode == 2) {
         load_col<R>(g + off, rr);
-        double e[R];
+        if constexpr (!DEF) {
+          double e[R];
 #pragma unroll
-        for (int a = 0; a < R; ++a) e[a] = 0.0;
-        store_col<R>(eta + off, e);
+          for (int a = 0; a < R; ++a) e[a] = 0.0;
+          store_col<R>(eta + off, e);
+        }
       } else {
-        double e[R], dl[R], hd[R];
-        load_col<R>(eta + off, e);
-        load_col<R>(delta + off, dl);
+        double hd[R];
+        if constexpr (!DEF) {
+          double e[R], dl[R];
+          load_col<R>(eta + off, e);
+          load_col<R>(delta + off, dl);
+#pragma unroll
+          for (int a = 0; a < R; ++a) e[a] = fma(alpha, dl[a], e[a]);
+          store_col<R>(eta + off, e);
+        }
         load_col<R>(Hd + off, hd);
         load_col<R>(r + off, rr);
 #pragma unroll
-        for (int a = 0; a < R; ++a) {
-          e[a] = fma(alpha, dl[a], e[a]);
-          rr[a] = fma(alpha, hd[a], rr[a]);
-        }
-        store_col<R>(eta + off, e);
+        for (int a = 0; a < R; ++a) rr[a] = fma(alpha, hd[a], rr[a]);
       }
       store_col<R>(r + off, rr);
 #pragma unroll

@@ -273,7 +273,10 @@ int launch_hess(dpgo_problem_s* p, const double* X, const double* S, const doubl
 }
 
 int launch_retract(dpgo_problem_s* p, const double* X, const double* eta, double scale, double* X2,
-                   const DevState* st, const double* rho_r, const double* rho_g) {
+                   const DevState* st, const double* rho_r, const double* rho_g, bool from_dirs) {
+  // from_dirs (the RTR step of a solve that kept tCG's directions): eta is formed from the handle's direction ring instead
+  // of being loaded, and written to p->eta when the rho test does not come from these sums -- the DPGO_RHO_EXACT tail
+  // applies H to it; nothing else reads tCG's iterate after the step
   // (50 VGPRs, 64 with the rho test's sums: not bound to the update kernel's grid -- at most DPGO_GRID_RETRACT workgroups, 1 024 by default; 512 / 1 024 / 1 563 measured 259.4 / 261.4 / 260.0 it/s)
   int gr = std::min(pose_tiles(p->n, p->b), options().grid_retract > 0 ? options().grid_retract : kMaxGrid);
   // rho_r, rho_g (the RTR step: tCG's residual and the gradient it started from): the rho test's two sums go to pH(), one
@@ -284,9 +287,17 @@ int launch_retract(dpgo_problem_s* p, const double* X, const double* eta, double
     gr = std::min(gr, kPartialCap);
     p->nb_hess = gr;
   }
+  if (from_dirs && (!p->dirs || !p->dirs_coef || scale != 1.0))
+    return fail(DPGO_ERR_STATE, "the retraction from kept directions is the RTR step of a solve that kept them");
   CHK(dispatch_dr(p->d, p->r, [&](auto D, auto R) {
-    if (rho) return launch(k_retract<D, R, true>, gr, 0, p->stream, X, eta, scale, X2, st, p->n, rho_r, rho_g, p->pH());
-    return launch(k_retract<D, R, false>, gr, 0, p->stream, X, eta, scale, X2, st, p->n, nullptr, nullptr, nullptr);
+    auto go = [&](auto kernel) {
+      return launch(kernel, gr, 0, p->stream, X, from_dirs ? nullptr : eta, scale, X2, st, p->n, rho ? rho_r : nullptr,
+                    rho ? rho_g : nullptr,
+                    rho ? p->pH() : nullptr, from_dirs ? p->dirs.get() : nullptr, from_dirs ? p->dirs_coef.get() : nullptr,
+                    (from_dirs && !rho) ? p->eta.get() : nullptr);
+    };
+    if (from_dirs) return rho ? go(k_retract<D, R, true, true>) : go(k_retract<D, R, false, true>);
+    return rho ? go(k_retract<D, R, true>) : go(k_retract<D, R, false>);
   }));
   HIPC(hipGetLastError());
   return DPGO_OK;
@@ -544,6 +555,11 @@ int dpgo_problem_set_Q_bsr(dpgo_problem_t p, int nnzb, const int32_t* rowptr, co
       ml_free(p);
     }
     sym_free(p);
+    // (another problem: its solves size tCG's direction ring afresh, tcg_dirs_ensure)
+    p->dirs = DevBuf<double>();
+    p->dirs_coef = DevBuf<double>();
+    p->dirs_cap = 0;
+    p->dirs_on = false;
   }
   p->sym.ready = p->tcg_sym = false;
   p->ml_ready = false;  // the hierarchy's values belong to the old Q: rebuilt on the device at the next use

@@ -13,19 +13,23 @@ int launch_tcg_update(dpgo_problem_s* p, const double* dinv, int first, double* 
   CHK(dispatch_dr(p->d, p->r, [&](auto Dc, auto Rc) {
     constexpr int D = decltype(Dc)::value, R = decltype(Rc)::value;
     // (the span kernels end in the fp32 output, the generic one has none)
+    // (a solve that keeps its directions: the deferred instances get neither delta nor eta, only the step-length array)
+    const bool def = p->dirs_on;
     auto go = [&](auto kernel, auto... z32_arg) {
-      return launch(kernel, g, 0, p->stream, p->x1, p->g1, dinv, p->delta, p->Hd, p->eta, p->rr, zt, p->pA(), p->grid_s(),
-                    p->pB(), p->dstate + p->cur, p->dstate + (p->cur ^ 1), first, p->n, p->hflag, p->gen, ml_omega,
+      return launch(kernel, g, 0, p->stream, p->x1, p->g1, dinv, def ? nullptr : p->delta.get(), p->Hd,
+                    def ? nullptr : p->eta.get(), p->rr, zt, p->pA(), p->grid_s(), p->pB(), p->dstate + p->cur,
+                    p->dstate + (p->cur ^ 1), first, p->n, p->hflag, p->gen, ml_omega, def ? p->dirs_coef.get() : nullptr,
                     z32_arg...);
     };
     if constexpr (Span<D, R, 1>::kOk) {
       // (its own instance for the multilevel mode: 3 waves per SIMD)
+      if (def) return go(ml_mode ? k_tcg_update_span<D, R, 1, 1> : k_tcg_update_span<D, R, 0, 1>, z32);
       return go(ml_mode ? k_tcg_update_span<D, R, 1> : k_tcg_update_span<D, R, 0>, z32);
     } else {
       // (odd tile size: the generic kernel has no fp32 output -- resolve_tcg_storage keeps such blocks off the symmetric
       // storage, hence off the cycle's fp32 vectors; a state that says otherwise is refused instead of dropping z32)
       if (z32) return fail(DPGO_ERR_STATE, "fp32 cycle vectors need the span kernels (even pose tile size)");
-      return go(k_tcg_update<D, R>);
+      return def ? go(k_tcg_update<D, R, 1>) : go(k_tcg_update<D, R>);
     }
   }));
   HIPC(hipGetLastError());
@@ -36,23 +40,30 @@ int launch_tcg_update(dpgo_problem_s* p, const double* dinv, int first, double* 
 // fused direction update + Riemannian Hessian-vector product (one tCG step)
 // the tCG-step kernel: span variant whenever the pose tile size is even (all 3-D cases)
 // f(kernel, Q in the storage that kernel reads) for the instance this handle's state selects
+// (DEF: the instances of a solve that keeps its directions -- their `delta` is the direction ring, kernels/tcg.h)
+template <int D, int R, int DEF, class F>
+int dispatch_tcg_hess_mode(const dpgo_problem_s* p, F&& f) {
+  if constexpr (Span<D, R, 1>::kOk) {
+    if (p->tcg_sym) return f(p->stream_nt ? k_tcg_hess_sym<D, R, 1, DEF> : k_tcg_hess_sym<D, R, 0, DEF>, p->sym.dev());
+    if (p->stream_nt && p->split == 1) return f(k_tcg_hess_span<D, R, 1, 1, DEF>, p->Q.dev());
+    return dispatch_split(p->split, [&](auto Sc) { return f(k_tcg_hess_span<D, R, decltype(Sc)::value, 0, DEF>, p->Q.dev()); });
+  } else {
+    return dispatch_split(p->split, [&](auto Sc) { return f(k_tcg_hess<D, R, decltype(Sc)::value, DEF>, p->Q.dev()); });
+  }
+}
 template <int D, int R, class F>
 int dispatch_tcg_hess(const dpgo_problem_s* p, F&& f) {
-  if constexpr (Span<D, R, 1>::kOk) {
-    if (p->tcg_sym) return f(p->stream_nt ? k_tcg_hess_sym<D, R, 1> : k_tcg_hess_sym<D, R, 0>, p->sym.dev());
-    if (p->stream_nt && p->split == 1) return f(k_tcg_hess_span<D, R, 1, 1>, p->Q.dev());
-    return dispatch_split(p->split, [&](auto Sc) { return f(k_tcg_hess_span<D, R, decltype(Sc)::value>, p->Q.dev()); });
-  } else {
-    return dispatch_split(p->split, [&](auto Sc) { return f(k_tcg_hess<D, R, decltype(Sc)::value>, p->Q.dev()); });
-  }
+  return p->dirs_on ? dispatch_tcg_hess_mode<D, R, 1>(p, f) : dispatch_tcg_hess_mode<D, R, 0>(p, f);
 }
 
 int launch_tcg_hess_with(dpgo_problem_s* p, const DevState* sin, DevState* sout, int first, unsigned long long* hflag,
                          unsigned gen) {  // (the state slots and the progress word of the caller's choice: kernel probes)
+  if (p->dirs_on && !p->dirs) return fail(DPGO_ERR_STATE, "deferred tCG launch without a direction ring");
+  double* dl = p->dirs_on ? p->dirs.get() : p->delta.get();
   CHK(dispatch_dr(p->d, p->r, [&](auto Dc, auto Rc) {
     constexpr int D = decltype(Dc)::value, R = decltype(Rc)::value;
     return dispatch_tcg_hess<D, R>(p, [&](auto kernel, const auto& Q) {
-      return launch(kernel, p->grid_s(), 0, p->stream, Q, p->x1, p->S1, p->z, p->delta, p->Hd, p->pB(), p->nb_zr(), p->pA(),
+      return launch(kernel, p->grid_s(), 0, p->stream, Q, p->x1, p->S1, p->z, dl, p->Hd, p->pB(), p->nb_zr(), p->pA(),
                     sin, sout, first, p->n, hflag, gen);
     });
   }));
@@ -83,6 +94,36 @@ int resolve_tcg_storage(dpgo_problem_s* p) {
   bool usable = false;
   CHK(sym_ensure(p, &usable));
   p->tcg_sym = usable;
+  return DPGO_OK;
+}
+
+// Whether the coming multi-launch RTR solve keeps tCG's directions (kernels/tcg.h, DEF) -- decided here, once per solve:
+// yes when DPGO_TCG_DIRS is not 0 and a ring of max(1, max_inner) pose vectors fits DPGO_TCG_DIRS_MAX_MB and the device
+// (the state record's max_inner is the solve's RTR_tCG_iterations and the last slot a run writes is max_inner - 1, so the
+// ring holds every slot a kernel can address).  The ring and its step lengths are allocated on first use and grown when a
+// solve has a larger budget; a ring that cannot be allocated leaves the handle without one and the solve on p->delta / p->eta.
+// may_alloc = false (the kernel probes, which address slots 0 and 1): deferred only on the ring a solve has left.
+int tcg_dirs_ensure(dpgo_problem_s* p, int max_inner, bool may_alloc) {
+  p->dirs_on = false;
+  if (options().tcg_dirs == 0) return DPGO_OK;
+  const int slots = std::max(1, max_inner);
+  const size_t slot = (size_t)p->n * p->T;
+  if ((double)slots * (double)slot * sizeof(double) > (double)std::max(0, options().tcg_dirs_max_mb) * 1048576.0) return DPGO_OK;
+  if (slots > p->dirs_cap || !p->dirs || !p->dirs_coef) {
+    if (!may_alloc) return DPGO_OK;
+    p->dirs = DevBuf<double>();  // (released first: the old and the new ring never exist side by side)
+    p->dirs_coef = DevBuf<double>();
+    p->dirs_cap = 0;
+    if (p->dirs.alloc((size_t)slots * slot) != DPGO_OK || p->dirs_coef.alloc((size_t)slots + 1) != DPGO_OK) {
+      (void)hipGetLastError();  // (out of memory is not an error of the solve)
+      p->dirs = DevBuf<double>();
+      p->dirs_coef = DevBuf<double>();
+      return DPGO_OK;
+    }
+    HIPC(hipMemsetAsync(p->dirs_coef, 0, sizeof(double) * ((size_t)slots + 1), p->stream));
+    p->dirs_cap = slots;
+  }
+  p->dirs_on = true;
   return DPGO_OK;
 }
 
@@ -414,8 +455,9 @@ int rtr_outer_iteration(dpgo_problem_s* p, const dpgo_ropt_params* prm, const do
   // between tCG and here writes r: the cycle only reads it), summed by the retraction from the eta it loads anyway.
   // DPGO_RHO_EXACT=1: from a fresh H eta instead, one more pass over Q (the reference path of the tests).
   const bool rho_exact = options().rho_exact != 0;
+  // (a solve that kept its directions: the retraction forms eta from them, and leaves it in p->eta for the exact tail)
   CHK(launch_retract(p, p->x1, p->eta, 1.0, p->x2, p->dstate + p->cur, rho_exact ? nullptr : p->rr.get(),
-                     rho_exact ? nullptr : p->g1.get()));
+                     rho_exact ? nullptr : p->g1.get(), p->dirs_on));
   CHK(launch_grad(p, p->x2, p->g2, p->S2, nullptr, p->dstate + p->cur, p->tcg_sym && outer_sym_enabled()));
   cnt.spmm += 1;
   if (rho_exact) {
@@ -542,6 +584,7 @@ int run_optimize(dpgo_problem_s* p, const dpgo_ropt_params* prm, dpgo_ropt_resul
   res->tCGStatus = DPGO_TCG_MAXITER;
   const bool resume = phase == RUN_END;
   if (p->hctrl && !resume) std::memset(p->hctrl, 0, sizeof(PersistCtrl));
+  if (!resume) p->dirs_on = false;  // (the one-launch solve keeps its vectors on chip)
   struct SlotGuard {  // the resident-slot reservation of the persistent kernel lives as long as the solve
     dpgo_problem_s* p;
     bool armed;
@@ -651,6 +694,9 @@ int run_optimize(dpgo_problem_s* p, const dpgo_ropt_params* prm, dpgo_ropt_resul
         std::fprintf(stderr, "dpgo_hip: persistent solve timed out; this handle continues with the multi-launch scheme\n");
     }
   }
+  // the multi-launch scheme from here on: whether this solve's tCG runs keep their directions (every launch follows it)
+  p->dirs_on = false;
+  if (prm->method == DPGO_METHOD_RTR) CHK(tcg_dirs_ensure(p, prm->RTR_tCG_iterations));
   // statistics before optimisation (:28-29) -- one fused pass: f, rgrad, S
   CHK(launch_grad(p, p->x1, p->g1, p->S1, nullptr, nullptr, prm->method == DPGO_METHOD_RTR && p->tcg_sym && outer_sym_enabled()));
   cnt.spmm += 1;
@@ -1185,6 +1231,14 @@ int dpgo_problem_tcg_kernel_info(dpgo_problem_t p, int* symmetric, int* split, i
   if (symmetric) *symmetric = p->tcg_sym ? 1 : 0;
   if (split) *split = p->tcg_sym ? 1 : p->split;
   if (stream_nt) *stream_nt = (p->stream_nt && (p->tcg_sym || p->split == 1)) ? 1 : 0;
+  return DPGO_OK;
+}
+
+
+int dpgo_problem_tcg_directions_info(dpgo_problem_t p, int* deferred, int* slots) {
+  if (!p) return fail(DPGO_ERR_INVALID, "null handle");
+  if (deferred) *deferred = p->dirs_on ? 1 : 0;
+  if (slots) *slots = p->dirs ? p->dirs_cap : 0;
   return DPGO_OK;
 }
 

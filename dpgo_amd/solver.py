@@ -521,10 +521,15 @@ class QuadraticProblem:
         L.check(self._lib.dpgo_problem_set_persistent(self._h, int(enable)))
 
     def tcgKernelInfo(self) -> dict:
-        """{"symmetric", "split", "stream_nt"}: the instance of the tCG-step kernel the next multi-launch solve runs."""
+        """{"symmetric", "split", "stream_nt"}: the instance of the tCG-step kernel the next multi-launch solve runs;
+        {"directions", "direction_slots"}: whether the last solve kept tCG's directions and summed eta once in the
+        retraction (False: eta += alpha delta every iteration, or a one-launch solve), and the slots of the handle's ring."""
         v = [C.c_int(0) for _ in range(3)]
         L.check(self._lib.dpgo_problem_tcg_kernel_info(self._h, *[C.byref(x) for x in v]))
-        return dict(symmetric=bool(v[0].value), split=v[1].value, stream_nt=bool(v[2].value))
+        w = [C.c_int(0) for _ in range(2)]
+        L.check(self._lib.dpgo_problem_tcg_directions_info(self._h, *[C.byref(x) for x in w]))
+        return dict(symmetric=bool(v[0].value), split=v[1].value, stream_nt=bool(v[2].value),
+                    directions=bool(w[0].value), direction_slots=w[1].value)
 
     def persistentInfo(self) -> dict:
         """{"enabled", "workgroups", "last_members", "last_iterations", "last_split", "last_tiles"}: last_members = 0

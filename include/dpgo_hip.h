@@ -478,6 +478,13 @@ int dpgo_problem_set_spmm_variant(dpgo_problem_t h, int variant, int* in_use);
  * non-temporal instance together when the tCG loop's working set -- Q, eight pose vectors and what the last solve's
  * preconditioner streams -- exceeds the 256 MB Infinity Cache; DPGO_SPMM_SYMMETRIC / DPGO_STREAM_NT = 0 / 1 override. */
 int dpgo_problem_tcg_kernel_info(dpgo_problem_t h, int* symmetric, int* split, int* stream_nt);
+/* Kept directions (multi-launch RTR solves).  Nothing inside a tCG run reads the iterate eta, so a solve whose
+ * RTR_tCG_iterations pose vectors fit DPGO_TCG_DIRS_MAX_MB (4096) keeps the search directions in a ring of the handle and
+ * k_retract sums eta = sum_k c_k delta_k once, in the order and with the fused multiply-adds of the running sum: the same
+ * bits, 48 MB less traffic per tCG iteration at 100k poses.  DPGO_TCG_DIRS=0, or a ring that does not fit, runs the
+ * reference path (eta += alpha delta every iteration).  deferred = 1: the last solve of the handle kept its directions
+ * (0: reference path, or a one-launch solve); slots = pose vectors the ring holds (0: none allocated). */
+int dpgo_problem_tcg_directions_info(dpgo_problem_t h, int* deferred, int* slots);
 /* time `reps` back-to-back SpMM launches with HIP events on the handle's stream;
  * n_buffers >= 1 rotates that many (V, OUT) buffer pairs; returns average ms per launch */
 int dpgo_bench_spmm(dpgo_problem_t h, int reps, int warmup, double* avg_ms);
