@@ -53,6 +53,24 @@ class PGOAgentStatus:
     relativeChange: float = 0.0
 
 
+@dataclass
+class AlignmentRecord:
+    """One attempt of a waiting agent to find its frame from one neighbour (C ABI dpgo_average_result): what
+    computeRobustNeighborTransformTwoStage reports and returns (src/PGOAgent.cpp:550-602)."""
+    agent: int
+    neighbour: int
+    status: str       # "OK", "EMPTY", "INVALID", "FEW_INLIERS"
+    inliers: int
+    candidates: int
+    iterations: int   # GNC iterations (0: the residuals were small and GNC was skipped)
+    mu: float
+    T_world_robot: np.ndarray  # tile [d+1, d]
+
+    @property
+    def ok(self) -> bool:
+        return self.status == "OK"
+
+
 def should_terminate(iteration: int, prm: PGOAgentParameters, weight_update_count: int,
                      team: Dict[int, PGOAgentStatus], num_robots: int, inactive=()) -> bool:
     """PGOAgent::shouldTerminate (src/PGOAgent.cpp:846-878); robots in `inactive` (PGOAgent::setRobotActive(id, false),
@@ -260,6 +278,133 @@ class DeviceAgent(AgentStatusMixin):
         self.acceleration = False
         self.iteration = 0
         self.tcg_total = 0
+        self.state = "INITIALIZED"  # (PGOAgentState: X0 is given in the global frame; from_local_frame starts earlier)
+
+    # ---- start in the agent's own frame (PGOAgent::initialize, src/PGOAgent.cpp:281-301, and what follows it) ----
+    @classmethod
+    def from_local_frame(cls, graphs: Sequence[PoseGraph], plan: ExchangePlan, my_id: int, T_local_tiles: np.ndarray,
+                         YLift: Optional[np.ndarray] = None, params: Optional[ROptParameters] = None, device: int = 0):
+        """An agent in state WAIT_FOR_INITIALIZATION: it holds TLocalInit -- its trajectory in its own frame, tiles
+        [n, d+1, d], moved so that its first pose is the identity (src/PGOAgent.cpp:281-289) -- on the device and an
+        iterate that means nothing yet.  try_initialize_from(neighbour) / initializeInGlobalFrame() move it into the global
+        frame; robot 0 IS the global frame and is initialised here (:299-301).  YLift (r x d, default [I_d; 0]: what
+        synthetic.lift_tiles applies) must be the same for the whole team."""
+        n = graphs[my_id].n()
+        d, r = graphs[my_id].d(), graphs[my_id].r()
+        T = np.ascontiguousarray(T_local_tiles, dtype=np.float64)
+        if T.shape != (n, d + 1, d):
+            raise ValueError("local trajectory has shape %s, expected %s" % (T.shape, (n, d + 1, d)))
+        ag = cls(graphs, plan, my_id, np.zeros((n, d + 1, r)), params, device)
+        torch = ag.torch
+        ag.state = "WAIT_FOR_INITIALIZATION"
+        if YLift is None:
+            YLift = np.eye(r, d)
+        YLift = np.asarray(YLift, dtype=np.float64)
+        if YLift.shape != (r, d):
+            raise ValueError("YLift has shape %s, expected %s" % (YLift.shape, (r, d)))
+        ag.YLift = np.ascontiguousarray(YLift.T)  # [d, r]: column-major r x d, the layout the C ABI takes
+        # T_0i = inv(T_w0) T_wi: tiles hold R^T and t, so R_0i^T = R_i^T R_0 and t_0i = R_0^T (t_i - t_0)
+        R0 = T[0, :d, :].T
+        Tn = np.empty_like(T)
+        Tn[:, :d, :] = T[:, :d, :] @ R0
+        Tn[:, d, :] = (T[:, d, :] - T[0, d, :]) @ R0
+        if ag.pose_order is not None:  # internal row of every caller frame, as X0 in __init__
+            Ti = np.empty_like(Tn)
+            Ti[ag.pose_order] = Tn
+            Tn = Ti
+        ag.T_local = torch.tensor(Tn, dtype=torch.float64, device=ag.device)
+        # shared-edge tables, grouped by neighbour (ascending id), uploaded once
+        m = ag.pg.sharedLoopClosures()
+        slot_of = {pid: k for k, pid in enumerate(plan.slots[my_id])}
+        out = m.r1 == my_id
+        nb_robot = np.where(out, m.r2, m.r1).astype(np.int64)
+        nb_frame = np.where(out, m.p2, m.p1).astype(np.int64)
+        order = np.argsort(nb_robot, kind="stable")
+        i32 = lambda a: torch.tensor(np.ascontiguousarray(a, dtype=np.int32), dtype=torch.int32, device=ag.device)
+        f64 = lambda a: torch.tensor(np.ascontiguousarray(a, dtype=np.float64), dtype=torch.float64, device=ag.device)
+        ag.align_my_pose = i32(np.where(out, m.p1, m.p2)[order])
+        ag.align_slot = i32([slot_of[(int(nb_robot[e]), int(nb_frame[e]))] for e in order])
+        ag.align_incoming = torch.tensor(np.ascontiguousarray(~out[order], dtype=np.uint8), dtype=torch.uint8, device=ag.device)
+        ag.align_R, ag.align_t = f64(m.R[order]), f64(m.t[order])
+        ag.align_range = {}  # neighbour -> its range of the tables
+        for k, q in enumerate(nb_robot[order]):
+            lo, _hi = ag.align_range.get(int(q), (k, k))
+            ag.align_range[int(q)] = (lo, k + 1)
+        ms = max(len(m), 1)
+        ag.align_cand = torch.zeros((ms, d + 1, d), dtype=torch.float64, device=ag.device)
+        ag.align_weights = torch.zeros(ms, dtype=torch.float64, device=ag.device)
+        nq = max(len(ag.align_range), 1)
+        # per neighbour: the CSR offsets [0, count] of its one group and its result record (dpgo_average_result)
+        ag.align_ptr = i32([[0, hi - lo] for _q, (lo, hi) in sorted(ag.align_range.items())] or [[0, 0]])
+        import ctypes as C
+        ag.align_records = torch.zeros((nq, C.sizeof(L.AverageResultC)), dtype=torch.uint8, device=ag.device)
+        ag.align_index = {q: k for k, q in enumerate(sorted(ag.align_range))}
+        if my_id == 0:
+            ag.initializeInGlobalFrame()
+        return ag
+
+    def _stream(self):
+        return self.torch.cuda.current_stream().cuda_stream or None
+
+    def _entered_global_frame(self) -> None:
+        """The host half of PGOAgent::initializeInGlobalFrame (src/PGOAgent.cpp:340-365): state, auxiliary sequences."""
+        self.state = "INITIALIZED"
+        if self.acceleration:  # initializeAcceleration (:899-908): XPrev = Y = V = X
+            for buf in (self.XPrev, self.Y, self.V):
+                buf.copy_(self.X)
+            self.gamma = self.alpha = 0.0
+        elif hasattr(self, "XPrev"):
+            self.XPrev.copy_(self.X)
+
+    def initializeInGlobalFrame(self, T_world_robot: Optional[np.ndarray] = None) -> None:
+        """PGOAgent::initializeInGlobalFrame (src/PGOAgent.cpp:308-352) with a transform the host knows: X = YLift
+        (T_world_robot T_local), tile [d+1, d], default the identity (robot 0, or multi-robot initialisation off)."""
+        T = np.zeros((self.d + 1, self.d))
+        T[:self.d] = np.eye(self.d)
+        if T_world_robot is not None:
+            T = np.ascontiguousarray(T_world_robot, dtype=np.float64)
+            if T.shape != (self.d + 1, self.d):
+                raise ValueError("T_world_robot has shape %s, expected %s" % (T.shape, (self.d + 1, self.d)))
+        L.check(self.problem._lib.dpgo_lift_in_frame_device(self.r, self.d, self.n, L.ptr(self.YLift), L.ptr(self.T_local),
+                                                            None, L.ptr(T), L.ptr(self.X), self._stream()))
+        self._entered_global_frame()
+
+    def try_initialize_from(self, neighbour_id: int, two_stage: bool = True, min_inliers: int = 2) -> "AlignmentRecord":
+        """What PGOAgent::updateNeighborPoses does for a waiting agent when the public poses of an initialised neighbour
+        have arrived (src/PGOAgent.cpp:658-663), enqueued on the agent's stream behind the exchange that filled the
+        neighbour buffer: candidates from the loop closures shared with that neighbour, their robust average, the lift --
+        which the device skips unless the record says OK.  One small read-back: the record."""
+        from .initialization import average_params
+        q = int(neighbour_id)
+        if q not in self.align_range:
+            raise ValueError("agent %d shares no loop closure with robot %d" % (self.id, q))
+        lo, hi = self.align_range[q]
+        k = self.align_index[q]
+        lib, s = self.problem._lib, self._stream()
+        prm = average_params(two_stage, min_inliers=min_inliers)
+        cand, w = self.align_cand[lo:hi], self.align_weights[lo:hi]
+        rec = self.align_records[k]
+        L.check(lib.dpgo_neighbor_candidates_device(
+            self.r, self.d, hi - lo, L.ptr(self.YLift), L.ptr(self.T_local), L.ptr(self.nbr), L.ptr(self.align_my_pose[lo:hi]),
+            L.ptr(self.align_slot[lo:hi]), L.ptr(self.align_incoming[lo:hi]), L.ptr(self.align_R[lo:hi]),
+            L.ptr(self.align_t[lo:hi]), L.ptr(cand), s))
+        import ctypes as C
+        L.check(lib.dpgo_robust_average_device(self.d, 1, L.ptr(self.align_ptr[k]), L.ptr(cand), None, None, C.byref(prm),
+                                               L.ptr(w), L.ptr(rec), s))
+        L.check(lib.dpgo_lift_in_frame_device(self.r, self.d, self.n, L.ptr(self.YLift), L.ptr(self.T_local), L.ptr(rec),
+                                              None, L.ptr(self.X), s))
+        c = L.AverageResultC.from_buffer_copy(rec.cpu().numpy().tobytes())
+        out = AlignmentRecord(self.id, q, L.AVERAGE_STATUS[c.status], c.inliers, c.candidates, c.iterations, c.mu,
+                              np.array(c.T[:(self.d + 1) * self.d]).reshape(self.d + 1, self.d))
+        if out.ok:
+            self._entered_global_frame()
+        return out
+
+    def alignment_weights(self, neighbour_id: int) -> np.ndarray:
+        """GNC weights of the candidates of the last try_initialize_from(neighbour), in the order of the agent's shared
+        loop closures with that neighbour (PoseGraph.sharedLoopClosures order)."""
+        lo, hi = self.align_range[int(neighbour_id)]
+        return self.align_weights[lo:hi].cpu().numpy()
 
     def enable_acceleration(self, num_robots: int, restart_interval: int = 30) -> None:
         """PGOAgent::initializeAcceleration (src/PGOAgent.cpp:899-908); restartInterval default 30
@@ -475,6 +620,52 @@ class RBCDCluster:
             if hasattr(ag, "setRobotActive"):
                 ag.setRobotActive(robot_id, active)
 
+    # ---- agents that start in their own frames (DeviceAgent.from_local_frame) ----
+    def waiting_agents(self) -> List[int]:
+        return sorted(a for a, ag in self.agents.items() if getattr(ag, "state", "INITIALIZED") != "INITIALIZED")
+
+    def _require_initialized(self, what: str) -> None:
+        waiting = self.waiting_agents()
+        if waiting:
+            raise RuntimeError("%s: agents %s are still in WAIT_FOR_INITIALIZATION (their iterates are not in the global "
+                               "frame); call initialize_in_global_frame() first" % (what, waiting))
+
+    def initialize_in_global_frame(self, min_inliers: int = 2, two_stage: bool = True, max_rounds: Optional[int] = None,
+                                   on_attempt=None):
+        """Bring every waiting agent into the global frame, round by round: the public poses are exchanged, then every
+        waiting agent tries the neighbours that were INITIALIZED before the round, in ascending id order -- the order
+        the updateNeighborPoses calls arrive in the reference's driver (examples/MultiRobotExample.cpp:183-204) --, and
+        the first success initialises it (PGOAgent::updateNeighborPoses, src/PGOAgent.cpp:658-663).  Stops when nobody
+        waits or a round makes no progress.  Returns ({agent: its last AlignmentRecord}, [agents still waiting]); never
+        raises for those.  on_attempt(record): called after every attempt (the example prints the reference's line)."""
+        if self.world > 1:
+            raise NotImplementedError("frame alignment across processes is not implemented (single-process clusters only)")
+        records: Dict[int, AlignmentRecord] = {}
+        rounds = 0
+        while max_rounds is None or rounds < max_rounds:
+            waiting = self.waiting_agents()
+            ready = {a for a in self.agents if a not in waiting}
+            if not waiting:
+                break
+            rounds += 1
+            self.exchange(None)
+            progress = False
+            for a in waiting:
+                ag = self.agents[a]
+                for q in self.plan.adj[a]:  # (ascending)
+                    if q not in ready:
+                        continue
+                    rec = ag.try_initialize_from(q, two_stage=two_stage, min_inliers=min_inliers)
+                    records[a] = rec
+                    if on_attempt is not None:
+                        on_attempt(rec)
+                    if rec.ok:
+                        progress = True
+                        break
+            if not progress:
+                break
+        return records, self.waiting_agents()
+
     def _active_ids(self, c: int):
         off = self.__dict__.get("inactive", ())
         return [a for a in self.agents if self.plan.colour[a] == c and a not in off]
@@ -649,6 +840,7 @@ class RBCDCluster:
         (concurrently when this process hosts several).  With status tracking (DeviceAgent.enable_status) and an
         iteration number, XPrev is saved before and the agents' relative changes are measured on the device after the
         solves, read back together (one small copy per phase) and turned into PGOAgentStatus records."""
+        self._require_initialized("phase")
         self.exchange(receivers=c)
         ids = self._active_ids(c)
         tracked = [a for a in ids if getattr(self.agents[a], "track_status", False)] if iteration is not None else []
@@ -710,6 +902,7 @@ class RBCDCluster:
         updated concurrently (C ABI dpgo_optimize_device_many: each on its own stream behind the exchange, one feeding
         host thread each), so a GPU that hosts several same-colour agents overlaps their latency-bound solves instead of
         running them one after the other."""
+        self._require_initialized("sweep")
         if self._stream_ordered_sweep():
             # ONE agent per colour on this process (the multi-GPU deployment: two agents per GPU): the whole sweep --
             # colour c's exchange, its solve, colour c+1's pack + exchange, ... -- is enqueued on one stream without a host
@@ -811,6 +1004,7 @@ class RBCDCluster:
         iterate(true); stop when the central gradnorm < 0.1; next = argmax of the block gradnorms.
         The central gradient block of agent a equals a's local gradient (SURVEY 8c'), so the selection is
         computed from agent-local evaluations + one tiny all-reduce instead of a central problem."""
+        self._require_initialized("run_greedy")
         selected, order, trace = 0, [], []
         for _ in range(max_iters):
             for a, agent in self.agents.items():

@@ -7,6 +7,7 @@
 //   solve.hip       QuadraticOptimizer::optimize: tCG launches, the one-launch solve, RTR outer loop, preconditioner
 //                   selection (DPGO_PRECOND_AUTO), concurrent / begin-end solves
 //   agents.hip      GNC re-weighting, initial guesses, manifold operations, public-pose exchange plans
+//   align.hip       frame alignment of agents that start in their own frames: candidates, robust average, lift
 //   bench_probes.hip  kernel timing probes used by bench.py
 //   certify.hip     certificate of global optimality (LOBPCG on C(X) = Q - Lambda(X)) and the staircase escape
 #pragma once

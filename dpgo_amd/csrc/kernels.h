@@ -30,6 +30,7 @@ namespace dpgo {
 #include "kernels/manifold.h"
 #include "kernels/rtr.h"
 #include "kernels/agent.h"
+#include "kernels/align.h"
 #include "kernels/init.h"
 #include "kernels/certify.h"
 

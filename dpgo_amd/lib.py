@@ -71,6 +71,21 @@ class ReweightStatsC(C.Structure):
                 ("max_rsq", C.c_double), ("cost", C.c_double)]
 
 
+AVERAGE_TWO_STAGE, AVERAGE_POSE = 0, 1  # DPGO_AVERAGE_* modes
+AVERAGE_OK, AVERAGE_EMPTY, AVERAGE_INVALID, AVERAGE_FEW_INLIERS = range(4)
+AVERAGE_STATUS = ["OK", "EMPTY", "INVALID", "FEW_INLIERS"]
+
+
+class AverageParamsC(C.Structure):
+    _fields_ = [("mode", C.c_int), ("barc", C.c_double), ("mu_step", C.c_double), ("mu_cap", C.c_double),
+                ("w_tol", C.c_double), ("max_iterations", C.c_int), ("min_inliers", C.c_int)]
+
+
+class AverageResultC(C.Structure):
+    _fields_ = [("status", C.c_int), ("inliers", C.c_int), ("candidates", C.c_int), ("iterations", C.c_int),
+                ("mu", C.c_double), ("T", C.c_double * 12)]
+
+
 CERT_CERTIFIED, CERT_NOT_CERTIFIED, CERT_NOT_CONVERGED = 0, 1, 2
 CERT_STATUS = ["CERTIFIED", "NOT_CERTIFIED", "NOT_CONVERGED"]
 
@@ -172,6 +187,11 @@ SIGNATURES = {
     "dpgo_flags_wait_device_checked": ([_I, _P, _P, C.c_longlong, _P, _P], _I),
     "dpgo_max_translation_distance_device": ([_I, _I, _I, _P, _P, _P, C.POINTER(_D), _P], _I),
     "dpgo_axpby_project_device": ([_I, _I, _I, _D, _P, _D, _P, _D, _P, _I, _P, _P], _I),
+    "dpgo_average_params_default": ([_I, C.POINTER(AverageParamsC)], None),
+    "dpgo_neighbor_candidates_device": ([_I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P], _I),
+    "dpgo_robust_average_device": ([_I, _I, _P, _P, _P, _P, C.POINTER(AverageParamsC), _P, _P, _P], _I),
+    "dpgo_robust_average": ([_I, _I, _P, _P, _P, _P, C.POINTER(AverageParamsC), _P, _P, _I], _I),
+    "dpgo_lift_in_frame_device": ([_I, _I, _I, _P, _P, _P, _P, _P, _P], _I),
     "dpgo_problem_set_persistent": ([_P, _I], _I),
     "dpgo_problem_persistent_info": ([_P, C.POINTER(_I), C.POINTER(_I), C.POINTER(_I), C.POINTER(_I), C.POINTER(_I)], _I),
     "dpgo_problem_persistent_phases": ([_P, _P, C.POINTER(_I)], _I),

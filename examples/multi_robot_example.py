@@ -9,12 +9,43 @@ the frame of robot 0's first pose (the global anchor, :249-254) is written as CS
 --robust-cost {L1,Huber,TLS,GM,GNC_TLS} runs the reference's robust agent protocol instead (coloured schedule, weight
 updates by PGOAgent::shouldUpdateMeasurementWeights, dpgo_amd.robust.DistributedRobustPGO) and prints the global robust
 cost of every weight update.
+
+--local-frames starts distributed: no centralised initialisation, every robot initialises in its own frame (odometry, or
+--local-init chordal) and joins robot 0's frame by robust frame alignment on the device, printing the reference's
+"Robot a attempts initialization from neighbor b: finds i/m inliers." for every attempt.
 """
 import argparse
 import os
 import sys
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+
+def local_frame_agents(args, meas, n, r):
+    """--local-frames: what the reference's agents do without a central initialisation.  Every robot computes a trajectory
+    from its OWN measurements in its own frame (PGOAgent::initialize, src/PGOAgent.cpp:219-289: odometry by default, or
+    chordal), robot 0's frame is the global one, and the others join it through their loop closures with an initialised
+    neighbour (computeRobustNeighborTransformTwoStage + initializeInGlobalFrame, :550-602, :308-352) -- on the device."""
+    import dpgo_amd
+    from dpgo_amd.agent import DeviceAgent, ExchangePlan, RBCDCluster, build_pose_graphs
+    from dpgo_amd.initialization import chordal_initialization, odometry_initialization
+    ranges, graphs = build_pose_graphs(meas, n, args.num_robots, r)
+    plan = ExchangePlan(graphs)
+    agents = {}
+    for a, pg in enumerate(graphs):
+        m = pg.measurements()
+        own = m.select((m.r1 == a) & (m.r2 == a))
+        if args.local_init == "chordal":
+            T_local = chordal_initialization(own, pg.n())
+        else:
+            T_local = odometry_initialization(own.select(own.p1 + 1 == own.p2), pg.n())
+        agents[a] = DeviceAgent.from_local_frame(graphs, plan, a, T_local, params=dpgo_amd.ROptParameters())
+    records, waiting = RBCDCluster(plan, agents).initialize_in_global_frame(on_attempt=lambda rec: print(
+        "Robot %d attempts initialization from neighbor %d: finds %d/%d inliers." % (
+            rec.agent, rec.neighbour, rec.inliers, rec.candidates)))  # (src/PGOAgent.cpp:583-584)
+    if waiting:
+        raise SystemExit("Robots %s found no neighbour to initialise from." % waiting)
+    return agents, graphs, plan
 
 
 def main():
@@ -31,6 +62,11 @@ def main():
                     help="robust agent protocol with this cost: weights re-computed on the device between blocks of iterations")
     ap.add_argument("--weight-updates", type=int, default=10, help="robustOptNumWeightUpdates")
     ap.add_argument("--inner-iterations", type=int, default=30, help="robustOptInnerIters")
+    ap.add_argument("--local-frames", action="store_true",
+                    help="every robot initialises from its own measurements, in its own frame, and joins the global frame "
+                         "through robust frame alignment with its neighbours (no centralised initialisation)")
+    ap.add_argument("--local-init", choices=["odometry", "chordal"], default="odometry",
+                    help="localInitializationMethod of --local-frames (include/DPGO/PGOAgent.h:134)")
     args = ap.parse_args()
     print("Multi-robot pose graph optimization example. ")
     if args.num_robots <= 0:
@@ -46,11 +82,14 @@ def main():
     meas, n = dpgo_amd.read_g2o_file(args.g2o)
     print("Loaded dataset from file %s." % args.g2o)
     r, d = args.rank, meas.d
-    X0 = lift_tiles(chordal_initialization(meas, n), r)  # PGOAgent's default: chordal initialisation
-    ranges, graphs = build_pose_graphs(meas, n, args.num_robots, r)
-    plan = ExchangePlan(graphs)
-    agents = {a: DeviceAgent(graphs, plan, a, X0[ranges[a][0]:ranges[a][1]], dpgo_amd.ROptParameters())
-              for a in range(args.num_robots)}
+    if args.local_frames:
+        agents, graphs, plan = local_frame_agents(args, meas, n, r)
+    else:
+        X0 = lift_tiles(chordal_initialization(meas, n), r)  # PGOAgent's default: chordal initialisation
+        ranges, graphs = build_pose_graphs(meas, n, args.num_robots, r)
+        plan = ExchangePlan(graphs)
+        agents = {a: DeviceAgent(graphs, plan, a, X0[ranges[a][0]:ranges[a][1]], dpgo_amd.ROptParameters())
+                  for a in range(args.num_robots)}
     if args.robust_cost:
         from dpgo_amd.agent import PGOAgentParameters
         from dpgo_amd.robust import DistributedRobustPGO, RobustCostParameters

@@ -686,6 +686,69 @@ int dpgo_axpby_project_device(int r, int d, int n, double a, const double* A_dev
                               const double* B_dev, double c, const double* C_dev, int project,
                               double* out_dev, void* stream);
 
+/* ---- Frame alignment of an agent that starts in its own frame ----
+ * A PGOAgent keeps a trajectory in its own frame (TLocalInit, src/PGOAgent.cpp:281-289) until public poses of an initialised
+ * neighbour arrive; every loop closure shared with that neighbour then gives one candidate for the transform from its frame
+ * to the global one (computeNeighborTransform, src/PGOAgent.cpp:515-548), the candidates are averaged robustly with GNC-TLS
+ * (computeRobustNeighborTransformTwoStage, :550-602, or computeRobustNeighborTransform, :604-648) and the trajectory is moved
+ * and lifted (initializeInGlobalFrame, :308-352).  Three launches on the caller's stream behind the public-pose exchange;
+ * the host reads one dpgo_average_result per (agent, neighbour) pair afterwards.  Transforms and local poses are tiles
+ * [d+1][d]: the d columns of the rotation, then the translation (what dpgo_round_trajectory writes).
+ * Alignment: these entries read and write caller buffers in 8-byte elements (the int32 / byte tables in their own), so
+ * any pointer with the alignment of its element type is ACCEPTED and gives the results of a 16-byte-aligned call. */
+#define DPGO_AVERAGE_TWO_STAGE 0 /* GNC on the rotations, then the mean of the inliers' translations (:579-594) */
+#define DPGO_AVERAGE_POSE 1      /* GNC on rotation and translation together (robustSinglePoseAveraging) */
+#define DPGO_AVERAGE_OK 0
+#define DPGO_AVERAGE_EMPTY 1       /* the group has no candidate (the reference: CHECK(n > 0)) */
+#define DPGO_AVERAGE_INVALID 2     /* a candidate entry or precision is not finite (the reference: checkRotationMatrix aborts) */
+#define DPGO_AVERAGE_FEW_INLIERS 3 /* fewer inliers than min_inliers (src/PGOAgent.cpp:587), or none in two-stage mode */
+typedef struct dpgo_average_params {
+  int mode;           /* DPGO_AVERAGE_* */
+  double barc;        /* GNC threshold: angular2ChordalSO3(0.5) (src/PGOAgent.cpp:580) / sqrt(chi2inv(0.9, 3)) (:630) */
+  double mu_step;     /* 1.4 (RobustCostParameters::GNCMuStep) */
+  double mu_cap;      /* 1e-5: muInit = min(barc^2 / (2 max rSq - barc^2), mu_cap) (src/DPGO_solver.cpp:97-98) */
+  double w_tol;       /* 1e-8 (src/DPGO_solver.cpp:77) */
+  int max_iterations; /* 0: the mode's default, 1000 (src/DPGO_solver.cpp:104) / 10000 (:181) */
+  int min_inliers;    /* 2: robustInitMinInliers (include/DPGO/PGOAgent.h:124,143) */
+} dpgo_average_params;
+void dpgo_average_params_default(int mode, dpgo_average_params* params);
+typedef struct dpgo_average_result {
+  int status;     /* DPGO_AVERAGE_OK ... */
+  int inliers;    /* candidates with weight > 1 - w_tol */
+  int candidates; /* size of the group */
+  int iterations; /* GNC iterations run: 0 when muInit <= 0 (small residuals: GNC is skipped, all weights stay 1) */
+  double mu;      /* GNC's mu when the loop ended (muInit when it was skipped) */
+  double T[12];   /* the estimate of the LAST solve, tile [d+1][d] (d = 2: the first 6 entries); zeros unless OK / FEW_INLIERS */
+} dpgo_average_result;
+/* computeNeighborTransform for m shared loop closures at once: cand[e] = (YLift^T X_nbr) inv(T_frame1_frame2)
+ * inv(T_world1_frame1) with X_nbr = nbr_tiles_dev[slot_dev[e]] (pose-tile layout above), T_world1_frame1 =
+ * T_local_dev[my_pose_dev[e]], T_frame1_frame2 = (R_dev[e] row-major, t_dev[e]) for an outgoing edge (incoming_dev[e] == 0:
+ * my pose is p1) and its inverse for an incoming one (src/PGOAgent.cpp:529-545); no projection, no check.  YLift_host: r x d
+ * column-major, host memory.  The indices are trusted. */
+int dpgo_neighbor_candidates_device(int r, int d, int m, const double* YLift_host, const double* T_local_dev,
+                                    const double* nbr_tiles_dev, const int32_t* my_pose_dev, const int32_t* slot_dev,
+                                    const uint8_t* incoming_dev, const double* R_dev, const double* t_dev,
+                                    double* cand_dev, void* stream);
+/* robustSingleRotationAveraging / robustSinglePoseAveraging (src/DPGO_solver.cpp:72-135, 137-218) for ngroups groups of
+ * candidates in one launch, one workgroup and one record per group: group g = candidates group_ptr[g] .. group_ptr[g+1] of
+ * cand_dev (tiles [d+1][d]).  kappa_dev / tau_dev: per-candidate precisions, NULL: the mode's (1 and 1 in two-stage mode,
+ * src/PGOAgent.cpp:573-574; 1.82 and 0.01 in pose mode, :628-629).  weights_dev gets every candidate's final GNC weight
+ * (0 for an INVALID group).  Same input, same bits. */
+int dpgo_robust_average_device(int d, int ngroups, const int32_t* group_ptr_dev, const double* cand_dev,
+                               const double* kappa_dev, const double* tau_dev, const dpgo_average_params* params,
+                               double* weights_dev, dpgo_average_result* results_dev, void* stream);
+/* The same with host arrays, synchronous (the C counterpart of the two reference functions); group_ptr must not decrease. */
+int dpgo_robust_average(int d, int ngroups, const int32_t* group_ptr, const double* cand, const double* kappa,
+                        const double* tau, const dpgo_average_params* params, double* weights,
+                        dpgo_average_result* results, int device);
+/* initializeInGlobalFrame (src/PGOAgent.cpp:329-337): X_i = YLift (T_world_robot T_local_i) for the n local poses.  Exactly
+ * one source of T_world_robot is non-NULL: result_dev, a record in device memory -- unless its status is DPGO_AVERAGE_OK the
+ * launch leaves X untouched --, or T_world_robot_host, a tile [d+1][d] in host memory (robot 0: the identity,
+ * src/PGOAgent.cpp:299-301). */
+int dpgo_lift_in_frame_device(int r, int d, int n, const double* YLift_host, const double* T_local_dev,
+                              const dpgo_average_result* result_dev, const double* T_world_robot_host, double* X_dev,
+                              void* stream);
+
 /* ---- host-side data-matrix construction (no GPU needed) ----
  * PoseGraph::constructQ (src/PoseGraph.cpp:381-491) with constructConnectionLaplacianSE
  * (src/DPGO_utils.cpp:272-344).  Measurements in SoA form (RelativeSEMeasurement.h:21-50):
