@@ -10,7 +10,7 @@ from . import lib as _lib
 _lib.load()  # ImportError if libdpgo_hip.so is missing
 
 from .lib import DpgoError, device_count  # noqa: E402
-from .measurements import RelativeSEMeasurements, partition_contiguous, read_g2o_file  # noqa: E402
+from .measurements import RelativeSEMeasurements, partition_by_ranges, partition_contiguous, read_g2o_file  # noqa: E402
 from .solver import (LiftedSEManifold, PoseGraph, QuadraticOptimizer, QuadraticProblem,  # noqa: E402
                      ROptParameters, ROPTResult)
 
@@ -19,6 +19,6 @@ from .trajectory import (load_trajectory, log_measurements, log_trajectory, roun
                          round_trajectory_device)
 
 __all__ = ["load_trajectory", "log_measurements", "log_trajectory", "round_trajectory", "round_trajectory_device",
-           "DpgoError", "device_count", "RelativeSEMeasurements", "partition_contiguous", "read_g2o_file",
+           "DpgoError", "device_count", "RelativeSEMeasurements", "partition_contiguous", "partition_by_ranges", "read_g2o_file",
            "LiftedSEManifold", "PoseGraph", "QuadraticOptimizer", "QuadraticProblem", "ROptParameters",
            "ROPTResult", "CertificateResult", "CertifiedPGOResult", "solveCertifiedPGO"]

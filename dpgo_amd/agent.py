@@ -25,7 +25,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import lib as L
-from .measurements import RelativeSEMeasurements, partition_contiguous
+from .measurements import RelativeSEMeasurements, partition_by_ranges, partition_contiguous
 from .solver import (PoseGraph, QuadraticOptimizer, QuadraticProblem, ROptParameters, ROPTResult,
                      eval_terms_device_many, optimize_device_many)
 
@@ -108,7 +108,8 @@ def should_update_measurement_weights(prm: PGOAgentParameters, weight_update_cou
     return True
 
 
-def build_pose_graphs(dataset: RelativeSEMeasurements, num_poses: int, num_robots: int, r: int, reorder=False):
+def build_pose_graphs(dataset: RelativeSEMeasurements, num_poses: int, num_robots: int, r: int, reorder=False,
+                      ranges=None):
     """Partition like examples/MultiRobotExample.cpp:71-146 and build one PoseGraph per robot.
 
     reorder (False; True, or the environment's DPGO_REORDER=1 with the default): the agent layer renumbers the poses
@@ -119,7 +120,10 @@ def build_pose_graphs(dataset: RelativeSEMeasurements, num_poses: int, num_robot
     OFF by default: measured on the 100k-pose lattice (round 4, tools/reorder_ab.sh, rotating operands) the odometry
     ("snake") order is already the best of those tried -- k_tcg_hess_sym 41.9 us as given, 45.8 / 44.7 / 42.8 us with
     reverse Cuthill-McKee over runs of 16 / 64 / 250 consecutive poses inside each XCD's eighth, 45.2 us pose by pose
-    (DESIGN.md section 3)."""
+    (DESIGN.md section 3).
+
+    ranges: the robots' global pose ranges [(start, end)] when the blocks are not the demo's even ones
+    (measurements.partition_by_ranges; not together with reorder)."""
     order = None
     import os
     if reorder is False and os.environ.get("DPGO_REORDER") == "1":  # A/B switch for the benchmarks
@@ -128,7 +132,12 @@ def build_pose_graphs(dataset: RelativeSEMeasurements, num_poses: int, num_robot
         from .measurements import locality_order, relabel
         order = locality_order(dataset, num_poses, num_robots)
         dataset = relabel(dataset, order)
-    ranges, per_robot = partition_contiguous(dataset, num_poses, num_robots)
+    if ranges is not None:
+        if reorder is True or len(ranges) != num_robots or ranges[-1][1] != num_poses:
+            raise ValueError("ranges: one block per robot that tile [0, num_poses), without reorder")
+        ranges, per_robot = partition_by_ranges(dataset, ranges)
+    else:
+        ranges, per_robot = partition_contiguous(dataset, num_poses, num_robots)
     graphs = []
     for a in range(num_robots):
         pg = PoseGraph(a, r, dataset.d)
@@ -978,6 +987,17 @@ class RBCDCluster:
         ok = ok and all(getattr(ag, "stream_id", None) == cur for ag in self.agents.values())
         self._so_sweep, self._so_sig = bool(ok), sig
         return self._so_sweep
+
+    def certify(self, **params):
+        """Certificate of global optimality of the team's current iterate from the agents' own blocks
+        (dpgo_amd.certificate.certify_team): one process, one device.  Several ranks are out of scope."""
+        if self.world > 1:
+            raise NotImplementedError("RBCDCluster.certify: a team spread over %d ranks is out of scope (one process, "
+                                      "one device)" % self.world)
+        if self.waiting_agents():
+            raise NotImplementedError("RBCDCluster.certify: agents %s are not in the global frame yet" % self.waiting_agents())
+        from .certificate import certify_team
+        return certify_team(self.agents, **params)
 
     def block_terms(self) -> np.ndarray:
         """[num_agents, 2] array of (0.5 (xqx + xg), |rgrad_a|^2) per agent, identical on every rank."""

@@ -3,6 +3,8 @@
   QuadraticProblem.certify(X)            lambda_min of C(X) = Q - Lambda(X) on the complement of the known null space, by a
                                          preconditioned block LOBPCG on the device -> CertificateResult (+ witness)
   QuadraticProblem.certificateApply(X, V)  V C(X) (tests)
+  certify_team(agents)                   the same for the iterate of a TEAM of DeviceAgents on one device, from the agents'
+                                         own blocks (Q_aa, the G coupling): no central copy of the problem is built
   solveCertifiedPGO(measurements)        SE-Sync's staircase on one handle per rank: solve, certify, escape to rank r + 1
                                          along the witness while the iterate is a saddle; rounds the certified iterate
 
@@ -39,6 +41,7 @@ class CertificateResult:
     deflation_residual: float
     elapsedMs: float
     witness: Optional[np.ndarray] = None
+    symmetry_defect: Optional[float] = None  # certify_team: the probe of the agents' pieces (None for one handle)
 
     @staticmethod
     def from_c(c: L.CertifyResultC, witness=None) -> "CertificateResult":
@@ -108,6 +111,89 @@ def certificate_apply(problem, X, V) -> np.ndarray:
     Xc, Vc, o = problem._in(X, "X"), problem._in(V, "V"), problem._out()
     L.check(problem._lib.dpgo_problem_certificate_apply(problem._h, L.ptr(Xc), L.ptr(Vc), L.ptr(o)))
     return o
+
+
+# ---------------------------------------------------------------- a team of agents on one device
+def team_layout(agents):
+    """(firsts, N, nbr_pose) of a team (C ABI dpgo_team_member): agent a owns tiles [firsts[a], firsts[a] + n_a) of the
+    team vector in its internal pose order; nbr_pose[a][k] = team tile of column slot k of its G coupling
+    (ExchangePlan.slots[a][k] = (robot, frame), frames in the robots' internal numbering)."""
+    ids = [int(ag.id) for ag in agents]
+    if ids != list(range(len(agents))) or len(agents) != agents[0].plan.num_agents:
+        raise ValueError("a team is every agent of the plan, in id order (got ids %s)" % ids)
+    return team_nbr_pose(agents[0].plan, [int(ag.n) for ag in agents])
+
+
+def team_nbr_pose(plan, ns):
+    """team_layout from an ExchangePlan and the agents' pose counts (host only)."""
+    firsts = [int(v) for v in np.concatenate([[0], np.cumsum(ns)[:-1]])]
+    nbr = [np.array([firsts[rob] + fr for rob, fr in plan.slots[a]], dtype=np.int32) for a in range(len(ns))]
+    return firsts, int(sum(ns)), nbr
+
+
+def _team_members(agents, firsts, nbr):
+    arr = (L.TeamMemberC * len(agents))()
+    for a, ag in enumerate(agents):
+        ag.problem.refresh()
+        arr[a].h, arr[a].first = ag.problem._h, firsts[a]
+        arr[a].nbr_pose = nbr[a].ctypes.data if len(nbr[a]) else None
+    return arr
+
+
+def _team_list(agents):
+    agents = [agents[k] for k in sorted(agents)] if isinstance(agents, dict) else list(agents)
+    if not agents:
+        raise ValueError("an empty team")
+    for ag in agents:
+        if len(ag.pg.priors_) > 0:
+            raise ValueError("certify_team: agent %d has priors (a constant term in G): out of scope" % ag.id)
+    return agents
+
+
+def certify_team(agents, witness: bool = True, **params) -> CertificateResult:
+    """Certificate of the team's current iterate (the agents' X, concatenated device to device) from the agents' own
+    handles: dpgo_team_certify_device.  agents: every DeviceAgent of one ExchangePlan, on one device (a list in id order
+    or {id: agent}).  The witness comes back in the caller's global pose order, (N, d+1).  The call refreshes every
+    agent's linear term G from the team's X, as an exchange of the certified iterate would.  Raises DpgoError (ERR_STATE)
+    when the agents hold different weights or activity for a shared edge (symmetry_defect, include/dpgo_hip.h)."""
+    agents = _team_list(agents)
+    torch = agents[0].torch
+    cp = certify_params(**params)
+    firsts, N, nbr = team_layout(agents)
+    d = agents[0].d
+    X = torch.cat([ag.X for ag in agents]).contiguous()
+    w = torch.empty(N * (d + 1), dtype=torch.float64, device=X.device) if witness else None
+    torch.cuda.synchronize(X.device)
+    cr = L.TeamCertifyResultC()
+    L.check(L.load().dpgo_team_certify_device(_team_members(agents, firsts, nbr), len(agents), L.ptr(X), C.byref(cp),
+                                              C.byref(cr), L.ptr(w) if w is not None else None))
+    wh = None
+    if w is not None:
+        wt = w.cpu().numpy().reshape(N, d + 1)
+        wh = np.concatenate([ag.in_caller_order(wt[f:f + ag.n]) for ag, f in zip(agents, firsts)])
+    res = CertificateResult.from_c(cr.cert, wh)
+    res.symmetry_defect = cr.symmetry_defect
+    return res
+
+
+def team_certificate_apply(agents, V_tiles, gram: bool = False):
+    """V C(X) at the team's current iterate for team tiles V [N, d+1, r] in team order (host array; tests):
+    dpgo_team_certificate_apply_device.  gram: also the r x r block V (CV)^T the kernel sums on the way."""
+    agents = _team_list(agents)
+    torch = agents[0].torch
+    firsts, N, nbr = team_layout(agents)
+    X = torch.cat([ag.X for ag in agents]).contiguous()
+    V = torch.as_tensor(np.ascontiguousarray(V_tiles), dtype=torch.float64, device=X.device)
+    if tuple(V.shape) != tuple(X.shape):
+        raise ValueError("V has shape %s, expected %s" % (tuple(V.shape), tuple(X.shape)))
+    CV = torch.empty_like(V)
+    torch.cuda.synchronize(X.device)
+    r = agents[0].r
+    vcv = np.empty((r, r)) if gram else None
+    L.check(L.load().dpgo_team_certificate_apply_gram_device(_team_members(agents, firsts, nbr), len(agents), L.ptr(X),
+                                                             L.ptr(V), L.ptr(CV), L.ptr(vcv)))
+    out = CV.cpu().numpy()
+    return (out, vcv) if gram else out
 
 
 @dataclass

@@ -97,8 +97,24 @@ int launch_cert_apply(dpgo_problem_s* p, int d, int r, bool sym, int g, const do
   return DPGO_OK;
 }
 
+// A team of agents side by side on one device and stream (include/dpgo_hip.h, dpgo_team_certify_device): the handles, the
+// slice of the team vector each owns, the device tables of k_cert_apply_team.  With a team, Cert's pose vectors hold
+// N = sum n_a tiles, `apply` is one launch over the tile table and `precondition` goes member by member on its slice;
+// Gram blocks, combinations and the Rayleigh-Ritz code never know.
+struct Team {
+  std::vector<dpgo_problem_s*> h;
+  std::vector<int> first, precond;
+  int N = 0, ntiles = 0;
+  std::vector<DevBuf<int32_t>> nbr;  // nbr_pose of every member (device)
+  DevBuf<int32_t> no_rows;           // an all-zero rowptr: the coupling of a member without neighbours
+  DevBuf<CertMember> members;
+  DevBuf<CertTile> tiles;
+  DevBuf<double> tin, tout;          // 16-byte-aligned staging of a slice the multilevel cycle cannot take in place
+};
+
 struct Cert {
-  dpgo_problem_s* p;
+  dpgo_problem_s* p;  // (a team: its first member -- the stream, the device, the launch cap)
+  Team* team = nullptr;
   int d, r, n;
   bool sym = false;     // products read the symmetric copy of Q
   DevBuf<double> S;     // Lambda blocks at X (k_grad)
@@ -141,8 +157,16 @@ struct Cert {
 
   // CW = W C(X); with wcw != null also W CW^T (r x r, row-major) on the host
   int apply(const double* W, double* CW, std::vector<double>* wcw = nullptr) {
-    const int g = sym ? p->grid_outer_sym() : p->grid_s();
-    CHK(launch_cert_apply(p, d, r, sym, g, S, W, CW, part, n));
+    // a team: one launch, at most the first member's DPGO_GRID_HESS cap (second trips can be forced as for k_cert_apply)
+    const int g = team ? std::max(1, std::min(team->ntiles, p->cap_h)) : sym ? p->grid_outer_sym() : p->grid_s();
+    if (team) {
+      CHK(dispatch_dr(d, r, [&](auto D, auto R) {
+        return launch(k_cert_apply_team<D, R>, g, 0, p->stream, team->members, team->tiles, team->ntiles, W, CW, part);
+      }));
+      HIPC(hipGetLastError());
+    } else {
+      CHK(launch_cert_apply(p, d, r, sym, g, S, W, CW, part, n));
+    }
     ++products;
     if (wcw) CHK(reduce(g, r * r, *wcw));
     return DPGO_OK;
@@ -198,6 +222,31 @@ struct Cert {
   }
   // Z = M^-1 V without tangent projection
   int precondition(const double* V, double* Z) {
+    if (team) {  // block diagonal over the members: each one's factors or cycle on its own slice
+      for (size_t a = 0; a < team->h.size(); ++a) {
+        dpgo_problem_s* q = team->h[a];
+        const size_t o = (size_t)team->first[a] * q->T;
+        const double* Vs = V + o;
+        double* Zs = Z + o;
+        if (team->precond[a] == DPGO_PRECOND_BLOCK_JACOBI) {
+          CHK(dispatch_dr(d, r, [&](auto D, auto R) {
+            return launch(k_cert_jacobi<D, R>, q->grid(), 0, q->stream, Vs, q->dinv, Zs, q->n);
+          }));
+          HIPC(hipGetLastError());
+        } else if (team->precond[a] == DPGO_PRECOND_MULTILEVEL) {
+          if (aligned16(Vs) && aligned16(Zs)) {
+            CHK(launch_ml_apply(q, zero, Vs, Zs));
+          } else {  // (odd tile sizes: a slice starts on an 8-byte boundary, the cycle moves 16-byte pieces)
+            HIPC(hipMemcpyAsync(team->tin, Vs, q->vec_bytes(), hipMemcpyDeviceToDevice, q->stream));
+            CHK(launch_ml_apply(q, zero, team->tin, team->tout));
+            HIPC(hipMemcpyAsync(Zs, team->tout, q->vec_bytes(), hipMemcpyDeviceToDevice, q->stream));
+          }
+        } else {
+          HIPC(hipMemcpyAsync(Zs, Vs, q->vec_bytes(), hipMemcpyDeviceToDevice, q->stream));
+        }
+      }
+      return DPGO_OK;
+    }
     if (precond == DPGO_PRECOND_BLOCK_JACOBI) {
       CHK(dispatch_dr(d, r, [&](auto D, auto R) {
         return launch(k_cert_jacobi<D, R>, p->grid(), 0, p->stream, V, p->dinv, Z, n);
@@ -240,6 +289,30 @@ int q_scale(dpgo_problem_s* p, DevBuf<double>& dv, double* out) {
   return DPGO_OK;
 }
 
+int resolve_params(const dpgo_certify_params* prm_in, dpgo_certify_params& prm) {
+  if (prm_in)
+    prm = *prm_in;
+  else
+    dpgo_certify_params_default(&prm);
+  if (!(prm.eta >= 0.0) || !(prm.tol_rel > 0.0) || prm.max_iterations < 1 || !(prm.precond_shift >= 0.0))
+    return fail(DPGO_ERR_INVALID, "certify: bad parameters");
+  return DPGO_OK;
+}
+// what the handle's AUTO / ADDITIVE mean for the certificate's preconditioner
+int resolve_precond(dpgo_problem_s* p, int precond, int* out) {
+  if (precond == DPGO_PRECOND_AUTO) {
+    p->auto_decide();
+    precond = p->auto_ml ? DPGO_PRECOND_MULTILEVEL : DPGO_PRECOND_BLOCK_JACOBI;
+  }
+  if (precond == DPGO_PRECOND_ADDITIVE) precond = DPGO_PRECOND_MULTILEVEL;  // (the additive form lives inside the one-launch solve only)
+  if (precond < DPGO_PRECOND_NONE || precond > DPGO_PRECOND_MULTILEVEL) return fail(DPGO_ERR_INVALID, "unknown preconditioner");
+  *out = precond;
+  return DPGO_OK;
+}
+
+int cert_run(Cert& c, const double* X, const dpgo_certify_params& prm, double scale, dpgo_certify_result* res,
+             double* witness, bool witness_on_host, std::chrono::steady_clock::time_point t0, double* symmetry_defect);
+
 int certify_impl(dpgo_problem_s* p, const double* X, const dpgo_certify_params* prm_in, dpgo_certify_result* res,
                  double* witness, bool witness_on_host) {
   const auto t0 = std::chrono::steady_clock::now();
@@ -248,19 +321,9 @@ int certify_impl(dpgo_problem_s* p, const double* X, const dpgo_certify_params* 
   if (p->has_G || p->C.nnzb > 0)
     return fail(DPGO_ERR_INVALID, "certification is defined for a problem without a linear term G (global / central problem)");
   dpgo_certify_params prm;
-  if (prm_in)
-    prm = *prm_in;
-  else
-    dpgo_certify_params_default(&prm);
-  if (!(prm.eta >= 0.0) || !(prm.tol_rel > 0.0) || prm.max_iterations < 1 || !(prm.precond_shift >= 0.0))
-    return fail(DPGO_ERR_INVALID, "certify: bad parameters");
-  int precond = prm.precond;
-  if (precond == DPGO_PRECOND_AUTO) {
-    p->auto_decide();
-    precond = p->auto_ml ? DPGO_PRECOND_MULTILEVEL : DPGO_PRECOND_BLOCK_JACOBI;
-  }
-  if (precond == DPGO_PRECOND_ADDITIVE) precond = DPGO_PRECOND_MULTILEVEL;  // (the additive form lives inside the one-launch solve only)
-  if (precond < DPGO_PRECOND_NONE || precond > DPGO_PRECOND_MULTILEVEL) return fail(DPGO_ERR_INVALID, "unknown preconditioner");
+  CHK(resolve_params(prm_in, prm));
+  int precond = 0;
+  CHK(resolve_precond(p, prm.precond, &precond));
   *res = dpgo_certify_result{};
   res->status = DPGO_CERT_NOT_CONVERGED;
 
@@ -272,7 +335,6 @@ int certify_impl(dpgo_problem_s* p, const double* X, const dpgo_certify_params* 
   c.precond = precond;
   c.shift = prm.precond_shift;
   CHK(c.init());
-  const int r = c.r;
   if (p->sym_wanted() && p->split == 1) {
     bool usable = false;
     CHK(sym_ensure(p, &usable));
@@ -286,9 +348,6 @@ int certify_impl(dpgo_problem_s* p, const double* X, const dpgo_certify_params* 
   double scale = 0.0;
   CHK(q_scale(p, c.qdiag, &scale));
   if (!(scale > 0.0)) return fail(DPGO_ERR_INVALID, "certify: Q has no positive diagonal");
-  res->scale = scale;
-  const double eta = prm.eta * scale, tol = prm.tol_rel * scale;
-  const double null_tol = std::sqrt(prm.tol_rel) * scale;  // a candidate direction z is null when |C z| <= this
   if (precond == DPGO_PRECOND_BLOCK_JACOBI) CHK(build_dinv(p, prm.precond_shift));
   if (precond == DPGO_PRECOND_MULTILEVEL) {
     CHK(ml_ensure(p, prm.precond_shift));
@@ -296,6 +355,18 @@ int certify_impl(dpgo_problem_s* p, const double* X, const dpgo_certify_params* 
     CHK(c.zero.alloc((size_t)c.n * (c.d + 1) * c.r));
     HIPC(hipMemsetAsync(c.zero, 0, c.vec_bytes(), p->stream));
   }
+  return cert_run(c, X, prm, scale, res, witness, witness_on_host, t0, nullptr);
+}
+
+// The eigen-solver on Cert's operator, one handle or a team alike.  symmetry_defect (a team): the probe of the operator's
+// symmetry from the two products the solver makes anyway (below).
+int cert_run(Cert& c, const double* X, const dpgo_certify_params& prm, double scale, dpgo_certify_result* res,
+             double* witness, bool witness_on_host, std::chrono::steady_clock::time_point t0, double* symmetry_defect) {
+  dpgo_problem_s* p = c.p;
+  const int r = c.r;
+  res->scale = scale;
+  const double eta = prm.eta * scale, tol = prm.tol_rel * scale;
+  const double null_tol = std::sqrt(prm.tol_rel) * scale;  // a candidate direction z is null when |C z| <= this
 
   // ---- deflation space: rows of X and the translation indicator, kept where one product confirms them null
   double *K1, *CK0, *CK1, *Z0, *Z1;
@@ -362,9 +433,24 @@ int certify_impl(dpgo_problem_s* p, const double* X, const dpgo_certify_params* 
   res->deflated = mz;
   res->deflation_residual = cz;
   const int nzb = (mz + r - 1) / r;  // Z blocks (rows beyond mz are zero)
+  std::vector<double> M((size_t)2 * 2 * r * r, 0.0);
+  // the reported |C z| (in place on CK0, CK1: a team's symmetry probe reads C X first, so there it runs behind the probe)
+  auto deflation_residual = [&]() -> int {
+    if (nzb == 0) return DPGO_OK;
+    // mu is an eigenvalue of a Gram matrix of squares, so sqrt(mu) carries sqrt(round-off) of the
+    // LARGEST |C k| (1e-8 of it: an exactly null t beside a non-stationary X reads 1e-11 scale).  C Z is the same
+    // combination of C K, and its row norms have no such cancellation.
+    CHK(c.combine({CK0, CK1}, {CK0, CK1}, M));
+    std::vector<double> Gz;
+    CHK(c.gram({CK0, CK1}, {{0, 0}, {1, 1}}, Gz));
+    double v = 0.0;
+    for (int q = 0; q < mz; ++q)
+      v = std::max(v, std::sqrt(std::max(Gz[(size_t)(q / r) * r * r + (q % r) * r + (q % r)], 0.0)));
+    res->deflation_residual = v;
+    return DPGO_OK;
+  };
   if (nzb > 0) {
     // Z rows = (B V_keep)^T K: coefficient of K row a (block j = a / r) for Z row q (block k = q / r)
-    std::vector<double> M((size_t)2 * 2 * r * r, 0.0);
     for (int q = 0; q < mz; ++q)
       for (int a = 0; a < m0; ++a) {
         double s = 0.0;
@@ -373,16 +459,7 @@ int certify_impl(dpgo_problem_s* p, const double* X, const dpgo_certify_params* 
         M[((size_t)k * 2 + jb) * r * r + ar * r + bq] = s;
       }
     CHK(c.combine({X, K1}, {Z0, Z1}, M));
-    // the reported |C z|: mu is an eigenvalue of a Gram matrix of squares, so sqrt(mu) carries sqrt(round-off) of the
-    // LARGEST |C k| (1e-8 of it: an exactly null t beside a non-stationary X reads 1e-11 scale).  C Z is the same
-    // combination of C K, and its row norms have no such cancellation.
-    CHK(c.combine({CK0, CK1}, {CK0, CK1}, M));
-    std::vector<double> Gz;
-    CHK(c.gram({CK0, CK1}, {{0, 0}, {1, 1}}, Gz));
-    cz = 0.0;
-    for (int q = 0; q < mz; ++q)
-      cz = std::max(cz, std::sqrt(std::max(Gz[(size_t)(q / r) * r * r + (q % r) * r + (q % r)], 0.0)));
-    res->deflation_residual = cz;
+    if (!symmetry_defect) CHK(deflation_residual());
   }
   std::vector<const double*> Zb;
   if (nzb >= 1) Zb.push_back(Z0);
@@ -449,6 +526,31 @@ int certify_impl(dpgo_problem_s* p, const double* X, const dpgo_certify_params* 
     std::swap(W, W2);
     std::swap(CW, CW2);
     theta = w;
+  }
+  if (symmetry_defect) {
+    // A team's pieces form a symmetric operator only if both owners of every shared edge hold the same weight and
+    // activity for it.  The start block W and the iterate X have both been multiplied by now (CW above, CK0 = C X of the
+    // deflation step): for a symmetric C the r x r blocks W (C X)^T and (C W) X^T are equal up to rounding.
+    // The bound: each entry is an inner product of length L = (d+1) N; its a-priori worst-case rounding error is
+    // gamma_L |w| |C x| <= L u |W|_F scale' |X|_F with u = 2^-53 and scale' = |C|_2 <= a small multiple of scale (a row of
+    // C holds the pose's own block and its few neighbours'); the rounding inside the two products C X and C W is of
+    // the order (row length) u scale |X|_F |W|_F, far below L u for any team.  Two such entries are subtracted, and a
+    // factor 4 covers scale' / scale: 8 L u, relative to scale |W|_F |X|_F.
+    std::vector<double> G;
+    CHK(c.gram({W, CK0, CW, X}, {{0, 1}, {2, 3}, {0, 0}, {3, 3}}, G));
+    double dmax = 0.0, w2 = 0.0, x2 = 0.0;
+    for (int e = 0; e < r * r; ++e) dmax = std::max(dmax, std::fabs(G[e] - G[(size_t)r * r + e]));
+    for (int a = 0; a < r; ++a) {
+      w2 += G[(size_t)2 * r * r + a * r + a];
+      x2 += G[(size_t)3 * r * r + a * r + a];
+    }
+    const double defect = dmax / (scale * std::sqrt(w2) * std::sqrt(x2));
+    *symmetry_defect = defect;
+    const double bound = 8.0 * (double)(c.d + 1) * (double)c.n * std::ldexp(1.0, -53);
+    if (!(defect <= bound))
+      return fail(DPGO_ERR_STATE, "team certificate: agents hold different weights or activity for a shared edge "
+                                  "(symmetry defect " + std::to_string(defect) + " of scale)");
+    CHK(deflation_residual());
   }
   bool have_p = false, negative = false;
   double resid0 = 0.0;
@@ -605,6 +707,159 @@ int certify_impl(dpgo_problem_s* p, const double* X, const dpgo_certify_params* 
   return DPGO_OK;
 }
 
+// ---------------------------------------------------------------- a team of agents (include/dpgo_hip.h)
+// Checks of the member table that need no device, then the device, then the handles: nothing is dereferenced before it
+// is known to be a handle of this process's device.
+int team_check(const dpgo_team_member* mem, int n_members, Team& t) {
+  if (!mem || n_members < 1) return fail(DPGO_ERR_INVALID, "team: no members");
+  for (int a = 0; a < n_members; ++a) {
+    if (!mem[a].h) return fail(DPGO_ERR_INVALID, "team: null handle");
+    if (mem[a].first < 0 || (a == 0 && mem[a].first != 0) || (a > 0 && mem[a].first <= mem[a - 1].first))
+      return fail(DPGO_ERR_INVALID, "team: the members' slices do not tile [0, N) in member order");
+  }
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) {
+    (void)hipGetLastError();
+    return fail(DPGO_ERR_HIP, "team: no HIP device");
+  }
+  dpgo_problem_s* p0 = mem[0].h;
+  int N = 0;
+  for (int a = 0; a < n_members; ++a) {
+    dpgo_problem_s* q = mem[a].h;
+    if (!q->Q.vals) return fail(DPGO_ERR_STATE, "team: quadratic matrix Q not set");
+    if (q->pending.active) return fail(DPGO_ERR_STATE, "team: a member has a solve in flight");
+    if (q->d != p0->d || q->r != p0->r) return fail(DPGO_ERR_INVALID, "team: members differ in (d, r)");
+    if (q->device != p0->device || q->stream != p0->stream)
+      return fail(DPGO_ERR_INVALID, "team: members on different devices or streams");
+    if (q->g0_nonzero) return fail(DPGO_ERR_INVALID, "team: a member has priors (a constant term in G): out of scope");
+    if (mem[a].first != N) return fail(DPGO_ERR_INVALID, "team: the members' slices do not tile [0, N) in member order");
+    if ((long long)N + q->n > 0x7fffffffLL) return fail(DPGO_ERR_INVALID, "team: too many poses");
+    N += q->n;
+  }
+  for (int a = 0; a < n_members; ++a) {
+    dpgo_problem_s* q = mem[a].h;
+    const int nc = q->C.rowptr ? q->C.ncols : 0;
+    if (nc > 0 && !mem[a].nbr_pose) return fail(DPGO_ERR_INVALID, "team: null nbr_pose");
+    for (int k = 0; k < nc; ++k) {
+      const int j = mem[a].nbr_pose[k];
+      if (j < 0 || j >= N || (j >= mem[a].first && j < mem[a].first + q->n))
+        return fail(DPGO_ERR_INVALID, "team: nbr_pose entry outside [0, N) or inside the member's own slice");
+    }
+    t.h.push_back(q);
+    t.first.push_back(mem[a].first);
+  }
+  t.N = N;
+  return DPGO_OK;
+}
+
+// device tables, every G_a from the team's X (the member's linear term as an exchange of X would leave it), every member's
+// S, f and |rgrad| (S: the team's Lambda blocks, [N, d, d]); gn2 = sum |rgrad_a|^2 in member order
+int team_setup(const dpgo_team_member* mem, Team& t, const double* X, double* S, double* gn2) {
+  dpgo_problem_s* p0 = t.h[0];
+  CHK(set_device(p0));
+  const int d = p0->d, T = p0->T, P = (64 / (d + 1)) * kWaves, na = (int)t.h.size();
+  int nmax = 0, cmax = 0;
+  for (dpgo_problem_s* q : t.h) {
+    nmax = std::max(nmax, q->n);
+    cmax = std::max(cmax, q->C.rowptr ? q->C.ncols : 0);
+  }
+  CHK(t.no_rows.alloc((size_t)nmax + 1));
+  HIPC(hipMemsetAsync(t.no_rows, 0, sizeof(int32_t) * ((size_t)nmax + 1), p0->stream));
+  DevBuf<double> nbuf;  // neighbour tiles of one member at a time
+  CHK(nbuf.alloc((size_t)std::max(cmax, 1) * T));
+  std::vector<CertMember> hm(na);
+  std::vector<CertTile> ht;
+  t.nbr.resize(na);
+  double sum = 0.0;
+  for (int a = 0; a < na; ++a) {
+    dpgo_problem_s* q = t.h[a];
+    const int nc = q->C.rowptr ? q->C.ncols : 0;
+    const double* Xa = X + (size_t)t.first[a] * T;
+    double* Sa = S + (size_t)t.first[a] * d * d;
+    CHK(upload(t.nbr[a], mem[a].nbr_pose, (size_t)nc, q->stream));
+    if (q->C.rowptr) {
+      if (nc > 0) {
+        launch(k_cert_gather_tiles, flat_grid((size_t)nc * T), 0, q->stream, X, t.nbr[a], T, nc, nbuf);
+        HIPC(hipGetLastError());
+      }
+      CHK(launch_spmm(q, q->C, nbuf, q->G0, q->G));
+      q->has_G = true;
+    }
+    CHK(launch_grad(q, Xa, nullptr, Sa, nullptr, nullptr, false));
+    CHK(launch_rtr_begin(q, 0.0, 1.0, 1.0, 0, 0));
+    CHK(poll_state(q));  // (synchronises: nbuf and the host's nbr_pose are free again)
+    sum += q->hstate->ngf * q->hstate->ngf;
+    hm[a].Q = q->Q.dev();
+    hm[a].C = q->C.rowptr ? q->C.dev() : BsrDev{t.no_rows, nullptr, nullptr};
+    hm[a].nbr_pose = t.nbr[a];
+    hm[a].S = Sa;
+    hm[a].first = t.first[a];
+    hm[a].n = q->n;
+    for (int p0_ = 0; p0_ < q->n; p0_ += P) ht.push_back(CertTile{a, p0_});
+  }
+  *gn2 = sum;
+  t.ntiles = (int)ht.size();
+  CHK(upload(t.members, hm.data(), hm.size(), p0->stream));
+  CHK(upload(t.tiles, ht.data(), ht.size(), p0->stream));
+  HIPC(hipStreamSynchronize(p0->stream));  // (the tables are host vectors of this scope)
+  return DPGO_OK;
+}
+
+int team_certify_impl(const dpgo_team_member* mem, int n_members, const double* X, const dpgo_certify_params* prm_in,
+                      dpgo_team_certify_result* out, double* witness) {
+  const auto t0 = std::chrono::steady_clock::now();
+  if (!X || !out) return fail(DPGO_ERR_INVALID, "null pointer");
+  dpgo_certify_params prm;
+  CHK(resolve_params(prm_in, prm));
+  Team t;
+  CHK(team_check(mem, n_members, t));
+  *out = dpgo_team_certify_result{};
+  out->cert.status = DPGO_CERT_NOT_CONVERGED;
+  out->members = n_members;
+  out->poses = t.N;
+  dpgo_problem_s* p0 = t.h[0];
+  Cert c;
+  c.p = p0;
+  c.team = &t;
+  c.d = p0->d;
+  c.r = p0->r;
+  c.n = t.N;
+  c.shift = prm.precond_shift;
+  CHK(set_device(p0));
+  CHK(c.init());
+  double gn2 = 0.0, scale = 0.0;
+  CHK(team_setup(mem, t, X, c.S, &gn2));
+  out->cert.gradnorm = std::sqrt(gn2);
+  int nml = 0;
+  bool staged = false;
+  for (size_t a = 0; a < t.h.size(); ++a) {
+    dpgo_problem_s* q = t.h[a];
+    double sa = 0.0;
+    CHK(q_scale(q, c.qdiag, &sa));
+    scale = std::max(scale, sa);
+    int pc = 0;
+    CHK(resolve_precond(q, prm.precond, &pc));
+    t.precond.push_back(pc);
+    if (pc == DPGO_PRECOND_BLOCK_JACOBI) CHK(build_dinv(q, prm.precond_shift));
+    if (pc == DPGO_PRECOND_MULTILEVEL) {
+      CHK(ml_ensure(q, prm.precond_shift));
+      CHK(ml_ops32_ensure(q));
+      nml = std::max(nml, q->n);
+      staged = staged || (((size_t)t.first[a] * q->T) & 1);
+    }
+  }
+  if (!(scale > 0.0)) return fail(DPGO_ERR_INVALID, "certify: Q has no positive diagonal");
+  if (nml > 0) {
+    CHK(c.zero.alloc((size_t)nml * p0->T));
+    HIPC(hipMemsetAsync(c.zero, 0, sizeof(double) * (size_t)nml * p0->T, p0->stream));
+    if (staged) {
+      CHK(t.tin.alloc((size_t)nml * p0->T));
+      CHK(t.tout.alloc((size_t)nml * p0->T));
+    }
+  }
+  return cert_run(c, X, prm, scale, &out->cert, witness, false, t0, &out->symmetry_defect);
+}
+
 }  // namespace
 }  // namespace dpgo_host
 
@@ -654,6 +909,53 @@ int dpgo_problem_certificate_apply(dpgo_problem_t h, const double* X_host, const
   CHK(launch_grad(h, X, nullptr, S, nullptr, nullptr, sym));
   CHK(launch_cert_apply(h, h->d, h->r, sym, sym ? h->grid_outer_sym() : h->grid_s(), S, V, CV, part, h->n));
   return d2h(h, CV_host, CV);
+}
+
+
+int dpgo_team_certify_device(const dpgo_team_member* members, int n_members, const double* X_team_dev,
+                             const dpgo_certify_params* params, dpgo_team_certify_result* result,
+                             double* witness_team_dev) {
+  if (!aligned8(X_team_dev) || !aligned8(witness_team_dev)) return fail(DPGO_ERR_INVALID, "team: pointer not 8-byte aligned");
+  return team_certify_impl(members, n_members, X_team_dev, params, result, witness_team_dev);
+}
+
+
+int dpgo_team_certificate_apply_gram_device(const dpgo_team_member* members, int n_members, const double* X_team_dev,
+                                            const double* V_team_dev, double* CV_team_dev, double* vcv_host) {
+  if (!X_team_dev || !V_team_dev || !CV_team_dev) return fail(DPGO_ERR_INVALID, "null pointer");
+  if (!aligned8(X_team_dev) || !aligned8(V_team_dev) || !aligned8(CV_team_dev))
+    return fail(DPGO_ERR_INVALID, "team: pointer not 8-byte aligned");
+  Team t;
+  CHK(team_check(members, n_members, t));
+  dpgo_problem_s* p0 = t.h[0];
+  CHK(set_device(p0));
+  Cert c;
+  c.p = p0;
+  c.team = &t;
+  c.d = p0->d;
+  c.r = p0->r;
+  c.n = t.N;
+  CHK(c.S.alloc((size_t)t.N * p0->d * p0->d));
+  CHK(c.part.alloc((size_t)kPartialCap * 36));
+  double gn2 = 0.0;
+  CHK(team_setup(members, t, X_team_dev, c.S, &gn2));
+  if (vcv_host) {
+    CHK(c.red.alloc(36));
+    CHK(c.hbuf.alloc(36));
+    std::vector<double> vcv;
+    CHK(c.apply(V_team_dev, CV_team_dev, &vcv));
+    std::copy(vcv.begin(), vcv.end(), vcv_host);
+  } else {
+    CHK(c.apply(V_team_dev, CV_team_dev));
+  }
+  HIPC(hipStreamSynchronize(p0->stream));
+  return DPGO_OK;
+}
+
+
+int dpgo_team_certificate_apply_device(const dpgo_team_member* members, int n_members, const double* X_team_dev,
+                                       const double* V_team_dev, double* CV_team_dev) {
+  return dpgo_team_certificate_apply_gram_device(members, n_members, X_team_dev, V_team_dev, CV_team_dev, nullptr);
 }
 
 

@@ -309,6 +309,7 @@ struct dpgo_problem_s {
   Bsr C;  // inter-agent coupling (rectangular), for G
   DevBuf<double> G0, G;
   bool has_G = false;
+  bool g0_nonzero = false;  // the constant term G0 of the coupling holds a non-zero entry (priors)
   DevBuf<double> dinv;
   double dinv_shift = -1.0;
   // work vectors

@@ -79,6 +79,106 @@ __global__ __launch_bounds__(kBlock) void k_cert_apply(MAT Q, const double* __re
   }
 }
 
+// ================================================================ the same product for a TEAM of agents, one launch
+// The team's pose vectors are one allocation of N = sum n_a tiles; member a owns the slice [first, first + n) in its own
+// internal pose order.  Rows of member a of W C(X):  W_a Q_aa + sum_b W_b Q_ba - W_a,rot Lambda_a, with Q_aa the member's
+// own Q (it already carries the diagonal terms of the shared edges), Q_ba its coupling matrix C -- column slot k of C is
+// team tile nbr_pose[k], read straight from W: no neighbour buffer, no pack, no exchange -- and Lambda_a the S that k_grad
+// cached with the member's G current.  The host's tile table maps every workgroup tile to (member, first local pose): a
+// tile lies inside ONE member (a member's last tile is ragged), so everything that selects a matrix is uniform per
+// workgroup.  One pose per D+1 lanes; the own-row gather, the coupling blocks in slot order, the S correction: a fixed
+// summation order, bitwise reproducible for any grid.  partials as k_cert_apply.
+struct CertMember {
+  BsrDev Q;                 // n x n block rows of the member
+  BsrDev C;                 // n block rows, column slots into nbr_pose
+  const int32_t* nbr_pose;  // team tile of every column slot of C
+  const double* S;          // the member's Lambda blocks [n, D, D]
+  int first, n;
+};
+struct CertTile {
+  int member, p0;  // first local pose of the tile
+};
+template <int D, int R>
+__global__ __launch_bounds__(kBlock) void k_cert_apply_team(const CertMember* __restrict__ members,
+                                                            const CertTile* __restrict__ tiles, int ntiles,
+                                                            const double* __restrict__ W, double* __restrict__ CW,
+                                                            double* __restrict__ partials) {
+  using GEO = Geo<D, R, 1>;
+  constexpr int B = GEO::B, T = GEO::T, BB = GEO::BB;
+  __shared__ double sm[kWaves][GEO::G][GEO::T];
+  __shared__ double red[kWaves * R * R];
+  const LaneId L = lane_id<D, 1>();
+  double part[R * R];
+#pragma unroll
+  for (int k = 0; k < R * R; ++k) part[k] = 0.0;
+  const TileIter ti_ = tile_iter(ntiles);
+  for (int tk = ti_.first; tk < ti_.last; tk += ti_.step) {
+    const int mi = tiles[tk].member, p0 = tiles[tk].p0;
+    const BsrDev Q = members[mi].Q, Cm = members[mi].C;
+    const int32_t* __restrict__ nbr = members[mi].nbr_pose;
+    const double* __restrict__ S = members[mi].S;
+    const int first = members[mi].first, n = members[mi].n;
+    const int il = p0 + L.wave * GEO::G + L.g;  // the member's pose
+    const bool ok = (L.g < GEO::G) && (il < n);
+    const int i = first + il;                   // the team's tile
+    double h[R], w[R];
+    const size_t off = (size_t)i * T + L.c * R;
+    double* ws = ok ? &sm[L.wave][L.g][0] : nullptr;
+    q_gather<D, R, 1>(Q, W + (size_t)first * T, il, 0, L.c, ok, h);
+    if (ok) {
+      // coupling blocks of the row: the other members' tiles, through nbr_pose (spmm_col's arithmetic)
+      const int t1 = Cm.rowptr[il + 1];
+      for (int t = Cm.rowptr[il]; t < t1; ++t) {
+        const double* __restrict__ q = Cm.vals + (size_t)t * BB + L.c * B;
+        const double* __restrict__ x = W + (size_t)nbr[Cm.colidx[t]] * T;
+        double qk[B];
+#pragma unroll
+        for (int kk = 0; kk < B; ++kk) qk[kk] = q[kk];
+#pragma unroll
+        for (int kk = 0; kk < B; ++kk) {
+#pragma unroll
+          for (int a = 0; a < R; ++a) h[a] = fma(x[kk * R + a], qk[kk], h[a]);
+        }
+      }
+      load_col<R>(W + off, w);
+      store_col<R>(ws + L.c * R, w);
+    }
+    wave_sync();
+    if (ok) {
+      if (L.c < D) {
+#pragma unroll
+        for (int a = 0; a < D; ++a) {
+          const double sac = S[(size_t)il * D * D + L.c * D + a];
+#pragma unroll
+          for (int k = 0; k < R; ++k) h[k] = fma(-ws[a * R + k], sac, h[k]);
+        }
+      }
+#pragma unroll
+      for (int a = 0; a < R; ++a)
+#pragma unroll
+        for (int b = 0; b < R; ++b) part[a * R + b] = fma(w[a], h[b], part[a * R + b]);
+      store_col<R>(CW + off, h);
+    }
+    wave_sync();
+  }
+  block_allreduce<R * R>(part, red);
+  if (threadIdx.x == 0) {
+#pragma unroll
+    for (int k = 0; k < R * R; ++k) partials[(size_t)blockIdx.x * R * R + k] = part[k];
+  }
+}
+
+// out[k] = X[idx[k]] for pose tiles of T doubles: the neighbour tiles of a member, taken from the team's iterate
+static __global__ __launch_bounds__(kBlock) void k_cert_gather_tiles(const double* __restrict__ X,
+                                                                     const int32_t* __restrict__ idx, int T, int count,
+                                                                     double* __restrict__ out) {
+  const size_t total = (size_t)count * T;
+  for (size_t e = (size_t)blockIdx.x * kBlock + threadIdx.x; e < total; e += (size_t)gridDim.x * kBlock) {
+    const size_t k = e / T;
+    out[e] = X[(size_t)idx[k] * T + (e - k * T)];
+  }
+}
+
 // ================================================================ Gram blocks  G_p = B_x(p) B_y(p)^T  (R x R each)
 // One streaming pass over up to NB blocks: chunks of kCertCols columns of every block are staged in LDS (each chunk of a
 // block is one contiguous span of kCertCols * R doubles), then every thread owns whole entries (pair, a, b) of the

@@ -678,8 +678,11 @@ int dpgo_problem_set_G_coupling(dpgo_problem_t p, int ncols, int nnzb, const int
   // shared re-weightable edges index into the old coupling pattern: drop them (the caller re-registers)
   if (p->gnc.n_shared_edges > 0) p->gnc = dpgo_problem_s::GncEdges();
   CHK(upload_bsr(p->C, p->n, ncols, nnzb, p->b, rowptr, colidx, vals, p->stream));
+  p->g0_nonzero = false;
   if (G0_host) {
     CHK(h2d(p, p->G0, G0_host));
+    const size_t cnt = (size_t)p->n * p->T;
+    p->g0_nonzero = std::any_of(G0_host, G0_host + cnt, [](double v) { return v != 0.0; });
   } else {
     HIPC(hipMemsetAsync(p->G0, 0, p->vec_bytes(), p->stream));
   }

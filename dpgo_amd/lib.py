@@ -57,6 +57,14 @@ class CertifyResultC(C.Structure):
                 ("deflation_residual", C.c_double), ("elapsedMs", C.c_double)]
 
 
+class TeamMemberC(C.Structure):
+    _fields_ = [("h", C.c_void_p), ("first", C.c_int), ("nbr_pose", C.c_void_p)]
+
+
+class TeamCertifyResultC(C.Structure):
+    _fields_ = [("cert", CertifyResultC), ("symmetry_defect", C.c_double), ("members", C.c_int), ("poses", C.c_int)]
+
+
 COST_L2, COST_L1, COST_TLS, COST_HUBER, COST_GM, COST_GNC_TLS = range(6)  # DPGO_COST_*
 COST_TYPES = {"L2": COST_L2, "L1": COST_L1, "TLS": COST_TLS, "Huber": COST_HUBER, "GM": COST_GM, "GNC_TLS": COST_GNC_TLS}
 
@@ -219,6 +227,10 @@ SIGNATURES = {
     "dpgo_problem_certify_device": ([_P, _P, C.POINTER(CertifyParamsC), C.POINTER(CertifyResultC), _P], _I),
     "dpgo_problem_certificate_apply": ([_P, _P, _P, _P], _I),
     "dpgo_certify_escape_device": ([_P, _I, _P, _P, _D, _P, C.POINTER(_D)], _I),
+    "dpgo_team_certify_device": ([C.POINTER(TeamMemberC), _I, _P, C.POINTER(CertifyParamsC),
+                                  C.POINTER(TeamCertifyResultC), _P], _I),
+    "dpgo_team_certificate_apply_device": ([C.POINTER(TeamMemberC), _I, _P, _P, _P], _I),
+    "dpgo_team_certificate_apply_gram_device": ([C.POINTER(TeamMemberC), _I, _P, _P, _P, _P], _I),
 }
 
 _lib: Optional[C.CDLL] = None

@@ -146,6 +146,26 @@ def partition_contiguous(dataset: RelativeSEMeasurements, num_poses: int, num_ro
     return [(int(s), int(e)) for s, e in zip(starts, ends)], per_robot
 
 
+def partition_by_ranges(dataset: RelativeSEMeasurements, ranges):
+    """partition_contiguous for blocks of any sizes: robot a owns the global pose range ranges[a] = (start, end); the
+    ranges tile [0, num_poses) in order, none empty.  Returns (ranges, [measurements of robot a])."""
+    ranges = [(int(s), int(e)) for s, e in ranges]
+    if not ranges or ranges[0][0] != 0 or any(e <= s for s, e in ranges) or \
+            any(ranges[a][1] != ranges[a + 1][0] for a in range(len(ranges) - 1)):
+        raise ValueError("ranges must tile [0, num_poses) in order with non-empty blocks")
+    num_poses = ranges[-1][1]
+    if len(dataset) and int(max(np.max(dataset.p1), np.max(dataset.p2))) >= num_poses:
+        raise ValueError("a measurement refers to a pose outside the ranges")
+    starts = np.array([s for s, _ in ranges])
+    robot_of = np.searchsorted(starts, np.arange(num_poses), side="right") - 1
+    local = np.arange(num_poses) - starts[robot_of]
+    g = RelativeSEMeasurements(dataset.d, robot_of[dataset.p1], local[dataset.p1], robot_of[dataset.p2],
+                               local[dataset.p2], dataset.R, dataset.t, dataset.kappa, dataset.tau,
+                               dataset.weight.copy(), dataset.fixedWeight.copy())
+    per_robot = [g.select((g.r1 == a) | (g.r2 == a)) for a in range(len(ranges))]
+    return ranges, per_robot
+
+
 def relabel(dataset: RelativeSEMeasurements, new_index: np.ndarray) -> RelativeSEMeasurements:
     """The same measurements with pose i of a SINGLE index space (r1 = r2 = 0: a data set before partitioning) renamed
     new_index[i].  Weights and the fixedWeight flags (odometry edges, never re-weighted) travel with their edges."""

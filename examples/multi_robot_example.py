@@ -58,6 +58,8 @@ def main():
     ap.add_argument("--out-dir", default=None)
     ap.add_argument("--certify", action="store_true",
                     help="certify the assembled global iterate on one central handle (QuadraticProblem.certify)")
+    ap.add_argument("--certify-team", action="store_true",
+                    help="certify the team's iterate from the agents' own blocks on the device (RBCDCluster.certify)")
     ap.add_argument("--robust-cost", choices=["L1", "Huber", "TLS", "GM", "GNC_TLS"], default=None,
                     help="robust agent protocol with this cost: weights re-computed on the device between blocks of iterations")
     ap.add_argument("--weight-updates", type=int, default=10, help="robustOptNumWeightUpdates")
@@ -122,6 +124,10 @@ def main():
         c = central.certify(np.ascontiguousarray(X).reshape(-1, r).T)
         print("Certificate of the global iterate: %s | lambda_min = %.6g | |rgrad| = %.3g | %d LOBPCG iterations" % (
             c.status, c.lambda_min, c.gradnorm, c.iterations))
+    if args.certify_team:
+        c = cluster.certify()
+        print("Certificate of the team's iterate: %s | lambda_min = %.6g | |rgrad| = %.3g | %d LOBPCG iterations | "
+              "symmetry defect = %.2g" % (c.status, c.lambda_min, c.gradnorm, c.iterations, c.symmetry_defect))
     if args.out_dir:
         os.makedirs(args.out_dir, exist_ok=True)
         for a, T in cluster.trajectories_in_global_frame().items():

@@ -836,6 +836,44 @@ int dpgo_problem_certificate_apply(dpgo_problem_t h, const double* X_host, const
 int dpgo_certify_escape_device(dpgo_problem_t h_next, int r, const double* X_dev, const double* witness_dev,
                                double grad_tol, double* X_next_dev, double* alpha);
 
+/* ---- certificate of a TEAM's iterate from the agents' own blocks (one process, one device) ----
+ * The agents of a team hold the global problem in pieces: agent a its block row Q_aa (shared edges' diagonal terms included,
+ * src/PGOAgent.cpp:97-166) and the coupling matrix Q_ba that builds its linear term G_a (src/PoseGraph.cpp:493-580).  The
+ * rows of agent a of W C(X) are W_a Q_aa + sum_b W_b Q_ba - W_a,rot Lambda_a with Lambda_a the S of its own gradient
+ * at a current G_a, so the certificate above is computed without assembling, uploading or factoring a central copy.
+ * All pose vectors are ONE device allocation of N = sum n_a tiles; member a owns [first, first + n_a), in the agent's
+ * internal pose order, and the members tile [0, N) exactly in table order.  nbr_pose (HOST, one entry per column slot of
+ * the member's G coupling): the team tile of that slot -- inside [0, N), outside the member's own slice.
+ * The call recomputes every G_a from X_team (it leaves G as an exchange of the certified iterate would) and evaluates
+ * every member's gradient; gradnorm = sqrt(sum |rgrad_a|^2), scale = max_a scale_a.  The preconditioner is block
+ * diagonal over the members (AUTO resolves per member).  symmetry_defect = max |W (C X)^T - (C W) X^T| /
+ * (scale |W|_F |X|_F) for the start block W: the agents' pieces form a symmetric operator only if both owners of a shared
+ * edge hold the same weight and activity for it; beyond 8 (d+1) N 2^-53 the call returns DPGO_ERR_STATE.
+ * DPGO_ERR_INVALID: a member with priors (a non-zero constant term of G), members on different devices or streams or of
+ * different (d, r), a table that does not tile [0, N), an nbr_pose entry out of range; DPGO_ERR_HIP without a device.
+ * Out of scope: several ranks, priors, the staircase escape. */
+typedef struct dpgo_team_member {
+  dpgo_problem_t h;
+  int first;
+  const int32_t* nbr_pose; /* host, ncols entries (may be NULL when the member has no column slot) */
+} dpgo_team_member;
+typedef struct dpgo_team_certify_result {
+  dpgo_certify_result cert;
+  double symmetry_defect;
+  int members;
+  int poses;
+} dpgo_team_certify_result;
+/* witness_team_dev: (d+1)N doubles in team order, or NULL */
+int dpgo_team_certify_device(const dpgo_team_member* members, int n_members, const double* X_team_dev,
+                             const dpgo_certify_params* params, dpgo_team_certify_result* result,
+                             double* witness_team_dev);
+/* CV = V C(X) on team vectors (device); for tests */
+int dpgo_team_certificate_apply_device(const dpgo_team_member* members, int n_members, const double* X_team_dev,
+                                       const double* V_team_dev, double* CV_team_dev);
+/* the same, and the r x r block V (CV)^T the kernel sums on the way (host, row-major; may be NULL); for tests */
+int dpgo_team_certificate_apply_gram_device(const dpgo_team_member* members, int n_members, const double* X_team_dev,
+                                            const double* V_team_dev, double* CV_team_dev, double* vcv_host);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1298,4 +1298,26 @@ inline Matrix solveRobustPGO(std::vector<RelativeSEMeasurement>& mutable_measure
   return T;
 }
 
+// Certificate of a team's iterate from the agents' own handles (dpgo_team_certify_device): problems
+// in team order, all on one device and stream, each with its coupling set (setCouplingFromPoseGraph); firsts[a] = first tile
+// of agent a in the team vector, nbr_pose[a][k] = team tile of column slot k of its coupling; X_team_dev: the team's
+// iterate on the device ((d+1) r doubles per tile); witness_team_dev: (d+1)N doubles on the device, or null.
+inline dpgo_team_certify_result certifyTeam(const std::vector<QuadraticProblem*>& problems, const std::vector<int>& firsts,
+                                            const std::vector<std::vector<int32_t>>& nbr_pose, const double* X_team_dev,
+                                            const dpgo_certify_params* params = nullptr,
+                                            double* witness_team_dev = nullptr) {
+  if (firsts.size() != problems.size() || nbr_pose.size() != problems.size())
+    throw std::invalid_argument("certifyTeam: one first tile and one nbr_pose list per problem");
+  std::vector<dpgo_team_member> mem(problems.size());
+  for (size_t a = 0; a < problems.size(); ++a) {
+    problems[a]->refresh();
+    mem[a].h = problems[a]->handle();
+    mem[a].first = firsts[a];
+    mem[a].nbr_pose = nbr_pose[a].empty() ? nullptr : nbr_pose[a].data();
+  }
+  dpgo_team_certify_result res{};
+  check(dpgo_team_certify_device(mem.data(), (int)mem.size(), X_team_dev, params, &res, witness_team_dev));
+  return res;
+}
+
 }  // namespace dpgo_hip
