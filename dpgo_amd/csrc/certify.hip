@@ -341,9 +341,7 @@ int certify_impl(dpgo_problem_s* p, const double* X, const dpgo_certify_params* 
     c.sym = usable;
   }
   // Lambda at X (and f, |rgrad| on the way)
-  CHK(launch_grad(p, X, nullptr, c.S, nullptr, nullptr, c.sym));
-  CHK(launch_rtr_begin(p, 0.0, 1.0, 1.0, 0, 0));
-  CHK(poll_state(p));
+  CHK(eval_state(p, X, c.S, c.sym));
   res->gradnorm = p->hstate->ngf;
   double scale = 0.0;
   CHK(q_scale(p, c.qdiag, &scale));
@@ -782,12 +780,9 @@ int team_setup(const dpgo_team_member* mem, Team& t, const double* X, double* S,
         launch(k_cert_gather_tiles, flat_grid((size_t)nc * T), 0, q->stream, X, t.nbr[a], T, nc, nbuf);
         HIPC(hipGetLastError());
       }
-      CHK(launch_spmm(q, q->C, nbuf, q->G0, q->G));
-      q->has_G = true;
+      CHK(refresh_G(q, nbuf));
     }
-    CHK(launch_grad(q, Xa, nullptr, Sa, nullptr, nullptr, false));
-    CHK(launch_rtr_begin(q, 0.0, 1.0, 1.0, 0, 0));
-    CHK(poll_state(q));  // (synchronises: nbuf and the host's nbr_pose are free again)
+    CHK(eval_state(q, Xa, Sa));  // (synchronises: nbuf and the host's nbr_pose are free again)
     sum += q->hstate->ngf * q->hstate->ngf;
     hm[a].Q = q->Q.dev();
     hm[a].C = q->C.rowptr ? q->C.dev() : BsrDev{t.no_rows, nullptr, nullptr};

@@ -297,6 +297,23 @@ inline std::string options_describe() {
   return s;
 }
 
+// What a solve has decided before its first launch (plan_solve, solve.hip): kept by a begin / end solve between the calls.
+struct SolvePlan {
+  dpgo_ropt_params prm{};  // the caller's, DPGO_PRECOND_AUTO resolved to what the handle currently runs
+  bool is_auto = false;    // (the caller asked for DPGO_PRECOND_AUTO: the solve reports to auto_update)
+  const double* dinv = nullptr;  // borrowed: the handle's block-Jacobi factors, or none
+  std::chrono::steady_clock::time_point t0;
+  bool one_launch = false;  // eligible for the one-launch solve (k_rtr_persist)
+};
+
+// The caller's device iterate as the handle's x1 for the duration of a solve (solve.hip).  Borrows, owns nothing.
+struct BorrowedIterate {
+  double* own_x1 = nullptr;  // the handle's x1, put back by end()
+  double* staged = nullptr;  // the caller's iterate when it is not 16-byte aligned: the solve runs on own_x1
+  int begin(dpgo_problem_s* p, double* X_dev);
+  int end(dpgo_problem_s* p, int rc);  // rc: what the solve returned; copies out after a successful solve only
+};
+
 }  // namespace dpgo_host
 using namespace dpgo_host;
 
@@ -500,13 +517,8 @@ struct dpgo_problem_s {
   struct Pending {
     bool active = false;    // begin has been called
     bool launched = false;  // the one-launch solve is in flight (else: the solve already ran, `result` holds its outcome)
-    dpgo_ropt_params resolved{};
-    bool is_auto = false;
-    // borrowed, not owned: the handle's factors or none, the handle's x1, the caller's buffer
-    const double* dinv = nullptr;
-    double* own_x1 = nullptr;
-    double* staged_x = nullptr;  // the caller's iterate when it is not 16-byte aligned (the solve runs on own_x1)
-    std::chrono::steady_clock::time_point t0;
+    SolvePlan plan;         // of the solve in flight: what one_launch_collect and a fallback after a time-out go by
+    BorrowedIterate x;      // the caller's iterate, returned by the call that ends the solve
     dpgo_ropt_result result{};
   } pending;
   DevBuf<PersistCtrl> pctrl;
@@ -705,8 +717,6 @@ struct PersistGeo {
   int split = 0, mt = 0, wgs = 0, slots = 0;
 };
 
-enum { RUN_FULL = 0, RUN_BEGIN = 1, RUN_END = 2 };  // run_optimize phases (solve.hip)
-
 // ---- problem.hip
 int set_device(dpgo_problem_s* p);
 int upload_bsr(Bsr& m, int nrows, int ncols, int nnzb, int b, const int32_t* rowptr, const int32_t* colidx,
@@ -733,6 +743,8 @@ int launch_retract(dpgo_problem_s* p, const double* X, const double* eta, double
 int launch_rtr_update(dpgo_problem_s* p);
 int launch_precond(dpgo_problem_s* p, const double* X, const double* V, const double* dinv, double* Z);
 int launch_rtr_begin(dpgo_problem_s* p, double tol, double Delta0, double Dmax, int max_inner, int tiny);
+int eval_state(dpgo_problem_s* p, const double* X, double* S = nullptr, bool sym = false);
+int refresh_G(dpgo_problem_s* p, const double* nbr_tiles);
 int check_ready(dpgo_problem_s* p);
 int h2d(dpgo_problem_s* p, double* dst, const double* src);
 int d2h(dpgo_problem_s* p, double* dst, const double* src);
@@ -794,7 +806,11 @@ int rtr_outer_iteration(dpgo_problem_s* p, const dpgo_ropt_params* prm, const do
 int auto_units_jacobi(dpgo_problem_s* p);
 int auto_units_additive(dpgo_problem_s* p);
 void auto_update(dpgo_problem_s* p, const dpgo_ropt_params* prm, int used, int products);
-int run_optimize(dpgo_problem_s* p, const dpgo_ropt_params* prm, dpgo_ropt_result* res, int phase = RUN_FULL);
+int plan_solve(dpgo_problem_s* p, const dpgo_ropt_params* prm, SolvePlan* plan);
+int one_launch_enqueue(dpgo_problem_s* p, const SolvePlan& plan, bool* used);
+int one_launch_collect(dpgo_problem_s* p, const SolvePlan& plan, dpgo_ropt_result* res, bool* ok);
+int multi_launch_solve(dpgo_problem_s* p, const SolvePlan& plan, dpgo_ropt_result* res);
+int run_optimize(dpgo_problem_s* p, const dpgo_ropt_params* prm, dpgo_ropt_result* res);
 int tune_launch_caps(dpgo_problem_s* p);
 int tune_persist(dpgo_problem_s* p);
 

@@ -336,6 +336,23 @@ int launch_rtr_begin(dpgo_problem_s* p, double tol, double Delta0, double Dmax, 
   return DPGO_OK;
 }
 
+// f, xqx, xg and |rgrad| of X into p->hstate (and S = Lambda's blocks at X where asked for); synchronises
+int eval_state(dpgo_problem_s* p, const double* X, double* S, bool sym) {
+  CHK(launch_grad(p, X, nullptr, S, nullptr, nullptr, sym));
+  // (neutral arguments: k_rtr_begin sums the gradient pass's partials into the state record; the tolerance, the radii, the
+  // tCG budget and the tiny-decrease switch are only stored there for a solve, and none follows)
+  CHK(launch_rtr_begin(p, 0.0, 1.0, 1.0, 0, 0));
+  return poll_state(p);
+}
+
+// PGOAgent::updateX: G from the neighbours' public poses (on the handle's stream)
+int refresh_G(dpgo_problem_s* p, const double* nbr_tiles) {
+  if (!p->C.rowptr) return fail(DPGO_ERR_STATE, "G coupling not set");
+  CHK(launch_spmm(p, p->C, nbr_tiles, p->G0, p->G));
+  p->has_G = true;
+  return DPGO_OK;
+}
+
 int check_ready(dpgo_problem_s* p) {
   if (!p) return fail(DPGO_ERR_INVALID, "null handle");
   if (!p->Q.vals) return fail(DPGO_ERR_STATE, "quadratic matrix Q not set");
@@ -693,12 +710,9 @@ int dpgo_problem_set_G_coupling(dpgo_problem_t p, int ncols, int nnzb, const int
 
 int dpgo_problem_update_G_from_neighbors_device(dpgo_problem_t p, const double* nbr_tiles_dev) {
   if (!p) return fail(DPGO_ERR_INVALID, "null handle");
-  if (!p->C.rowptr) return fail(DPGO_ERR_STATE, "G coupling not set");
-  if (!nbr_tiles_dev && p->C.nnzb > 0) return fail(DPGO_ERR_INVALID, "null neighbour tiles");
+  if (!nbr_tiles_dev && p->C.rowptr && p->C.nnzb > 0) return fail(DPGO_ERR_INVALID, "null neighbour tiles");
   CHK(set_device(p));
-  CHK(launch_spmm(p, p->C, nbr_tiles_dev, p->G0, p->G));
-  p->has_G = true;
-  return DPGO_OK;
+  return refresh_G(p, nbr_tiles_dev);
 }
 
 
@@ -714,9 +728,7 @@ static int eval_common(dpgo_problem_t p, const double* X) {
 int dpgo_problem_f(dpgo_problem_t p, const double* X, double* f) {
   if (!f) return fail(DPGO_ERR_INVALID, "null out");
   CHK(eval_common(p, X));
-  CHK(launch_grad(p, p->x2, nullptr, nullptr, nullptr));
-  CHK(launch_rtr_begin(p, 0.0, 1.0, 1.0, 0, 0));
-  CHK(poll_state(p));
+  CHK(eval_state(p, p->x2));
   *f = p->hstate->f1;
   return DPGO_OK;
 }
@@ -749,9 +761,7 @@ int dpgo_problem_rie_grad(dpgo_problem_t p, const double* X, double* RG) {
 int dpgo_problem_rie_grad_norm(dpgo_problem_t p, const double* X, double* gn) {
   if (!gn) return fail(DPGO_ERR_INVALID, "null out");
   CHK(eval_common(p, X));
-  CHK(launch_grad(p, p->x2, nullptr, nullptr, nullptr));
-  CHK(launch_rtr_begin(p, 0.0, 1.0, 1.0, 0, 0));
-  CHK(poll_state(p));
+  CHK(eval_state(p, p->x2));
   *gn = p->hstate->ngf;
   return DPGO_OK;
 }
@@ -809,9 +819,7 @@ int dpgo_spmm_device(dpgo_problem_t p, const double* V_dev, double* OUT_dev, int
 int dpgo_problem_eval_device(dpgo_problem_t p, const double* X_dev, double* f, double* gradnorm) {
   CHK(check_ready(p));
   if (!X_dev) return fail(DPGO_ERR_INVALID, "null pointer");
-  CHK(launch_grad(p, X_dev, nullptr, nullptr, nullptr));
-  CHK(launch_rtr_begin(p, 0.0, 1.0, 1.0, 0, 0));
-  CHK(poll_state(p));
+  CHK(eval_state(p, X_dev));
   if (f) *f = p->hstate->f1;
   if (gradnorm) *gradnorm = p->hstate->ngf;
   return DPGO_OK;
@@ -821,9 +829,7 @@ int dpgo_problem_eval_device(dpgo_problem_t p, const double* X_dev, double* f, d
 int dpgo_problem_eval_terms_device(dpgo_problem_t p, const double* X_dev, double* xqx, double* xg, double* g2) {
   CHK(check_ready(p));
   if (!X_dev) return fail(DPGO_ERR_INVALID, "null pointer");
-  CHK(launch_grad(p, X_dev, nullptr, nullptr, nullptr));
-  CHK(launch_rtr_begin(p, 0.0, 1.0, 1.0, 0, 0));
-  CHK(poll_state(p));
+  CHK(eval_state(p, X_dev));
   if (xqx) *xqx = p->hstate->xqx;
   if (xg) *xg = p->hstate->xg;
   if (g2) *g2 = p->hstate->ngf * p->hstate->ngf;

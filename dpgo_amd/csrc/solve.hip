@@ -135,8 +135,8 @@ int tcg_dirs_ensure(dpgo_problem_s* p, int max_inner, bool may_alloc) {
 // one 256-thread workgroup; capacity = two per CU: every variant of the kernel is compiled for two workgroups per CU
 // -- registers, LDS --, whatever else runs), reserved for the duration of the solve.  A handle that cannot reserve runs the
 // multi-launch scheme.  Other processes are not covered: every in-kernel spin is bounded, a time-out poisons the state
-// record (rtr_stop = kPersistPoison) and leaves the caller's iterate untouched; run_optimize then runs the solve with the
-// multi-launch scheme.
+// record (rtr_stop = kPersistPoison) and leaves the caller's iterate untouched; the solve then runs on the multi-launch
+// scheme (one_launch_collect).
 constexpr int kMaxDevices = 64;
 std::atomic<int> g_warnings{0};  // warnings printed to stderr so far (dpgo_warning_count)
 std::atomic<int> g_persist_used[kMaxDevices];
@@ -572,48 +572,35 @@ void auto_update(dpgo_problem_s* p, const dpgo_ropt_params* prm, int used, int p
   }
 }
 
-// phase: RUN_FULL = the whole solve, synchronously.  RUN_BEGIN = enqueue only: if the solve is a one-launch solve
-// (k_rtr_persist) the call returns with the launch, its commit kernel and the read-backs in flight (p->pending.launched);
-// otherwise the solve runs to completion right here.  RUN_END = collect what RUN_BEGIN left in flight (waits for the
-// stream, reads the state record, falls back to the multi-launch scheme after a time-out exactly as the synchronous call).
-int run_optimize(dpgo_problem_s* p, const dpgo_ropt_params* prm, dpgo_ropt_result* res, int phase) {
-  // X is in p->x1 on entry and on exit.  src/QuadraticOptimizer.cpp:26-48.
-  auto t0 = std::chrono::steady_clock::now();
-  Counters cnt;
-  std::memset(res, 0, sizeof(*res));
-  res->tCGStatus = DPGO_TCG_MAXITER;
-  const bool resume = phase == RUN_END;
-  if (p->hctrl && !resume) std::memset(p->hctrl, 0, sizeof(PersistCtrl));
-  if (!resume) p->dirs_on = false;  // (the one-launch solve keeps its vectors on chip)
-  struct SlotGuard {  // the resident-slot reservation of the persistent kernel lives as long as the solve
-    dpgo_problem_s* p;
-    bool armed;
-    ~SlotGuard() {
-      if (armed) persist_release(p);
-    }
-  } slot_guard{p, true};
-  dpgo_ropt_params resolved = resume ? p->pending.resolved : *prm;  // DPGO_PRECOND_AUTO -> what this handle currently runs
-  if (!resume) {
-    if (prm->precond == DPGO_PRECOND_AUTO) p->auto_decide();
-    if (prm->precond == DPGO_PRECOND_AUTO)  // (the multilevel choice: the additive form wherever its persistent kernel runs)
-      resolved.precond = (p->auto_ml && prm->method == DPGO_METHOD_RTR)
-                             ? ((additive_available(p) && !p->ml_user_ks) ? DPGO_PRECOND_ADDITIVE : DPGO_PRECOND_MULTILEVEL)
-                             : DPGO_PRECOND_BLOCK_JACOBI;
+// A solve is planned (plan_solve), then either enqueued as ONE launch (one_launch_enqueue) and collected
+// (one_launch_collect) -- by the same call, or by dpgo_optimize_device_end for what ..._begin enqueued -- or run on the
+// multi-launch scheme (multi_launch_solve), which is also what follows a one-launch solve that timed out.
+// X is in p->x1 on entry and on exit.  src/QuadraticOptimizer.cpp:26-48.
+
+// Everything a solve decides before its first launch: the preconditioner (and its factors), the storage of Q the tCG-step
+// kernel reads, whether the one-launch kernel may run.
+int plan_solve(dpgo_problem_s* p, const dpgo_ropt_params* prm, SolvePlan* plan) {
+  plan->t0 = std::chrono::steady_clock::now();
+  if (p->hctrl) std::memset(p->hctrl, 0, sizeof(PersistCtrl));
+  p->dirs_on = false;  // (the one-launch solve keeps its vectors on chip)
+  plan->prm = *prm;    // DPGO_PRECOND_AUTO -> what this handle currently runs
+  plan->is_auto = prm->precond == DPGO_PRECOND_AUTO;
+  if (plan->is_auto) {
+    p->auto_decide();
+    // (the multilevel choice: the additive form wherever its persistent kernel runs)
+    plan->prm.precond = (p->auto_ml && prm->method == DPGO_METHOD_RTR)
+                            ? ((additive_available(p) && !p->ml_user_ks) ? DPGO_PRECOND_ADDITIVE : DPGO_PRECOND_MULTILEVEL)
+                            : DPGO_PRECOND_BLOCK_JACOBI;
   }
-  const bool is_auto = resume ? p->pending.is_auto : prm->precond == DPGO_PRECOND_AUTO;
-  if (resume) t0 = p->pending.t0;
-  prm = &resolved;
-  const double* dinv = nullptr;
-  if (resume) {
-    dinv = p->pending.dinv;
-  } else
+  prm = &plan->prm;
+  plan->dinv = nullptr;
   if (prm->precond == DPGO_PRECOND_BLOCK_JACOBI) {
     CHK(build_dinv(p, prm->precond_shift));
-    dinv = p->dinv;
+    plan->dinv = p->dinv;
   } else if (prm->precond == DPGO_PRECOND_MULTILEVEL) {
     // built lazily for the current Q, like the reference's factor (src/PoseGraph.cpp:582-586)
     CHK(ml_ensure(p, prm->precond_shift));
-    dinv = p->dinv;  // the smoother's block-Jacobi factors (same shift)
+    plan->dinv = p->dinv;  // the smoother's block-Jacobi factors (same shift)
   } else if (prm->precond == DPGO_PRECOND_ADDITIVE) {
     if (prm->method != DPGO_METHOD_RTR) return fail(DPGO_ERR_UNSUPPORTED, "the additive preconditioner exists inside the tCG loop only");
     if (!additive_split_of(p) && !additive_plan(p).split)
@@ -621,80 +608,85 @@ int run_optimize(dpgo_problem_s* p, const dpgo_ropt_params* prm, dpgo_ropt_resul
                                             std::to_string(ml_tile(p->b, 1)) + " poses" +
                                             (additive_tiles(p) == 2 ? ", or of two" : "; dpgo_problem_additive_tiles: two") + ")");
     CHK(ml_ensure(p, prm->precond_shift, /*additive=*/true));
-    dinv = p->dinv;
+    plan->dinv = p->dinv;
   } else if (prm->precond != DPGO_PRECOND_NONE) {
     return fail(DPGO_ERR_INVALID, "unknown preconditioner");
   }
-  if (!resume) {
-    p->loop_extra_bytes = 0;
-    if (prm->precond == DPGO_PRECOND_MULTILEVEL && !p->ml.empty()) {
-      const size_t nd = (size_t)p->dense.lda;
-      size_t bytes = nd * nd * (size_t)(p->ml_coarse_bits / 8) / (p->ml_use_dense_sym() ? 2 : 1);
-      const auto& L0 = p->ml[0];
-      bytes += (size_t)L0.AP.nnzb * (sizeof(double) * p->b * p->b + sizeof(int32_t)) + sizeof(double) * (size_t)p->n * p->b * p->b;
-      bytes += 3 * p->vec_bytes();
-      p->loop_extra_bytes = bytes;
-    }
-    CHK(resolve_tcg_storage(p));
-    if (prm->precond == DPGO_PRECOND_MULTILEVEL) CHK(ml_ops32_ensure(p));  // (opt-in fp32 operator copies of the cycle)
+  p->loop_extra_bytes = 0;
+  if (prm->precond == DPGO_PRECOND_MULTILEVEL && !p->ml.empty()) {
+    const size_t nd = (size_t)p->dense.lda;
+    size_t bytes = nd * nd * (size_t)(p->ml_coarse_bits / 8) / (p->ml_use_dense_sym() ? 2 : 1);
+    const auto& L0 = p->ml[0];
+    bytes += (size_t)L0.AP.nnzb * (sizeof(double) * p->b * p->b + sizeof(int32_t)) + sizeof(double) * (size_t)p->n * p->b * p->b;
+    bytes += 3 * p->vec_bytes();
+    p->loop_extra_bytes = bytes;
   }
+  CHK(resolve_tcg_storage(p));
+  if (prm->precond == DPGO_PRECOND_MULTILEVEL) CHK(ml_ops32_ensure(p));  // (opt-in fp32 operator copies of the cycle)
   // ---- blocks in the latency regime: the whole solve is ONE persistent launch (k_rtr_persist) and one read-back.  The
   // single-iteration radius-shrink mode (:80-99) and the polling mode keep the multi-launch scheme.
-  const bool add = prm->precond == DPGO_PRECOND_ADDITIVE;
   // (the in-kernel all-reduce tags its granules with salt | step, the step counter in the low 20 bits: a solve whose
   // parameters allow more reductions than that -- at most 3 per tCG iteration + 4 per outer iteration + 1 -- keeps the
   // multi-launch scheme)
   const bool epochs_fit = (long long)std::max(1, prm->RTR_iterations) * (3LL * std::max(0, prm->RTR_tCG_iterations) + 4) + 1 < (1LL << 20);
-  if (resume || (prm->method == DPGO_METHOD_RTR && prm->RTR_iterations != 1 && prm->tcg_poll_interval <= 0 && p->persist && epochs_fit &&
-                 !p->persist_failed_once && (add || prm->precond == DPGO_PRECOND_BLOCK_JACOBI || prm->precond == DPGO_PRECOND_NONE))) {
-    bool used = resume;
-    if (!resume) CHK(launch_rtr_persistent(p, prm, dinv, &used, add));
-    if (used) {
-      if (!resume) {
-        // (no read-back commands: k_persist_commit has written the state record and the control block into hstate / hctrl)
-        if (phase == RUN_BEGIN) {  // everything of the solve is enqueued: the caller collects it with RUN_END
-          auto& pd = p->pending;
-          pd.launched = true;
-          pd.resolved = resolved;
-          pd.is_auto = is_auto;
-          pd.dinv = dinv;
-          pd.t0 = t0;
-          slot_guard.armed = false;  // (the reservation is released by the collecting call)
-          return DPGO_OK;
-        }
-      }
-      HIPC(hipStreamSynchronize(p->stream));
-      persist_report(p);
-      // (k_persist_commit, which ran behind the solve, saw the same two words: with a poisoned record OR a raised time-out
-      // flag -- some participant gave up, however late -- the caller's iterate has not been touched)
-      if (p->hstate->rtr_stop != kPersistPoison && !p->hctrl->error) {
-        const DevState& h = *p->hstate;
-        res->fInit = h.fInit;
-        res->gradNormInit = h.gnInit;
-        res->fOpt = h.f1;
-        res->gradNormOpt = h.ngf;
-        res->tCGStatus = h.outer_iter > 0 ? h.tcg_status : DPGO_TCG_MAXITER;
-        res->rtr_iterations = h.outer_iter;
-        res->rtr_accepted = h.n_accept;
-        res->latest_step_accepted = h.accepted_last;
-        res->tcg_iterations = h.n_hess;
-        res->precond_used = prm->precond;
-        res->spmm_count = 1 + 2 * h.outer_iter + h.n_hess;
-        if (is_auto) auto_update(p, prm, prm->precond, h.n_hess);
-        res->success = 1;  // :44
-        res->elapsedMs = 1e3 * std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-        return DPGO_OK;
-      }
-      // a time-out (the launch's workgroups were not all resident: another process on the device): the caller's iterate is
-      // untouched; this handle stops using the kernel and the solve runs on the multi-launch scheme
-      p->persist_failed_once = true;
-      p->pctrl_dirty = true;
-      persist_release(p);
-      if (options().persist_verbose)
-        std::fprintf(stderr, "dpgo_hip: persistent solve timed out; this handle continues with the multi-launch scheme\n");
-    }
+  plan->one_launch = prm->method == DPGO_METHOD_RTR && prm->RTR_iterations != 1 && prm->tcg_poll_interval <= 0 && p->persist &&
+                     epochs_fit && !p->persist_failed_once &&
+                     (prm->precond == DPGO_PRECOND_ADDITIVE || prm->precond == DPGO_PRECOND_BLOCK_JACOBI ||
+                      prm->precond == DPGO_PRECOND_NONE);
+  return DPGO_OK;
+}
+
+// *used = false: not launched (no geometry / no free slots) -- the caller runs the multi-launch scheme
+int one_launch_enqueue(dpgo_problem_s* p, const SolvePlan& plan, bool* used) {
+  return launch_rtr_persistent(p, &plan.prm, plan.dinv, used, plan.prm.precond == DPGO_PRECOND_ADDITIVE);
+}
+
+// Waits for an enqueued one-launch solve.  *ok = false: it timed out (the launch's workgroups were not all resident: another
+// process on the device) -- the caller's iterate is untouched, this handle stops using the kernel and the caller runs the
+// solve on the multi-launch scheme.
+int one_launch_collect(dpgo_problem_s* p, const SolvePlan& plan, dpgo_ropt_result* res, bool* ok) {
+  *ok = false;
+  std::memset(res, 0, sizeof(*res));
+  res->tCGStatus = DPGO_TCG_MAXITER;
+  // (no read-back commands: k_persist_commit has written the state record and the control block into hstate / hctrl)
+  HIPC(hipStreamSynchronize(p->stream));
+  persist_report(p);
+  // (k_persist_commit, which ran behind the solve, saw the same two words: with a poisoned record OR a raised time-out
+  // flag -- some participant gave up, however late -- the caller's iterate has not been touched)
+  if (p->hstate->rtr_stop == kPersistPoison || p->hctrl->error) {
+    p->persist_failed_once = true;
+    p->pctrl_dirty = true;
+    persist_release(p);
+    if (options().persist_verbose)
+      std::fprintf(stderr, "dpgo_hip: persistent solve timed out; this handle continues with the multi-launch scheme\n");
+    return DPGO_OK;
   }
-  // the multi-launch scheme from here on: whether this solve's tCG runs keep their directions (every launch follows it)
+  const DevState& h = *p->hstate;
+  res->fInit = h.fInit;
+  res->gradNormInit = h.gnInit;
+  res->fOpt = h.f1;
+  res->gradNormOpt = h.ngf;
+  res->tCGStatus = h.outer_iter > 0 ? h.tcg_status : DPGO_TCG_MAXITER;
+  res->rtr_iterations = h.outer_iter;
+  res->rtr_accepted = h.n_accept;
+  res->latest_step_accepted = h.accepted_last;
+  res->tcg_iterations = h.n_hess;
+  res->precond_used = plan.prm.precond;
+  res->spmm_count = 1 + 2 * h.outer_iter + h.n_hess;
+  if (plan.is_auto) auto_update(p, &plan.prm, plan.prm.precond, h.n_hess);
+  res->success = 1;  // :44
+  res->elapsedMs = 1e3 * std::chrono::duration<double>(std::chrono::steady_clock::now() - plan.t0).count();
+  *ok = true;
+  return DPGO_OK;
+}
+
+int multi_launch_solve(dpgo_problem_s* p, const SolvePlan& plan, dpgo_ropt_result* res) {
+  const dpgo_ropt_params* prm = &plan.prm;
+  const double* dinv = plan.dinv;
+  Counters cnt;
+  std::memset(res, 0, sizeof(*res));
+  res->tCGStatus = DPGO_TCG_MAXITER;
+  // whether this solve's tCG runs keep their directions (every launch follows it)
   p->dirs_on = false;
   if (prm->method == DPGO_METHOD_RTR) CHK(tcg_dirs_ensure(p, prm->RTR_tCG_iterations));
   // statistics before optimisation (:28-29) -- one fused pass: f, rgrad, S
@@ -741,7 +733,7 @@ int run_optimize(dpgo_problem_s* p, const dpgo_ropt_params* prm, dpgo_ropt_resul
         for (int it = 0; it < prm->RTR_iterations; ++it) {
           CHK(rtr_outer_iteration(p, prm, dinv, cnt, polling));
           if (polling ? (p->hstate->rtr_stop != 0) : p->saw_rtr_stop) break;
-          const double el = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+          const double el = std::chrono::duration<double>(std::chrono::steady_clock::now() - plan.t0).count();
           if (prm->time_bound_s > 0 && el > prm->time_bound_s) break;  // Solver.TimeBound (:78)
         }
         CHK(poll_state(p));
@@ -782,11 +774,43 @@ int run_optimize(dpgo_problem_s* p, const dpgo_ropt_params* prm, dpgo_ropt_resul
   }
   res->tcg_iterations = n_hess_total;
   res->precond_used = (prm->precond == DPGO_PRECOND_ADDITIVE && cnt.vcycle_for_additive) ? DPGO_PRECOND_MULTILEVEL : prm->precond;
-  if (is_auto && prm->method == DPGO_METHOD_RTR) auto_update(p, prm, res->precond_used, n_hess_total);
+  if (plan.is_auto && prm->method == DPGO_METHOD_RTR) auto_update(p, prm, res->precond_used, n_hess_total);
   res->spmm_count = cnt.spmm + n_hess_total;
   res->success = 1;  // :44 (set unconditionally after a solve)
-  res->elapsedMs = 1e3 * std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+  res->elapsedMs = 1e3 * std::chrono::duration<double>(std::chrono::steady_clock::now() - plan.t0).count();
   return DPGO_OK;
+}
+
+// The whole solve, synchronously.
+int run_optimize(dpgo_problem_s* p, const dpgo_ropt_params* prm, dpgo_ropt_result* res) {
+  struct SlotGuard {  // the resident-slot reservation of the persistent kernel lives as long as the solve
+    dpgo_problem_s* p;
+    ~SlotGuard() { persist_release(p); }
+  } slot_guard{p};
+  SolvePlan plan;
+  bool used = false, ok = false;
+  CHK(plan_solve(p, prm, &plan));
+  if (plan.one_launch) CHK(one_launch_enqueue(p, plan, &used));
+  if (used) CHK(one_launch_collect(p, plan, res, &ok));
+  return ok ? DPGO_OK : multi_launch_solve(p, plan, res);
+}
+
+int BorrowedIterate::begin(dpgo_problem_s* p, double* X_dev) {
+  if (!aligned8(X_dev)) return fail(DPGO_ERR_INVALID, "iterate not 8-byte aligned");
+  // the caller's buffer IS the iterate for the duration of the solve (no copies in or out): accepted steps are written
+  // into it by k_rtr_update, rejected ones leave it untouched -- unless it is not 16-byte aligned (the tCG and cycle
+  // kernels read the iterate in 16-byte pieces): then the solve runs on the handle's own x1, copied in here and out when
+  // the solve has ended -- stream-ordered, as the solve itself
+  own_x1 = p->x1;
+  staged = aligned16(X_dev) ? nullptr : X_dev;
+  if (staged) HIPC(hipMemcpyAsync(own_x1, staged, p->vec_bytes(), hipMemcpyDeviceToDevice, p->stream));
+  else p->x1 = X_dev;
+  return DPGO_OK;
+}
+int BorrowedIterate::end(dpgo_problem_s* p, int rc) {
+  p->x1 = own_x1;
+  if (rc == DPGO_OK && staged) HIPC(hipMemcpyAsync(staged, own_x1, p->vec_bytes(), hipMemcpyDeviceToDevice, p->stream));
+  return rc;
 }
 
 // The two kernels of the tCG loop run as persistent grids: one workgroup per resident slot (occupancy x CUs).
@@ -933,17 +957,9 @@ int dpgo_optimize_device(dpgo_problem_t p, const dpgo_ropt_params* params, doubl
   CHK(check_ready(p));
   if (!params || !X_dev || !result) return fail(DPGO_ERR_INVALID, "null pointer");
   if (!aligned8(X_dev)) return fail(DPGO_ERR_INVALID, "X_dev not 8-byte aligned");
-  // the caller's buffer IS the iterate for the duration of the call (no copies in or out): accepted steps are written
-  // into it by k_rtr_update, rejected ones leave it untouched -- unless it is not 16-byte aligned (the tCG and cycle
-  // kernels read the iterate in 16-byte pieces): then the solve runs on the handle's own x1, copied in and out
-  double* own = p->x1;
-  const bool staged = !aligned16(X_dev);
-  if (staged) HIPC(hipMemcpyAsync(own, X_dev, p->vec_bytes(), hipMemcpyDeviceToDevice, p->stream));
-  else p->x1 = X_dev;
-  const int rc = run_optimize(p, params, result);
-  p->x1 = own;
-  if (rc != DPGO_OK) return rc;
-  if (staged) HIPC(hipMemcpyAsync(X_dev, own, p->vec_bytes(), hipMemcpyDeviceToDevice, p->stream));
+  BorrowedIterate x;
+  CHK(x.begin(p, X_dev));
+  CHK(x.end(p, run_optimize(p, params, result)));
   HIPC(hipStreamSynchronize(p->stream));
   return DPGO_OK;
 }
@@ -951,40 +967,30 @@ int dpgo_optimize_device(dpgo_problem_t p, const dpgo_ropt_params* params, doubl
 
 int dpgo_warning_count(void) { return g_warnings.load(); }
 
+// Enqueue only: a one-launch solve is left in flight with its commit kernel (pd.launched; dpgo_optimize_device_end collects
+// it), any other solve runs to completion right here, into pd.result.
+static int begin_solve(dpgo_problem_s* p, const dpgo_ropt_params* prm, dpgo_problem_s::Pending& pd) {
+  CHK(plan_solve(p, prm, &pd.plan));
+  if (pd.plan.one_launch) CHK(one_launch_enqueue(p, pd.plan, &pd.launched));
+  return pd.launched ? DPGO_OK : multi_launch_solve(p, pd.plan, &pd.result);
+}
+
 int dpgo_optimize_device_begin(dpgo_problem_t p, const dpgo_ropt_params* params, double* X_dev,
                                const double* nbr_tiles_dev) {
   CHK(check_ready(p));
   if (!params || !X_dev) return fail(DPGO_ERR_INVALID, "null pointer");
   if (!aligned8(X_dev)) return fail(DPGO_ERR_INVALID, "X_dev not 8-byte aligned");
   if (p->pending.active) return fail(DPGO_ERR_STATE, "a solve of this handle is already in flight (dpgo_optimize_device_end)");
-  if (nbr_tiles_dev) {  // PGOAgent::updateX: G from the neighbours' public poses first (same stream)
-    if (!p->C.rowptr) return fail(DPGO_ERR_STATE, "G coupling not set");
-    CHK(launch_spmm(p, p->C, nbr_tiles_dev, p->G0, p->G));
-    p->has_G = true;
-  }
+  if (nbr_tiles_dev) CHK(refresh_G(p, nbr_tiles_dev));  // (first, on the same stream)
   auto& pd = p->pending;
   pd = dpgo_problem_s::Pending();
-  pd.own_x1 = p->x1;
-  // (a caller's iterate that is not 16-byte aligned: the solve runs on the handle's own x1, copied in here and out when
-  // the solve has ended -- stream-ordered, as the solve itself)
-  if (!aligned16(X_dev)) {
-    pd.staged_x = X_dev;
-    HIPC(hipMemcpyAsync(p->x1, X_dev, p->vec_bytes(), hipMemcpyDeviceToDevice, p->stream));
-  } else {
-    p->x1 = X_dev;
-  }
+  CHK(pd.x.begin(p, X_dev));
   p->persist_stream_ordered = true;
-  dpgo_ropt_result tmp;
-  const int rc = run_optimize(p, params, &tmp, RUN_BEGIN);
+  const int rc = begin_solve(p, params, pd);
   p->persist_stream_ordered = false;
   if (rc != DPGO_OK || !pd.launched) {  // failed, or the solve is not a one-launch solve and has run to completion
-    p->x1 = pd.own_x1;
-    if (rc != DPGO_OK) return rc;
-    if (pd.staged_x) {
-      HIPC(hipMemcpyAsync(pd.staged_x, p->x1, p->vec_bytes(), hipMemcpyDeviceToDevice, p->stream));
-      HIPC(hipStreamSynchronize(p->stream));
-    }
-    pd.result = tmp;
+    CHK(pd.x.end(p, rc));
+    if (pd.x.staged) HIPC(hipStreamSynchronize(p->stream));
   }
   pd.active = true;
   return DPGO_OK;
@@ -1002,10 +1008,11 @@ int dpgo_optimize_device_end(dpgo_problem_t p, dpgo_ropt_result* result) {
     return DPGO_OK;
   }
   pd.launched = false;
-  const int rc = run_optimize(p, &pd.resolved, result, RUN_END);
-  p->x1 = pd.own_x1;
-  if (rc != DPGO_OK) return rc;
-  if (pd.staged_x) HIPC(hipMemcpyAsync(pd.staged_x, p->x1, p->vec_bytes(), hipMemcpyDeviceToDevice, p->stream));
+  bool ok = false;
+  int rc = one_launch_collect(p, pd.plan, result, &ok);
+  if (rc == DPGO_OK && !ok) rc = multi_launch_solve(p, pd.plan, result);  // (after a time-out, as the synchronous call)
+  // (no resident slots to release: launch_rtr_persistent reserves none for a stream-ordered solve, and none were held going in)
+  CHK(pd.x.end(p, rc));
   HIPC(hipStreamSynchronize(p->stream));
   return DPGO_OK;
 }
@@ -1138,19 +1145,10 @@ int dpgo_optimize_device_many(int count, const dpgo_problem_t* handles, const dp
   }
   return run_many(count, handles, after_stream, [&](int k) -> int {
     dpgo_problem_s* p = handles[k];
-    if (nbr_tiles_dev && nbr_tiles_dev[k]) {  // PGOAgent::updateX: G from the neighbours' public poses first
-      if (!p->C.rowptr) return fail(DPGO_ERR_STATE, "G coupling not set");
-      CHK(launch_spmm(p, p->C, nbr_tiles_dev[k], p->G0, p->G));
-      p->has_G = true;
-    }
-    double* own = p->x1;
-    const bool staged = !aligned16(X_dev[k]);  // (as dpgo_optimize_device)
-    if (staged) HIPC(hipMemcpyAsync(own, X_dev[k], p->vec_bytes(), hipMemcpyDeviceToDevice, p->stream));
-    else p->x1 = X_dev[k];
-    const int rc = run_optimize(p, params, &results[k]);
-    p->x1 = own;
-    if (rc == DPGO_OK && staged) HIPC(hipMemcpyAsync(X_dev[k], own, p->vec_bytes(), hipMemcpyDeviceToDevice, p->stream));
-    return rc;
+    if (nbr_tiles_dev && nbr_tiles_dev[k]) CHK(refresh_G(p, nbr_tiles_dev[k]));
+    BorrowedIterate x;
+    CHK(x.begin(p, X_dev[k]));
+    return x.end(p, run_optimize(p, params, &results[k]));
   });
 }
 
@@ -1163,14 +1161,8 @@ int dpgo_problem_eval_terms_device_many(int count, const dpgo_problem_t* handles
     if (!X_dev[k]) return fail(DPGO_ERR_INVALID, "null iterate");
   return run_many(count, handles, after_stream, [&](int k) -> int {
     dpgo_problem_s* p = handles[k];
-    if (nbr_tiles_dev && nbr_tiles_dev[k]) {
-      if (!p->C.rowptr) return fail(DPGO_ERR_STATE, "G coupling not set");
-      CHK(launch_spmm(p, p->C, nbr_tiles_dev[k], p->G0, p->G));
-      p->has_G = true;
-    }
-    CHK(launch_grad(p, X_dev[k], nullptr, nullptr, nullptr));
-    CHK(launch_rtr_begin(p, 0.0, 1.0, 1.0, 0, 0));
-    CHK(poll_state(p));
+    if (nbr_tiles_dev && nbr_tiles_dev[k]) CHK(refresh_G(p, nbr_tiles_dev[k]));
+    CHK(eval_state(p, X_dev[k]));
     terms[3 * k + 0] = p->hstate->xqx;
     terms[3 * k + 1] = p->hstate->xg;
     terms[3 * k + 2] = p->hstate->ngf * p->hstate->ngf;

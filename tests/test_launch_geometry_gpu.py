@@ -1,6 +1,7 @@
 """Launch geometry of the SpMM-family kernels against fp64 references: every (d, r) at 1, 2 and 4 lane groups per pose
 (DPGO_SPLIT) on pose counts around the workgroup tile, forced launch caps (DPGO_GRID_*) on both tile-walk branches of
-tile_iter (kernels/common.h), and caller pointers at an 8-byte offset (include/dpgo_hip.h, "Alignment").
+tile_iter (kernels/common.h), caller pointers at an 8-byte offset (include/dpgo_hip.h, "Alignment"), and what a solve entry
+leaves behind when the solve is refused after it has borrowed the caller's iterate.
 
 Every output leaves through a buffer with a guard region of at least one workgroup tile before and after it: the result
 region is prefilled with NaN, the guards with a sentinel bit pattern; a kernel that skips a tile leaves NaN, one that
@@ -503,3 +504,118 @@ def test_device_solves_at_an_odd_element_offset(oracle):
             assert prob._lib.dpgo_optimize_device(prob.handle, C.byref(cp), bad, C.byref(cr)) == L.ERR_INVALID
             assert prob._lib.dpgo_optimize_device_begin(prob.handle, C.byref(cp), bad, None) == L.ERR_INVALID
             del opt, prob
+
+
+# ---------------------------------------------------------------- D. a solve refused after the iterate was borrowed
+_TINY = {}
+
+
+def _tiny(oracle):
+    """tinyGrid3D at r = 5: (pose graph, n, d, r, lifted chordal initialisation as a flat vector), built once."""
+    if not _TINY:
+        import dpgo_amd
+        om, n = oracle.read_g2o(os.path.join(DATA, "tinyGrid3D.g2o"))
+        pg = dpgo_amd.PoseGraph(0, 5, om.d)
+        pg.setMeasurements(to_product_measurements(om))
+        X0 = np.ascontiguousarray(oracle.lift(oracle.chordal_initialization(om, n), 5)).reshape(-1)
+        _TINY["graph"] = (pg, n, om.d, 5, X0)
+    return _TINY["graph"]
+
+
+def _optimizers(pg, persistent, count):
+    import dpgo_amd
+    opts = []
+    for _ in range(count):
+        prob = dpgo_amd.QuadraticProblem(pg)
+        prob.setPersistent(persistent)
+        opts.append(dpgo_amd.QuadraticOptimizer(prob, dpgo_amd.ROptParameters(precond="jacobi")))
+    return opts
+
+
+def _solve_through(entry, opts, xs):
+    import dpgo_amd
+    if entry == "device":
+        return [opts[0].optimizeDevice(xs[0])]
+    if entry == "begin_end":
+        opts[0].optimizeDeviceBegin(xs[0])
+        return [opts[0].optimizeDeviceEnd()]
+    return dpgo_amd.solver.optimize_device_many(opts, xs)
+
+
+def _fresh_solve(oracle, entry, persistent):
+    """(tcg_iterations, rtr_iterations, fOpt, iterate) per handle of the ordinary solve through `entry` on fresh handles and
+    aligned iterates; computed once per (entry, persistent), the handles released before it returns."""
+    key = (entry, persistent)
+    if key not in _TINY:
+        import torch
+        pg, n, d, r, X0 = _tiny(oracle)
+        opts = _optimizers(pg, persistent, 2 if entry == "many" else 1)
+        xs = [torch.from_numpy(X0).to("cuda") for _ in opts]
+        torch.cuda.synchronize()
+        res = _solve_through(entry, opts, xs)
+        torch.cuda.synchronize()
+        _TINY[key] = [(q.tcg_iterations, q.rtr_iterations, q.fOpt, x.cpu().numpy()) for q, x in zip(res, xs)]
+    return _TINY[key]
+
+
+@pytest.mark.parametrize("offset", [0, 1])
+@pytest.mark.parametrize("persistent", [False, True])
+@pytest.mark.parametrize("entry", ["device", "begin_end", "many"])
+def test_refused_solve_returns_the_borrowed_iterate(oracle, entry, persistent, offset):
+    """A solve that the host refuses AFTER the entry has borrowed the caller's iterate (an unknown preconditioner:
+    ERR_INVALID; the additive preconditioner under RGD: ERR_UNSUPPORTED -- both found while the solve is planned, before any
+    of its launches) leaves the whole guarded buffer bitwise as it was, allocates nothing, leaves no solve in flight, and
+    hands the handle its own x1 back: the ordinary solve that follows through the same entry on the same handle is the
+    fresh handle's (iteration counts equal, fOpt to 1e-9 relative, iterate to 1e-6 -- the odd-offset test's tolerances for
+    "same solve, other buffer").  tinyGrid3D, d = 3, r = 5; aligned iterates and iterates at element offset 1 (staged)."""
+    import torch
+    import dpgo_amd.lib as L
+    from dpgo_amd.solver import _ptr_array
+    pg, n, d, r, X0 = _tiny(oracle)
+    want = _fresh_solve(oracle, entry, persistent)
+    opts = _optimizers(pg, persistent, len(want))
+    lib = opts[0].problem_._lib
+    handles = [o.problem_.handle for o in opts]
+    guard = guard_of(d, r) + offset  # (an odd guard puts the body at an odd element offset)
+    bufs = [Guarded(X0.size, guard, device=True, body=X0, guard_nan=True) for _ in opts]
+    xs = [b.body for b in bufs]
+    assert all(x.data_ptr() % 16 == 8 * offset for x in xs)
+    before = [b.buf.cpu().numpy().view(np.uint64).copy() for b in bufs]
+
+    def live():
+        a, b = C.c_longlong(), C.c_longlong()
+        L.check(lib.dpgo_debug_live_allocations(C.byref(a), C.byref(b)))
+        return a.value, b.value
+
+    def call(cp):
+        if entry == "device":
+            return lib.dpgo_optimize_device(handles[0], C.byref(cp), L.ptr(xs[0]), C.byref(L.RoptResultC()))
+        if entry == "begin_end":
+            return lib.dpgo_optimize_device_begin(handles[0], C.byref(cp), L.ptr(xs[0]), None)
+        res = (L.RoptResultC * len(opts))()
+        return lib.dpgo_optimize_device_many(len(opts), _ptr_array([h.value for h in handles]), C.byref(cp),
+                                             _ptr_array([L.ptr(x) for x in xs]), None, None, res)
+
+    for changes, code in (({"precond": 99}, L.ERR_INVALID),
+                          ({"method": L.METHOD_RGD, "precond": L.PRECOND_ADDITIVE}, L.ERR_UNSUPPORTED)):
+        cp = L.RoptParamsC()
+        lib.dpgo_ropt_params_default(C.byref(cp))
+        for k, v in changes.items():
+            setattr(cp, k, v)
+        held = live()
+        assert call(cp) == code, changes
+        assert live() == held, changes
+        if entry == "begin_end":  # no solve is in flight
+            assert lib.dpgo_optimize_device_end(handles[0], C.byref(L.RoptResultC())) == L.ERR_STATE
+        torch.cuda.synchronize()
+        for b, was in zip(bufs, before):
+            assert np.array_equal(b.buf.cpu().numpy().view(np.uint64), was), changes
+
+    res = _solve_through(entry, opts, xs)
+    torch.cuda.synchronize()
+    for q, b, was, (tcg, rtr, f, x) in zip(res, bufs, before, want):
+        bits = b.buf.cpu().numpy().view(np.uint64)
+        assert np.array_equal(bits[:guard], was[:guard]) and np.array_equal(bits[guard + X0.size:], was[guard + X0.size:])
+        assert (q.tcg_iterations, q.rtr_iterations) == (tcg, rtr)
+        assert abs(q.fOpt - f) <= 1e-9 * abs(f)
+        assert relerr(b.body.cpu().numpy(), x) < 1e-6
