@@ -651,10 +651,15 @@ int dpgo_exchange_plan_run(dpgo_exchange_plan_t pl, void* stream) {
 
 
 // ---- ordering words of the peer-store transport (kernels/agent.h: k_flags_write / k_flags_wait) ----
+// (a table longer than kFlagCap goes out in several launches: a null word anywhere is refused before the first of them)
+static int flag_words_ok(int n, unsigned long long* const* words_dev) {
+  for (int k = 0; k < n; ++k)
+    if (!words_dev[k]) return fail(DPGO_ERR_INVALID, "null ordering word");
+  return DPGO_OK;
+}
 static int flag_table(int n, unsigned long long* const* words_dev, const unsigned long long* values, int first, FlagTable* t) {
   t->n = std::min(kFlagCap, n - first);
   for (int k = 0; k < t->n; ++k) {
-    if (!words_dev[first + k]) return fail(DPGO_ERR_INVALID, "null ordering word");
     t->p[k] = words_dev[first + k];
     t->v[k] = values[first + k];
   }
@@ -662,6 +667,7 @@ static int flag_table(int n, unsigned long long* const* words_dev, const unsigne
 }
 int dpgo_flags_write_device(int n, unsigned long long* const* words_dev, const unsigned long long* values, void* stream) {
   if (n < 0 || (n > 0 && (!words_dev || !values))) return fail(DPGO_ERR_INVALID, "bad ordering-word arguments");
+  CHK(flag_words_ok(n, words_dev));
   for (int first = 0; first < n; first += kFlagCap) {
     FlagTable t;
     CHK(flag_table(n, words_dev, values, first, &t));
@@ -673,6 +679,7 @@ int dpgo_flags_write_device(int n, unsigned long long* const* words_dev, const u
 namespace {
 int flags_wait(int n, unsigned long long* const* words_dev, const unsigned long long* values, long long timeout_ms,
                unsigned long long* err_word, void* stream) {
+  CHK(flag_words_ok(n, words_dev));
   for (int first = 0; first < n; first += kFlagCap) {
     FlagTable t;
     CHK(flag_table(n, words_dev, values, first, &t));

@@ -658,7 +658,8 @@ int dpgo_exchange_plan_destroy(dpgo_exchange_plan_t plan);
  * memory both sides map.  write: words_dev[k] <- values[k] (system-scope release store), enqueued BEHIND the kernel that
  * produced the data.  wait: the stream stalls until every word >= its value (system-scope acquire loads), enqueued IN
  * FRONT of the kernel that consumes the data; a word that does not arrive within timeout_ms traps the waiting kernel (the
- * process fails loudly; nothing hangs).  Host arrays of device pointers / values; any n. */
+ * process fails loudly; nothing hangs).  Host arrays of device pointers / values; any n (32 words per launch).  A null
+ * word anywhere in the table is refused with DPGO_ERR_INVALID before the first launch: no word is written or waited for. */
 int dpgo_flags_write_device(int n, unsigned long long* const* words_dev, const unsigned long long* values, void* stream);
 int dpgo_flags_wait_device(int n, unsigned long long* const* words_dev, const unsigned long long* values, int timeout_ms,
                            void* stream);
