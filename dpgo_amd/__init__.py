@@ -14,11 +14,13 @@ from .measurements import RelativeSEMeasurements, partition_by_ranges, partition
 from .solver import (LiftedSEManifold, PoseGraph, QuadraticOptimizer, QuadraticProblem,  # noqa: E402
                      ROptParameters, ROPTResult)
 
-from .certificate import CertificateResult, CertifiedPGOResult, solveCertifiedPGO  # noqa: E402
+from .certificate import (CertificateResult, CertifiedPGOResult, DistributedCertifiedPGOResult,  # noqa: E402
+                          solveCertifiedDistributedPGO, solveCertifiedPGO)
 from .trajectory import (load_trajectory, log_measurements, log_trajectory, round_trajectory,  # noqa: E402
                          round_trajectory_device)
 
 __all__ = ["load_trajectory", "log_measurements", "log_trajectory", "round_trajectory", "round_trajectory_device",
            "DpgoError", "device_count", "RelativeSEMeasurements", "partition_contiguous", "partition_by_ranges", "read_g2o_file",
            "LiftedSEManifold", "PoseGraph", "QuadraticOptimizer", "QuadraticProblem", "ROptParameters",
-           "ROPTResult", "CertificateResult", "CertifiedPGOResult", "solveCertifiedPGO"]
+           "ROPTResult", "CertificateResult", "CertifiedPGOResult", "solveCertifiedPGO",
+           "DistributedCertifiedPGOResult", "solveCertifiedDistributedPGO"]

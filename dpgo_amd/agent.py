@@ -999,6 +999,19 @@ class RBCDCluster:
         from .certificate import certify_team
         return certify_team(self.agents, **params)
 
+    def team_cost_and_gradnorm(self) -> Tuple[float, float]:
+        """Central cost f(X) and Riemannian gradient norm of the team's current iterate from the agents' own blocks in one
+        launch (dpgo_amd.certificate.evaluate_team): no exchange, the agents' G and neighbour buffers stay as they are.
+        One process, one device, as certify(); central_cost_and_gradnorm() is the form that works across ranks."""
+        if self.world > 1:
+            raise NotImplementedError("RBCDCluster.team_cost_and_gradnorm: a team spread over %d ranks is out of scope "
+                                      "(one process, one device)" % self.world)
+        if self.waiting_agents():
+            raise NotImplementedError("RBCDCluster.team_cost_and_gradnorm: agents %s are not in the global frame yet"
+                                      % self.waiting_agents())
+        from .certificate import evaluate_team
+        return evaluate_team(self.agents)
+
     def block_terms(self) -> np.ndarray:
         """[num_agents, 2] array of (0.5 (xqx + xg), |rgrad_a|^2) per agent, identical on every rank."""
         self.exchange(None)

@@ -111,6 +111,9 @@ struct Team {
   DevBuf<CertTile> tiles;
   DevBuf<double> tin, tout;          // 16-byte-aligned staging of a slice the multilevel cycle cannot take in place
 };
+// workgroups of a launch over the team's tile table: at most the first member's DPGO_GRID_HESS cap (second trips can be
+// forced as for k_cert_apply)
+int team_grid(const Team& t) { return std::max(1, std::min(t.ntiles, t.h[0]->cap_h)); }
 
 struct Cert {
   dpgo_problem_s* p;  // (a team: its first member -- the stream, the device, the launch cap)
@@ -157,8 +160,7 @@ struct Cert {
 
   // CW = W C(X); with wcw != null also W CW^T (r x r, row-major) on the host
   int apply(const double* W, double* CW, std::vector<double>* wcw = nullptr) {
-    // a team: one launch, at most the first member's DPGO_GRID_HESS cap (second trips can be forced as for k_cert_apply)
-    const int g = team ? std::max(1, std::min(team->ntiles, p->cap_h)) : sym ? p->grid_outer_sym() : p->grid_s();
+    const int g = team ? team_grid(*team) : sym ? p->grid_outer_sym() : p->grid_s();  // (a team: one launch)
     if (team) {
       CHK(dispatch_dr(d, r, [&](auto D, auto R) {
         return launch(k_cert_apply_team<D, R>, g, 0, p->stream, team->members, team->tiles, team->ntiles, W, CW, part);
@@ -750,31 +752,51 @@ int team_check(const dpgo_team_member* mem, int n_members, Team& t) {
   return DPGO_OK;
 }
 
-// device tables, every G_a from the team's X (the member's linear term as an exchange of X would leave it), every member's
-// S, f and |rgrad| (S: the team's Lambda blocks, [N, d, d]); gn2 = sum |rgrad_a|^2 in member order
-int team_setup(const dpgo_team_member* mem, Team& t, const double* X, double* S, double* gn2) {
+// device tables of the team kernels (k_cert_apply_team, k_team_eval): members, tiles, every member's nbr_pose.  S: the team's
+// Lambda blocks [N, d, d] the member table points into, or null for a kernel that reads none
+int team_tables(const dpgo_team_member* mem, Team& t, double* S) {
   dpgo_problem_s* p0 = t.h[0];
   CHK(set_device(p0));
-  const int d = p0->d, T = p0->T, P = (64 / (d + 1)) * kWaves, na = (int)t.h.size();
-  int nmax = 0, cmax = 0;
-  for (dpgo_problem_s* q : t.h) {
-    nmax = std::max(nmax, q->n);
-    cmax = std::max(cmax, q->C.rowptr ? q->C.ncols : 0);
-  }
+  const int d = p0->d, P = (64 / (d + 1)) * kWaves, na = (int)t.h.size();
+  int nmax = 0;
+  for (dpgo_problem_s* q : t.h) nmax = std::max(nmax, q->n);
   CHK(t.no_rows.alloc((size_t)nmax + 1));
   HIPC(hipMemsetAsync(t.no_rows, 0, sizeof(int32_t) * ((size_t)nmax + 1), p0->stream));
-  DevBuf<double> nbuf;  // neighbour tiles of one member at a time
-  CHK(nbuf.alloc((size_t)std::max(cmax, 1) * T));
   std::vector<CertMember> hm(na);
   std::vector<CertTile> ht;
   t.nbr.resize(na);
-  double sum = 0.0;
   for (int a = 0; a < na; ++a) {
     dpgo_problem_s* q = t.h[a];
     const int nc = q->C.rowptr ? q->C.ncols : 0;
-    const double* Xa = X + (size_t)t.first[a] * T;
-    double* Sa = S + (size_t)t.first[a] * d * d;
     CHK(upload(t.nbr[a], mem[a].nbr_pose, (size_t)nc, q->stream));
+    hm[a].Q = q->Q.dev();
+    hm[a].C = q->C.rowptr ? q->C.dev() : BsrDev{t.no_rows, nullptr, nullptr};
+    hm[a].nbr_pose = t.nbr[a];
+    hm[a].S = S ? S + (size_t)t.first[a] * d * d : nullptr;
+    hm[a].first = t.first[a];
+    hm[a].n = q->n;
+    for (int p0_ = 0; p0_ < q->n; p0_ += P) ht.push_back(CertTile{a, p0_});
+  }
+  t.ntiles = (int)ht.size();
+  CHK(upload(t.members, hm.data(), hm.size(), p0->stream));
+  CHK(upload(t.tiles, ht.data(), ht.size(), p0->stream));
+  HIPC(hipStreamSynchronize(p0->stream));  // (the tables are host vectors of this scope, nbr_pose the caller's)
+  return DPGO_OK;
+}
+
+// the tables, every G_a from the team's X (the member's linear term as an exchange of X would leave it), every member's
+// S, f and |rgrad| (S: the team's Lambda blocks, [N, d, d]); gn2 = sum |rgrad_a|^2 in member order
+int team_setup(const dpgo_team_member* mem, Team& t, const double* X, double* S, double* gn2) {
+  CHK(team_tables(mem, t, S));
+  const int d = t.h[0]->d, T = t.h[0]->T;
+  int cmax = 0;
+  for (dpgo_problem_s* q : t.h) cmax = std::max(cmax, q->C.rowptr ? q->C.ncols : 0);
+  DevBuf<double> nbuf;  // neighbour tiles of one member at a time
+  CHK(nbuf.alloc((size_t)std::max(cmax, 1) * T));
+  double sum = 0.0;
+  for (size_t a = 0; a < t.h.size(); ++a) {
+    dpgo_problem_s* q = t.h[a];
+    const int nc = q->C.rowptr ? q->C.ncols : 0;
     if (q->C.rowptr) {
       if (nc > 0) {
         launch(k_cert_gather_tiles, flat_grid((size_t)nc * T), 0, q->stream, X, t.nbr[a], T, nc, nbuf);
@@ -782,23 +804,44 @@ int team_setup(const dpgo_team_member* mem, Team& t, const double* X, double* S,
       }
       CHK(refresh_G(q, nbuf));
     }
-    CHK(eval_state(q, Xa, Sa));  // (synchronises: nbuf and the host's nbr_pose are free again)
+    CHK(eval_state(q, X + (size_t)t.first[a] * T, S + (size_t)t.first[a] * d * d));  // (synchronises: nbuf is free again)
     sum += q->hstate->ngf * q->hstate->ngf;
-    hm[a].Q = q->Q.dev();
-    hm[a].C = q->C.rowptr ? q->C.dev() : BsrDev{t.no_rows, nullptr, nullptr};
-    hm[a].nbr_pose = t.nbr[a];
-    hm[a].S = Sa;
-    hm[a].first = t.first[a];
-    hm[a].n = q->n;
-    for (int p0_ = 0; p0_ < q->n; p0_ += P) ht.push_back(CertTile{a, p0_});
   }
   *gn2 = sum;
-  t.ntiles = (int)ht.size();
-  CHK(upload(t.members, hm.data(), hm.size(), p0->stream));
-  CHK(upload(t.tiles, ht.data(), ht.size(), p0->stream));
-  HIPC(hipStreamSynchronize(p0->stream));  // (the tables are host vectors of this scope)
   return DPGO_OK;
 }
+
+// f and |rgrad f| of a team's iterate, one launch and the reduce (k_team_eval): what an escape trial and the sweep loop's
+// stopping test need, without the members' G
+struct TeamEval {
+  DevBuf<double> part, red;
+  PinBuf<double> host;
+  int init() {
+    CHK(part.alloc((size_t)kPartialCap * 2));
+    CHK(red.alloc(2));
+    CHK(host.alloc(2));
+    return DPGO_OK;
+  }
+  // rank r of the compiled (d, r) instance is the caller's: the tables hold nothing that depends on it
+  int run(const Team& t, int d, int r, const double* X, double* RG, double* f, double* gn) {
+    dpgo_problem_s* p0 = t.h[0];
+    const int g = team_grid(t);
+    CHK(dispatch_dr(d, r, [&](auto Dc, auto Rc) {
+      constexpr int D = decltype(Dc)::value, R = decltype(Rc)::value;
+      auto go = [&](auto kernel) {
+        return launch(kernel, g, 0, p0->stream, t.members, t.tiles, t.ntiles, X, RG, part);
+      };
+      return RG ? go(k_team_eval<D, R, true>) : go(k_team_eval<D, R, false>);
+    }));
+    launch(k_cert_reduce, 1, 0, p0->stream, part, g, 2, red);
+    HIPC(hipGetLastError());
+    HIPC(hipMemcpyAsync(host, red, sizeof(double) * 2, hipMemcpyDeviceToHost, p0->stream));
+    HIPC(hipStreamSynchronize(p0->stream));
+    *f = 0.5 * host[0];
+    *gn = std::sqrt(host[1]);
+    return DPGO_OK;
+  }
+};
 
 int team_certify_impl(const dpgo_team_member* mem, int n_members, const double* X, const dpgo_certify_params* prm_in,
                       dpgo_team_certify_result* out, double* witness) {
@@ -990,6 +1033,64 @@ int dpgo_certify_escape_device(dpgo_problem_t h_next, int r, const double* X_dev
     }
   }
   if (alpha) *alpha = 0.0;
+  return fail(DPGO_ERR_STATE, "certify: no step along the witness decreases f");
+}
+
+
+int dpgo_team_eval_device(const dpgo_team_member* members, int n_members, const double* X_team_dev, double* f,
+                          double* gradnorm, double* rgrad_team_dev) {
+  if (!X_team_dev || !f || !gradnorm) return fail(DPGO_ERR_INVALID, "null pointer");
+  if (!aligned8(X_team_dev) || !aligned8(rgrad_team_dev)) return fail(DPGO_ERR_INVALID, "team: pointer not 8-byte aligned");
+  Team t;
+  CHK(team_check(members, n_members, t));
+  CHK(team_tables(members, t, nullptr));
+  TeamEval ev;
+  CHK(ev.init());
+  return ev.run(t, t.h[0]->d, t.h[0]->r, X_team_dev, rgrad_team_dev, f, gradnorm);
+}
+
+
+int dpgo_team_escape_device(const dpgo_team_member* members_next, int n_members, int r, const double* X_team_dev,
+                            const double* witness_team_dev, double grad_tol, double* X_next_team_dev,
+                            dpgo_team_escape_result* out) {
+  if (!X_team_dev || !witness_team_dev || !X_next_team_dev || !out) return fail(DPGO_ERR_INVALID, "null pointer");
+  if (!aligned8(X_team_dev) || !aligned8(witness_team_dev) || !aligned8(X_next_team_dev))
+    return fail(DPGO_ERR_INVALID, "team: pointer not 8-byte aligned");
+  if (!(grad_tol >= 0.0)) return fail(DPGO_ERR_INVALID, "certify: bad gradient tolerance");
+  Team t;
+  CHK(team_check(members_next, n_members, t));
+  dpgo_problem_s* p0 = t.h[0];
+  const int d = p0->d;
+  if (!supported(d, r) || !supported(d, r + 1)) return fail(DPGO_ERR_UNSUPPORTED, "certify: (d, r + 1) not compiled in");
+  if (p0->r != r + 1) return fail(DPGO_ERR_INVALID, "certify: the escape handles must have rank r + 1");
+  *out = dpgo_team_escape_result{};
+  CHK(team_tables(members_next, t, nullptr));
+  TeamEval ev;
+  CHK(ev.init());
+  // f0 at alpha = 0: [X; 0] has the cost of X, and the tables hold nothing that depends on the rank
+  double gn0 = 0.0;
+  CHK(ev.run(t, d, r, X_team_dev, nullptr, &out->f_before, &gn0));
+  const int g = std::min(pose_tiles(t.N, d + 1), kMaxGrid);
+  // SE-Sync's rule, as dpgo_certify_escape_device applies it
+  double a = 0.1 * std::sqrt((double)t.N);
+  for (int k = 0; k < 60; ++k, a *= 0.5) {
+    CHK(dispatch_dr(d, r + 1, [&](auto D, auto R1) {  // (by the rank it writes: only compiled lifts are instantiated)
+      if constexpr (R1 > D)
+        return launch(k_cert_lift_retract<D, R1 - 1>, g, 0, p0->stream, X_team_dev, witness_team_dev, a, X_next_team_dev, t.N);
+      return fail(DPGO_ERR_UNSUPPORTED, "certify: no lift to rank d");
+    }));
+    HIPC(hipGetLastError());
+    double f = 0.0, gn = 0.0;
+    CHK(ev.run(t, d, r + 1, X_next_team_dev, nullptr, &f, &gn));
+    out->trials = k + 1;
+    if (f < out->f_before && gn > grad_tol) {
+      out->alpha = a;
+      out->f_after = f;
+      out->gradnorm_after = gn;
+      return DPGO_OK;
+    }
+  }
+  out->alpha = 0.0;
   return fail(DPGO_ERR_STATE, "certify: no step along the witness decreases f");
 }
 

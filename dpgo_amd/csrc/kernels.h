@@ -33,5 +33,6 @@ namespace dpgo {
 #include "kernels/align.h"
 #include "kernels/init.h"
 #include "kernels/certify.h"
+#include "kernels/team.h"
 
 }  // namespace dpgo

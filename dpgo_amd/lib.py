@@ -65,6 +65,11 @@ class TeamCertifyResultC(C.Structure):
     _fields_ = [("cert", CertifyResultC), ("symmetry_defect", C.c_double), ("members", C.c_int), ("poses", C.c_int)]
 
 
+class TeamEscapeResultC(C.Structure):
+    _fields_ = [("alpha", C.c_double), ("trials", C.c_int), ("f_before", C.c_double), ("f_after", C.c_double),
+                ("gradnorm_after", C.c_double)]
+
+
 COST_L2, COST_L1, COST_TLS, COST_HUBER, COST_GM, COST_GNC_TLS = range(6)  # DPGO_COST_*
 COST_TYPES = {"L2": COST_L2, "L1": COST_L1, "TLS": COST_TLS, "Huber": COST_HUBER, "GM": COST_GM, "GNC_TLS": COST_GNC_TLS}
 
@@ -231,6 +236,8 @@ SIGNATURES = {
                                   C.POINTER(TeamCertifyResultC), _P], _I),
     "dpgo_team_certificate_apply_device": ([C.POINTER(TeamMemberC), _I, _P, _P, _P], _I),
     "dpgo_team_certificate_apply_gram_device": ([C.POINTER(TeamMemberC), _I, _P, _P, _P, _P], _I),
+    "dpgo_team_eval_device": ([C.POINTER(TeamMemberC), _I, _P, C.POINTER(_D), C.POINTER(_D), _P], _I),
+    "dpgo_team_escape_device": ([C.POINTER(TeamMemberC), _I, _I, _P, _P, _D, _P, C.POINTER(TeamEscapeResultC)], _I),
 }
 
 _lib: Optional[C.CDLL] = None

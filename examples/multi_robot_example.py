@@ -10,6 +10,10 @@ the frame of robot 0's first pose (the global anchor, :249-254) is written as CS
 updates by PGOAgent::shouldUpdateMeasurementWeights, dpgo_amd.robust.DistributedRobustPGO) and prints the global robust
 cost of every weight update.
 
+--staircase runs the distributed Riemannian staircase instead (dpgo_amd.solveCertifiedDistributedPGO, from rank d: RBCD
+sweeps, the team's certificate, escape to the next rank while the iterate is a saddle); --iterations bounds the sweeps per
+rank; one line per escape, the verdict on the last line.
+
 --local-frames starts distributed: no centralised initialisation, every robot initialises in its own frame (odometry, or
 --local-init chordal) and joins robot 0's frame by robust frame alignment on the device, printing the reference's
 "Robot a attempts initialization from neighbor b: finds i/m inliers." for every attempt.
@@ -48,6 +52,30 @@ def local_frame_agents(args, meas, n, r):
     return agents, graphs, plan
 
 
+def staircase(args, meas, n):
+    """--staircase: the team's Riemannian staircase from rank d; one line per escape, the final verdict last."""
+    import numpy as np
+    import dpgo_amd
+    from dpgo_amd.trajectory import log_trajectory
+    d = meas.d
+    if args.robust_cost or args.local_frames:
+        raise SystemExit("--staircase takes neither --robust-cost nor --local-frames.")
+    print("Running the distributed staircase from rank %d..." % d)
+    res = dpgo_amd.solveCertifiedDistributedPGO(meas, n, args.num_robots, max_sweeps=args.iterations)
+    for e in res.escapes:
+        print("Escape | rank = %d -> %d | lambda_min = %.6g | alpha = %.4g | cost = %.6g -> %.6g | sweeps = %d" % (
+            e["rank"], e["rank"] + 1, e["lambda_min"], e["alpha"], 2 * e["f_before"], 2 * e["f_after"], e["sweeps"]))
+    if args.out_dir:
+        os.makedirs(args.out_dir, exist_ok=True)
+        path = os.path.join(args.out_dir, "team.csv")
+        if log_trajectory(d, n, np.asfortranarray(res.trajectory), path):
+            print("wrote %s" % path)
+    c = res.certificate
+    print("Certificate of the team's iterate: %s | rank = %d | lambda_min = %s | cost = %.6g | rounded cost = %.6g | "
+          "sweeps per rank = %s" % (res.status, res.rank, "%.6g" % c.lambda_min if c is not None else "n/a", 2 * res.f,
+                                    2 * res.f_rounded, res.sweeps))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("num_robots", type=int)
@@ -60,6 +88,9 @@ def main():
                     help="certify the assembled global iterate on one central handle (QuadraticProblem.certify)")
     ap.add_argument("--certify-team", action="store_true",
                     help="certify the team's iterate from the agents' own blocks on the device (RBCDCluster.certify)")
+    ap.add_argument("--staircase", action="store_true",
+                    help="distributed Riemannian staircase from rank d (dpgo_amd.solveCertifiedDistributedPGO): RBCD sweeps, "
+                         "the team's certificate (implies --certify-team), escape to the next rank while it is a saddle")
     ap.add_argument("--robust-cost", choices=["L1", "Huber", "TLS", "GM", "GNC_TLS"], default=None,
                     help="robust agent protocol with this cost: weights re-computed on the device between blocks of iterations")
     ap.add_argument("--weight-updates", type=int, default=10, help="robustOptNumWeightUpdates")
@@ -84,6 +115,8 @@ def main():
     meas, n = dpgo_amd.read_g2o_file(args.g2o)
     print("Loaded dataset from file %s." % args.g2o)
     r, d = args.rank, meas.d
+    if args.staircase:
+        return staircase(args, meas, n)
     if args.local_frames:
         agents, graphs, plan = local_frame_agents(args, meas, n, r)
     else:

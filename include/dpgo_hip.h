@@ -852,7 +852,7 @@ int dpgo_certify_escape_device(dpgo_problem_t h_next, int r, const double* X_dev
  * edge hold the same weight and activity for it; beyond 8 (d+1) N 2^-53 the call returns DPGO_ERR_STATE.
  * DPGO_ERR_INVALID: a member with priors (a non-zero constant term of G), members on different devices or streams or of
  * different (d, r), a table that does not tile [0, N), an nbr_pose entry out of range; DPGO_ERR_HIP without a device.
- * Out of scope: several ranks, priors, the staircase escape. */
+ * Out of scope: several ranks, priors.  The staircase escape of a team: dpgo_team_escape_device below. */
 typedef struct dpgo_team_member {
   dpgo_problem_t h;
   int first;
@@ -874,6 +874,34 @@ int dpgo_team_certificate_apply_device(const dpgo_team_member* members, int n_me
 /* the same, and the r x r block V (CV)^T the kernel sums on the way (host, row-major; may be NULL); for tests */
 int dpgo_team_certificate_apply_gram_device(const dpgo_team_member* members, int n_members, const double* X_team_dev,
                                             const double* V_team_dev, double* CV_team_dev, double* vcv_host);
+
+/* ---- the staircase step of a team ("Team staircase") ----
+ * f(X) = 0.5 <X Q, X> and |rgrad f(X)| of the team's iterate from the same member table, in one launch and a fixed-order
+ * reduce: rows of member a of X Q are X_a Q_aa + sum_b X_b Q_ba with the coupling blocks read from the other members'
+ * slices of X_team through nbr_pose.  The members' G, S and neighbour buffers are neither read nor written.  f and gradnorm
+ * are host scalars; rgrad_team_dev (may be NULL) receives the Riemannian gradient tiles [N, d+1, r] in team order.  Two
+ * calls give the same bits.  Errors as dpgo_team_certify_device's member table checks. */
+int dpgo_team_eval_device(const dpgo_team_member* members, int n_members, const double* X_team_dev, double* f,
+                          double* gradnorm, double* rgrad_team_dev);
+typedef struct dpgo_team_escape_result {
+  double alpha;          /* the accepted step; 0 when no trial qualifies */
+  int trials;            /* trial steps evaluated */
+  double f_before;       /* f(X) = f([X; 0]) */
+  double f_after;        /* f(X_next) */
+  double gradnorm_after; /* |rgrad f(X_next)| at rank r + 1 */
+} dpgo_team_escape_result;
+/* Riemannian-staircase escape of a team: X_next = retract([X; alpha w^T]) for the first alpha of alpha0, alpha0 / 2, ...
+ * (alpha0 = 0.1 sqrt(N), at most 60 trials) with f(X_next) < f(X) and |rgrad f(X_next)| > grad_tol -- the rule of
+ * dpgo_certify_escape_device.  members_next: the same agents' handles at rank r + 1 (same slices, same nbr_pose);
+ * X_team_dev [N, d+1, r], witness_team_dev (d+1)N doubles in team order (dpgo_team_certify_device), X_next_team_dev
+ * [N, d+1, r+1].  The member tables are built once; every trial is one lift-and-retract launch and one evaluation.
+ * DPGO_ERR_INVALID: null or misaligned pointers, grad_tol < 0, a member table dpgo_team_certify_device refuses (priors,
+ * slices that do not tile [0, N), ...), members whose rank is not r + 1; DPGO_ERR_UNSUPPORTED: (d, r + 1) is not compiled;
+ * DPGO_ERR_STATE: a member has a solve in flight, or no trial qualifies (alpha = 0, X_next unspecified).  Every refusal
+ * but the last is decided on the host before any launch. */
+int dpgo_team_escape_device(const dpgo_team_member* members_next, int n_members, int r, const double* X_team_dev,
+                            const double* witness_team_dev, double grad_tol, double* X_next_team_dev,
+                            dpgo_team_escape_result* out);
 
 #ifdef __cplusplus
 }

@@ -1302,12 +1302,11 @@ inline Matrix solveRobustPGO(std::vector<RelativeSEMeasurement>& mutable_measure
 // in team order, all on one device and stream, each with its coupling set (setCouplingFromPoseGraph); firsts[a] = first tile
 // of agent a in the team vector, nbr_pose[a][k] = team tile of column slot k of its coupling; X_team_dev: the team's
 // iterate on the device ((d+1) r doubles per tile); witness_team_dev: (d+1)N doubles on the device, or null.
-inline dpgo_team_certify_result certifyTeam(const std::vector<QuadraticProblem*>& problems, const std::vector<int>& firsts,
-                                            const std::vector<std::vector<int32_t>>& nbr_pose, const double* X_team_dev,
-                                            const dpgo_certify_params* params = nullptr,
-                                            double* witness_team_dev = nullptr) {
+inline std::vector<dpgo_team_member> teamMembers(const char* who, const std::vector<QuadraticProblem*>& problems,
+                                                 const std::vector<int>& firsts,
+                                                 const std::vector<std::vector<int32_t>>& nbr_pose) {
   if (firsts.size() != problems.size() || nbr_pose.size() != problems.size())
-    throw std::invalid_argument("certifyTeam: one first tile and one nbr_pose list per problem");
+    throw std::invalid_argument(std::string(who) + ": one first tile and one nbr_pose list per problem");
   std::vector<dpgo_team_member> mem(problems.size());
   for (size_t a = 0; a < problems.size(); ++a) {
     problems[a]->refresh();
@@ -1315,9 +1314,42 @@ inline dpgo_team_certify_result certifyTeam(const std::vector<QuadraticProblem*>
     mem[a].first = firsts[a];
     mem[a].nbr_pose = nbr_pose[a].empty() ? nullptr : nbr_pose[a].data();
   }
+  return mem;
+}
+inline dpgo_team_certify_result certifyTeam(const std::vector<QuadraticProblem*>& problems, const std::vector<int>& firsts,
+                                            const std::vector<std::vector<int32_t>>& nbr_pose, const double* X_team_dev,
+                                            const dpgo_certify_params* params = nullptr,
+                                            double* witness_team_dev = nullptr) {
+  const std::vector<dpgo_team_member> mem = teamMembers("certifyTeam", problems, firsts, nbr_pose);
   dpgo_team_certify_result res{};
   check(dpgo_team_certify_device(mem.data(), (int)mem.size(), X_team_dev, params, &res, witness_team_dev));
   return res;
+}
+
+// f and |rgrad f| of the team's iterate in one launch (dpgo_team_eval_device): the same member table; rgrad_team_dev: the
+// gradient tiles in team order on the device, or null.  The agents' G and neighbour buffers are not touched.
+struct TeamEval {
+  double f, gradnorm;
+};
+inline TeamEval evalTeam(const std::vector<QuadraticProblem*>& problems, const std::vector<int>& firsts,
+                         const std::vector<std::vector<int32_t>>& nbr_pose, const double* X_team_dev,
+                         double* rgrad_team_dev = nullptr) {
+  const std::vector<dpgo_team_member> mem = teamMembers("evalTeam", problems, firsts, nbr_pose);
+  TeamEval out{};
+  check(dpgo_team_eval_device(mem.data(), (int)mem.size(), X_team_dev, &out.f, &out.gradnorm, rgrad_team_dev));
+  return out;
+}
+
+// The team's staircase step (dpgo_team_escape_device): problems_next are the same agents' problems at rank r + 1;
+// X_next_team_dev receives the lifted, retracted iterate ((d+1)(r+1) doubles per tile).
+inline dpgo_team_escape_result escapeTeam(const std::vector<QuadraticProblem*>& problems_next, const std::vector<int>& firsts,
+                                          const std::vector<std::vector<int32_t>>& nbr_pose, int r, const double* X_team_dev,
+                                          const double* witness_team_dev, double grad_tol, double* X_next_team_dev) {
+  const std::vector<dpgo_team_member> mem = teamMembers("escapeTeam", problems_next, firsts, nbr_pose);
+  dpgo_team_escape_result out{};
+  check(dpgo_team_escape_device(mem.data(), (int)mem.size(), r, X_team_dev, witness_team_dev, grad_tol, X_next_team_dev,
+                                &out));
+  return out;
 }
 
 }  // namespace dpgo_hip
