@@ -1,6 +1,16 @@
 // bench_probes.hip -- kernel timing probes behind bench.py (HIP events on the stream of the solver; rotating operand sets for HBM-only rates).
 #include "host.h"
 
+namespace {
+// The tCG-step probes launch k_tcg_hess without an update kernel in front of it: the kernel sums whatever region B holds
+// (the pushed state never evaluates the test).  On a handle no launch has written B yet that is the zeros of its creation,
+// as many entries as the update kernel would have left.
+int probe_reads_B(dpgo_problem_s* p) {
+  double* zeros = nullptr;
+  return p->pB.is_written() ? DPGO_OK : sums_out(p->pB, p->grid(), &zeros);
+}
+}  // namespace
+
 extern "C" {
 
 
@@ -34,6 +44,7 @@ int dpgo_bench_hess_rotating(dpgo_problem_t p, int nsets, int reps, int warmup, 
   p->hstate->max_inner = 1 << 30;
   p->hstate->min_inner = 1 << 30;  // the convergence test is never evaluated, whatever the partial sums hold
   CHK(push_state(p));
+  CHK(probe_reads_B(p));
   // every operand of the tCG-step kernel gets nsets private copies; per launch a set's buffers are exchanged with the
   // handle's own and exchanged back before the launch helper's result is looked at: the handle never keeps a copy, a set
   // never keeps the handle's buffer, whichever way this function is left
@@ -97,7 +108,7 @@ int dpgo_bench_hess_rotating(dpgo_problem_t p, int nsets, int reps, int warmup, 
   int rc = ok ? DPGO_OK : fail(DPGO_ERR_HIP, "hipMalloc failed for the rotating buffer sets");
   auto launch = [&](int i) -> int {
     exchange(sets[i % nsets]);
-    const int r2 = launch_tcg_hess_with(p, p->dstate, p->dstate + 1, 0, nullptr, 0u);
+    const int r2 = launch_tcg_hess_with(p, p->state.slot(0), p->state.slot(1), 0, nullptr, 0u);
     exchange(sets[i % nsets]);
     return r2;
   };
@@ -242,8 +253,9 @@ int dpgo_bench_hess(dpgo_problem_t p, int reps, int warmup, double* avg_ms) {
   p->hstate->max_inner = 1 << 30;
   p->hstate->min_inner = 1 << 30;  // the convergence test is never evaluated, whatever the partial sums hold
   CHK(push_state(p));
+  CHK(probe_reads_B(p));
   auto launch = [&]() -> int {
-    return launch_tcg_hess_with(p, p->dstate, p->dstate + 1, 0, nullptr, 0u);
+    return launch_tcg_hess_with(p, p->state.slot(0), p->state.slot(1), 0, nullptr, 0u);
   };
   hipEvent_t e0, e1;
   HIPC(hipEventCreate(&e0));
@@ -317,9 +329,11 @@ int dpgo_bench_iteration_kernels(dpgo_problem_t p, int reps, int warmup, double 
   p->hstate->Delta = 1e300;
   CHK(push_state(p));
   CHK(build_dinv(p, p->ml_ready ? p->ml_shift : 1e-1));
-  {  // <delta, H delta> partials of a "previous k_tcg_hess": positive, so that the update kernel takes its regular path
+  {  // <delta, H delta> partials of a "previous k_tcg_hess" on its grid: positive, so that the update kernel takes its regular path
     std::vector<double> ones((size_t)kPartialCap * kNP, 1.0);
-    HIPC(hipMemcpyAsync(p->pA(), ones.data(), sizeof(double) * ones.size(), hipMemcpyHostToDevice, p->stream));
+    double* pa = nullptr;
+    CHK(sums_out(p->pA, p->grid_s(), &pa));
+    HIPC(hipMemcpyAsync(pa, ones.data(), sizeof(double) * ones.size(), hipMemcpyHostToDevice, p->stream));
     HIPC(hipStreamSynchronize(p->stream));
   }
   hipEvent_t e0, e1;
@@ -337,15 +351,12 @@ int dpgo_bench_iteration_kernels(dpgo_problem_t p, int reps, int warmup, double 
     return DPGO_OK;
   };
   const bool ml = p->ml_ready;
+  const StateSlots<DevState>::Hold pushed(p->state);  // every launch below keeps reading the pushed state
   int rc = timed([&]() -> int {
-    const int cur = p->cur;
-    int r2 = launch_tcg_update(p, p->dinv, 0, ml ? p->ml[0].x1 : nullptr, ml ? p->ml_omega : 0.0);
-    p->cur = cur;  // keep reading the pushed state
-    return r2;
+    return launch_tcg_update(p, p->dinv, 0, ml ? p->ml[0].x1 : nullptr, ml ? p->ml_omega : 0.0);
   }, &out_ms[0]);
   if (rc == DPGO_OK && ml) {
     const int nl = (int)p->ml.size();
-    auto& L0 = p->ml[0];
     const bool ap = p->ml_use_ap();
     rc = timed([&]() -> int { return launch_ml_restrict0(p, p->rr, nullptr, p->grid_restrict()); }, &out_ms[1]);
     if (rc == DPGO_OK) rc = timed([&]() -> int {
@@ -354,22 +365,9 @@ int dpgo_bench_iteration_kernels(dpgo_problem_t p, int reps, int warmup, double 
       if (p->ml_use_dense_sym()) return launch_dense_sym(p, Cc, nullptr);
       return launch_coarse_prolong(p, L, Cc, nullptr, ap ? Cc.x : nullptr);
     }, &out_ms[2]);
-    if (rc == DPGO_OK) rc = timed([&]() -> int {
-      if (ap) {
-        return launch_ml_post_ap(p, p->x1, p->rr, p->z, p->pB(), nullptr);
-      }
-      CHK(dispatch_drs(p->d, p->r, p->split, [&](auto D, auto R, auto SPLIT) {
-        auto go = [&](auto kernel, const auto& Q) {
-          return launch(kernel, p->grid_post(), 0, p->stream, Q, p->x1, L0.x, p->rr, p->dinv, p->ml_omega, p->ml_shift, p->z,
-                        p->pB(), nullptr, p->n);
-        };
-        return p->tcg_sym ? go(k_ml_post<D, R, 1, BsrSymDev>, p->sym.dev()) : go(k_ml_post<D, R, SPLIT>, p->Q.dev());
-      }));
-      HIPC(hipGetLastError());
-      return DPGO_OK;
-    }, &out_ms[3]);
+    if (rc == DPGO_OK) rc = timed([&]() -> int { return launch_ml_post0(p, p->x1, p->rr, p->z, &p->pB, nullptr); }, &out_ms[3]);
     if (rc == DPGO_OK)
-      rc = timed([&]() -> int { return launch_ml_tail(p, p->x1, p->rr, p->z, p->pB(), nullptr); }, &out_ms[4]);
+      rc = timed([&]() -> int { return launch_ml_tail(p, p->x1, p->rr, p->z, &p->pB, nullptr); }, &out_ms[4]);
   }
   (void)hipEventDestroy(e0);
   (void)hipEventDestroy(e1);

@@ -10,8 +10,10 @@
 //   align.hip       frame alignment of agents that start in their own frames: candidates, robust average, lift
 //   bench_probes.hip  kernel timing probes used by bench.py
 //   certify.hip     certificate of global optimality (LOBPCG on C(X) = Q - Lambda(X)) and the staircase escape
+// handoff.h (host compiler only, no HIP): the partial-sum regions and the state slots one launch leaves for the next.
 #pragma once
 #include "kernels.h"
+#include "handoff.h"
 
 #include <algorithm>
 #include <atomic>
@@ -133,7 +135,7 @@ inline bool aligned16(const void* q) { return ((uintptr_t)q & 15) == 0; }
 // ---- the library's own device and pinned memory ----
 // Every buffer the library keeps is a DevBuf (hipMalloc) or a PinBuf (hipHostMalloc): move-only, released by the destructor,
 // so a struct that gains a buffer needs no second edit anywhere and an early return leaks nothing.  Assigning an empty value
-// releases (`S = SymQ()`); the conversion to T* lets code that only reads the pointer -- launch arguments, `p->dstate + 1`,
+// releases (`S = SymQ()`); the conversion to T* lets code that only reads the pointer -- launch arguments, `p->dirs + slot`,
 // `if (!p->Q.vals)` -- look as it did with raw pointers.  These two types are the only callers of hipMalloc / hipFree /
 // hipHostMalloc / hipHostFree (dpgo_device_malloc / dpgo_device_free hand memory to the caller and are not counted).
 // g_live_*: what all of them hold at the moment (dpgo_debug_live_allocations).
@@ -313,6 +315,17 @@ struct BorrowedIterate {
   int begin(dpgo_problem_s* p, double* X_dev);
   int end(dpgo_problem_s* p, int rc);  // rc: what the solve returned; copies out after a successful solve only
 };
+
+// The handle's partial-sum regions (handoff.h; DESIGN.md section 4 says who writes and who reads each).  sums_out: for the
+// launch that writes R on `grid` workgroups; sums_ready: in front of a launch whose kernel sums R.
+using Partials = PartialRegion<kPartialCap>;
+inline int sums_out(Partials& R, int grid, double** ptr) {
+  *ptr = R.out(grid);
+  return *ptr ? DPGO_OK : fail(DPGO_ERR_STATE, "partial sums: the writing launch's grid is outside 1 .. kPartialCap");
+}
+inline int sums_ready(const Partials& R) {
+  return R.is_written() ? DPGO_OK : fail(DPGO_ERR_STATE, "partial sums: read before any launch of this handle wrote them");
+}
 
 }  // namespace dpgo_host
 using namespace dpgo_host;
@@ -526,8 +539,10 @@ struct dpgo_problem_s {
   DevBuf<unsigned long long> pgran;  // granule table of the in-kernel all-reduce (kGranWords 8-byte words)
   unsigned gran_cleared_at = 0;         // value of `gen` when the table was last cleared
   PinBuf<PersistCtrl> hctrl;
-  DevBuf<double> partials;  // 5 regions of kPartialCap*kNP
-  DevBuf<DevState> dstate;  // 2 slots
+  DevBuf<double> partial_mem;  // the four regions below, kPartialCap * kNP doubles each
+  Partials pE, pA, pB, pH;
+  DevBuf<DevState> state_mem;  // the two slots of `state`
+  StateSlots<DevState> state;
   PinBuf<DevState> hstate;
   PinBuf<unsigned long long> hflag;  // host-coherent: host-coherent: device-published tCG progress word
   unsigned gen = 0;
@@ -551,21 +566,12 @@ struct dpgo_problem_s {
       return EdgeDev{e_p1, e_p2, e_R, e_t, e_kappa, e_tau, e_fixed, e_role, e_slot, e_w, e_rsq, em};
     }
   } gnc;
-  int cur = 0;
   size_t vec_bytes() const { return (size_t)n * T * sizeof(double); }
-  double* pE() const { return partials; }
-  double* pA() const { return partials + 1 * kPartialCap * kNP; }
-  double* pB() const { return partials + 2 * kPartialCap * kNP; }
-  double* pH() const { return partials + 3 * kPartialCap * kNP; }
   int grid() const { return std::min(pose_tiles(n, b), cap_u); }
   int cap_u = kMaxGrid, cap_h = kMaxGrid;  // launch caps of the streaming / SpMM kernel families
   // k_tcg_update_span's multilevel-mode instance (no iterate, no projection: 143 VGPRs = 3 waves per SIMD) has its own cap
   int cap_u_ml = kMaxGrid;
   int grid_u(bool ml_mode) const { return std::min(pose_tiles(n, b), ml_mode ? cap_u_ml : cap_u); }
-  // entries of partial region B (<r,r>, <z,r>) that k_tcg_hess has to sum: written by k_tcg_update (its grid) or,
-  // with the fused multilevel cycle, by k_ml_post (SpMM-family grid)
-  bool zr_from_post = false;
-  int nb_zr() const { return zr_from_post ? grid_post() : grid(); }
   int split = 1;  // lane groups per pose in the SpMM kernels (latency layout for small blocks)
   // SpMM kernels (k_spmm, k_grad, k_hess, k_tcg_hess)
   int grid_s() const { return std::min(pose_tiles(n, b, split), tcg_sym ? cap_hs : cap_h); }
@@ -575,10 +581,8 @@ struct dpgo_problem_s {
   int grid_restrict() const { return std::min(pose_tiles(n, b, split), cap_restrict); }
   int grid_post() const { return std::min(pose_tiles(n, b, split), cap_post); }
   // the outer iteration's kernels on the symmetric storage (k_grad, k_hess: 110-114 VGPRs = 4 waves per SIMD) have their own
-  // cap -- grid_s() is sized for the tCG-step kernel's 2 waves per SIMD -- and whoever sums their partials is told the
-  // grid of the launch that wrote them
+  // cap -- grid_s() is sized for the tCG-step kernel's 2 waves per SIMD
   int cap_outer_sym = kMaxGrid;
-  int nb_grad = 0, nb_hess = 0;
   int grid_outer_sym() const { return std::min(pose_tiles(n, b), cap_outer_sym); }
   int cap_spmm_sym = kMaxGrid;  // launch cap of k_spmm_sym (resident count of the compiled kernel)
   int grid_spmm_sym() const { return std::min(pose_tiles(n, b), cap_spmm_sym); }
@@ -737,7 +741,7 @@ bool outer_sym_enabled();
 int launch_grad(dpgo_problem_s* p, const double* X, double* RG, double* S, double* EG,
                 const DevState* st = nullptr, bool sym = false);
 int launch_hess(dpgo_problem_s* p, const double* X, const double* S, const double* V, const double* Gdot,
-                double* HV, double* partials, const DevState* st, int check_tcg, bool sym = false);
+                double* HV, const DevState* st, int check_tcg, bool sym = false);
 int launch_retract(dpgo_problem_s* p, const double* X, const double* eta, double scale, double* X2,
                    const DevState* st, const double* rho_r = nullptr, const double* rho_g = nullptr, bool from_dirs = false);
 int launch_rtr_update(dpgo_problem_s* p);
@@ -780,8 +784,8 @@ int launch_coarse_prolong(dpgo_problem_s* p, const dpgo_problem_s::MlLevel& L, c
                           const DevState* gate, double* xc_out = nullptr);
 int launch_dense_sym(dpgo_problem_s* p, const dpgo_problem_s::MlLevel& C, const DevState* gate);
 int launch_ml_restrict0(dpgo_problem_s* p, const double* r, const DevState* gate, int g0, bool stop_check = false);
-int launch_ml_post_ap(dpgo_problem_s* p, const double* Xdev, const double* r, double* z, double* pout, const DevState* gate);
-int launch_ml_tail(dpgo_problem_s* p, const double* Xdev, const double* r, double* z, double* pout,
+int launch_ml_post0(dpgo_problem_s* p, const double* Xdev, const double* r, double* z, Partials* sums, const DevState* gate);
+int launch_ml_tail(dpgo_problem_s* p, const double* Xdev, const double* r, double* z, Partials* sums,
                    const DevState* gate, bool stop_check = false);
 int launch_ml_apply(dpgo_problem_s* p, const double* Xdev, const double* v, double* z);
 

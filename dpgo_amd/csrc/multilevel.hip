@@ -1017,12 +1017,13 @@ int launch_ml_restrict0(dpgo_problem_s* p, const double* r, const DevState* gate
   auto& L = p->ml[0];
   auto& C = p->ml[1];
   // inside the tCG loop (not after its first update): tCG's residual test one kernel early (TcgStopCheck, multilevel.h);
-  // the <r,r> partial sums are the ones k_tcg_update wrote, one per workgroup of ITS grid
+  // the <r,r> partial sums are the ones k_tcg_update has just left in region B, one per workgroup of ITS grid
   TcgStopCheck stop;
   if (stop_check && gate) {
+    CHK(sums_ready(p->pB));
     stop.state = const_cast<DevState*>(gate);
-    stop.pin = p->pB();
-    stop.nb = p->grid_u(true);  // (k_tcg_update_span's multilevel-mode instance wrote them)
+    stop.pin = p->pB.in();
+    stop.nb = p->pB.count();
     stop.hflag = p->hflag;
     stop.gen = p->gen;
   }
@@ -1056,22 +1057,35 @@ int dispatch_post_ap(const dpgo_problem_s* p, F&& f) {
   return dispatch_split(p->split, [&](auto Sc) { return f(k_ml_post_ap<D, R, decltype(Sc)::value>, L0.AP.dev(), L0.res1, L0.Pb); });
 }
 
-// Level-0 post-smoothing of a two-level hierarchy through A P (k_ml_post_ap).
-int launch_ml_post_ap(dpgo_problem_s* p, const double* Xdev, const double* r, double* z, double* pout, const DevState* gate) {
-  CHK(dispatch_dr(p->d, p->r, [&](auto Dc, auto Rc) {
-    constexpr int D = decltype(Dc)::value, R = decltype(Rc)::value;
-    return dispatch_post_ap<D, R>(p, [&](auto kernel, const auto& AP, const auto& res1, const auto& Pb) {
-      return launch(kernel, p->grid_post(), 0, p->stream, AP, Xdev, r, res1, p->ml[1].x, Pb, p->ml[0].agg(), p->dinv,
-                    p->ml_omega, z, pout, gate, p->n);
-    });
-  }));
+// Level-0 post-smoothing, the cycle's last launch: z = proj_X(M^-1 r), partial sums <r,r>, <z,r> into `sums` (may be NULL:
+// none).  A two-level hierarchy goes through A P and the coarse solution (k_ml_post_ap), any other through Q (k_ml_post).
+int launch_ml_post0(dpgo_problem_s* p, const double* Xdev, const double* r, double* z, Partials* sums, const DevState* gate) {
+  const int g0 = p->grid_post();
+  double* pout = nullptr;
+  if (sums) CHK(sums_out(*sums, g0, &pout));
+  if (p->ml_use_ap()) {
+    CHK(dispatch_dr(p->d, p->r, [&](auto Dc, auto Rc) {
+      constexpr int D = decltype(Dc)::value, R = decltype(Rc)::value;
+      return dispatch_post_ap<D, R>(p, [&](auto kernel, const auto& AP, const auto& res1, const auto& Pb) {
+        return launch(kernel, g0, 0, p->stream, AP, Xdev, r, res1, p->ml[1].x, Pb, p->ml[0].agg(), p->dinv, p->ml_omega, z,
+                      pout, gate, p->n);
+      });
+    }));
+  } else {
+    CHK(dispatch_drs(p->d, p->r, p->ml[0].split, [&](auto D, auto R, auto SPLIT) {
+      auto go = [&](auto kernel, const auto& Q) {  // level 0 reads Q: the symmetric copy when the tCG-step kernel does
+        return launch(kernel, g0, 0, p->stream, Q, Xdev, p->ml[0].x, r, p->dinv, p->ml_omega, p->ml_shift, z, pout, gate, p->n);
+      };
+      return p->tcg_sym ? go(k_ml_post<D, R, 1, BsrSymDev>, p->sym.dev()) : go(k_ml_post<D, R, SPLIT>, p->Q.dev());
+    }));
+  }
   HIPC(hipGetLastError());
   return DPGO_OK;
 }
 
 // The launches of one cycle after the pre-smoothing step of level 0 (x1 = w Dinv r is in ml[0].x1):
-// z = proj_X(M^-1 r); partial sums <r,r>, <z,r> into `pout` (may be NULL).  `gate`: state record for early exit.
-int launch_ml_tail(dpgo_problem_s* p, const double* Xdev, const double* r, double* z, double* pout,
+// z = proj_X(M^-1 r); partial sums <r,r>, <z,r> into `sums` (may be NULL).  `gate`: state record for early exit.
+int launch_ml_tail(dpgo_problem_s* p, const double* Xdev, const double* r, double* z, Partials* sums,
                    const DevState* gate, bool stop_check) {
   const int nl = (int)p->ml.size();
   // the dense level reads its right-hand side in the precision its inverse is stored in (same buffer)
@@ -1080,12 +1094,11 @@ int launch_ml_tail(dpgo_problem_s* p, const double* Xdev, const double* r, doubl
   };
   auto A_of = [&](int l) { return l == 0 ? p->Q.dev() : p->ml[l].A.dev(); };
   auto r_of = [&](int l) { return l == 0 ? r : (const double*)p->ml[l].r; };
-  int g0 = p->grid_restrict();  // grid of the level-0 launches: restriction first, post-smoothing later
-  auto grid_of = [&](const dpgo_problem_s::MlLevel& L) {
-    return &L == &p->ml[0] ? g0 : std::min(kMaxGrid, pose_tiles(L.n, p->b, L.split));
+  auto grid_of = [&](const dpgo_problem_s::MlLevel& L) {  // (of a level below 0)
+    return std::min(kMaxGrid, pose_tiles(L.n, p->b, L.split));
   };
   const bool ap = p->ml_use_ap();  // two levels: the residual after pre-smoothing is kept, the dense level hands over xc
-  CHK(launch_ml_restrict0(p, r, gate, g0, stop_check));
+  CHK(launch_ml_restrict0(p, r, gate, p->grid_restrict(), stop_check));
   for (int l = 1; l + 1 < nl; ++l) {  // down
     auto& L = p->ml[l];
     auto& C = p->ml[l + 1];
@@ -1102,9 +1115,7 @@ int launch_ml_tail(dpgo_problem_s* p, const double* Xdev, const double* r, doubl
     else
       CHK(launch_coarse_prolong(p, L, C, gate, ap ? C.x : nullptr));
   }
-  g0 = p->grid_post();
-  if (ap) return launch_ml_post_ap(p, Xdev, r, z, pout, gate);
-  for (int l = nl - 2; l >= 1; --l) {  // up
+  for (int l = nl - 2; l >= 1; --l) {  // up (two levels: nothing between the dense level and level 0)
     auto& L = p->ml[l];
     auto& F = p->ml[l - 1];
     CHK(dispatch_drs(p->d, p->r, L.split, [&](auto D, auto R, auto SPLIT) {
@@ -1112,14 +1123,7 @@ int launch_ml_tail(dpgo_problem_s* p, const double* Xdev, const double* r, doubl
                     F.k, F.x, F.n, gate, L.n);
     }));
   }
-  CHK(dispatch_drs(p->d, p->r, p->ml[0].split, [&](auto D, auto R, auto SPLIT) {
-    auto go = [&](auto kernel, const auto& Q) {  // level 0 reads Q: the symmetric copy when the tCG-step kernel does
-      return launch(kernel, g0, 0, p->stream, Q, Xdev, p->ml[0].x, r, p->dinv, p->ml_omega, p->ml_shift, z, pout, gate, p->n);
-    };
-    return p->tcg_sym ? go(k_ml_post<D, R, 1, BsrSymDev>, p->sym.dev()) : go(k_ml_post<D, R, SPLIT>, p->Q.dev());
-  }));
-  HIPC(hipGetLastError());
-  return DPGO_OK;
+  return launch_ml_post0(p, Xdev, r, z, sums, gate);
 }
 
 // Stand-alone application z = proj_X(M^-1 v) (QuadraticProblem::PreConditioner outside the tCG loop).

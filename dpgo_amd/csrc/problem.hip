@@ -58,14 +58,14 @@ int build_dinv(dpgo_problem_s* p, double shift) {
 }
 
 int poll_state(dpgo_problem_s* p) {
-  HIPC(hipMemcpyAsync(p->hstate, p->dstate + p->cur, sizeof(DevState), hipMemcpyDeviceToHost, p->stream));
+  HIPC(hipMemcpyAsync(p->hstate, p->state.in(), sizeof(DevState), hipMemcpyDeviceToHost, p->stream));
   HIPC(hipStreamSynchronize(p->stream));
   return DPGO_OK;
 }
 
 int push_state(dpgo_problem_s* p) {
-  HIPC(hipMemcpyAsync(p->dstate + 0, p->hstate, sizeof(DevState), hipMemcpyHostToDevice, p->stream));
-  HIPC(hipMemcpyAsync(p->dstate + 1, p->hstate, sizeof(DevState), hipMemcpyHostToDevice, p->stream));
+  HIPC(hipMemcpyAsync(p->state.slot(0), p->hstate, sizeof(DevState), hipMemcpyHostToDevice, p->stream));
+  HIPC(hipMemcpyAsync(p->state.slot(1), p->hstate, sizeof(DevState), hipMemcpyHostToDevice, p->stream));
   HIPC(hipStreamSynchronize(p->stream));
   return DPGO_OK;
 }
@@ -249,24 +249,26 @@ int launch_grad(dpgo_problem_s* p, const double* X, double* RG, double* S, doubl
                 const DevState* st, bool sym) {
   const double* Gm = p->has_G ? p->G : nullptr;
   sym = sym && p->split == 1;
-  p->nb_grad = sym ? p->grid_outer_sym() : p->grid_s();
+  const int g = sym ? p->grid_outer_sym() : p->grid_s();
+  double* pe = nullptr;
+  CHK(sums_out(p->pE, g, &pe));
   CHK(dispatch_drs(p->d, p->r, p->split, [&](auto D, auto R, auto SPLIT) {
-    if (sym) return launch(k_grad<D, R, 1, BsrSymDev>, p->nb_grad, 0, p->stream, p->sym.dev(), X, Gm, RG, S, EG, p->pE(), st, p->n);
-    return launch(k_grad<D, R, SPLIT>, p->nb_grad, 0, p->stream, p->Q.dev(), X, Gm, RG, S, EG, p->pE(), st, p->n);
+    if (sym) return launch(k_grad<D, R, 1, BsrSymDev>, g, 0, p->stream, p->sym.dev(), X, Gm, RG, S, EG, pe, st, p->n);
+    return launch(k_grad<D, R, SPLIT>, g, 0, p->stream, p->Q.dev(), X, Gm, RG, S, EG, pe, st, p->n);
   }));
   HIPC(hipGetLastError());
   return DPGO_OK;
 }
 
 int launch_hess(dpgo_problem_s* p, const double* X, const double* S, const double* V, const double* Gdot,
-                double* HV, double* partials, const DevState* st, int check_tcg, bool sym) {
+                double* HV, const DevState* st, int check_tcg, bool sym) {
   sym = sym && p->split == 1;
-  p->nb_hess = sym ? p->grid_outer_sym() : p->grid_s();
+  const int g = sym ? p->grid_outer_sym() : p->grid_s();
+  double* ph = nullptr;
+  CHK(sums_out(p->pH, g, &ph));
   CHK(dispatch_drs(p->d, p->r, p->split, [&](auto D, auto R, auto SPLIT) {
-    if (sym)
-      return launch(k_hess<D, R, 1, BsrSymDev>, p->nb_hess, 0, p->stream, p->sym.dev(), X, S, V, Gdot, HV, partials, st,
-                    check_tcg, p->n);
-    return launch(k_hess<D, R, SPLIT>, p->nb_hess, 0, p->stream, p->Q.dev(), X, S, V, Gdot, HV, partials, st, check_tcg, p->n);
+    if (sym) return launch(k_hess<D, R, 1, BsrSymDev>, g, 0, p->stream, p->sym.dev(), X, S, V, Gdot, HV, ph, st, check_tcg, p->n);
+    return launch(k_hess<D, R, SPLIT>, g, 0, p->stream, p->Q.dev(), X, S, V, Gdot, HV, ph, st, check_tcg, p->n);
   }));
   HIPC(hipGetLastError());
   return DPGO_OK;
@@ -279,21 +281,21 @@ int launch_retract(dpgo_problem_s* p, const double* X, const double* eta, double
   // applies H to it; nothing else reads tCG's iterate after the step
   // (50 VGPRs, 64 with the rho test's sums: not bound to the update kernel's grid -- at most DPGO_GRID_RETRACT workgroups, 1 024 by default; 512 / 1 024 / 1 563 measured 259.4 / 261.4 / 260.0 it/s)
   int gr = std::min(pose_tiles(p->n, p->b), options().grid_retract > 0 ? options().grid_retract : kMaxGrid);
-  // rho_r, rho_g (the RTR step: tCG's residual and the gradient it started from): the rho test's two sums go to pH(), one
-  // entry per workgroup, and launch_rtr_update is told the grid as after launch_hess
+  // rho_r, rho_g (the RTR step: tCG's residual and the gradient it started from): the rho test's two sums go to region H,
+  // one entry per workgroup, as launch_hess leaves them
   const bool rho = rho_r && rho_g;
-  if (rho) {
-    if (scale != 1.0) return fail(DPGO_ERR_STATE, "the rho-test sums of k_retract belong to the full step (scale 1)");
-    gr = std::min(gr, kPartialCap);
-    p->nb_hess = gr;
-  }
+  if (rho && scale != 1.0) return fail(DPGO_ERR_STATE, "the rho-test sums of k_retract belong to the full step (scale 1)");
   if (from_dirs && (!p->dirs || !p->dirs_coef || scale != 1.0))
     return fail(DPGO_ERR_STATE, "the retraction from kept directions is the RTR step of a solve that kept them");
+  double* ph = nullptr;
+  if (rho) {
+    gr = std::min(gr, kPartialCap);
+    CHK(sums_out(p->pH, gr, &ph));
+  }
   CHK(dispatch_dr(p->d, p->r, [&](auto D, auto R) {
     auto go = [&](auto kernel) {
       return launch(kernel, gr, 0, p->stream, X, from_dirs ? nullptr : eta, scale, X2, st, p->n, rho ? rho_r : nullptr,
-                    rho ? rho_g : nullptr,
-                    rho ? p->pH() : nullptr, from_dirs ? p->dirs.get() : nullptr, from_dirs ? p->dirs_coef.get() : nullptr,
+                    rho ? rho_g : nullptr, ph, from_dirs ? p->dirs.get() : nullptr, from_dirs ? p->dirs_coef.get() : nullptr,
                     (from_dirs && !rho) ? p->eta.get() : nullptr);
     };
     if (from_dirs) return rho ? go(k_retract<D, R, true, true>) : go(k_retract<D, R, false, true>);
@@ -304,14 +306,15 @@ int launch_retract(dpgo_problem_s* p, const double* X, const double* eta, double
 }
 
 int launch_rtr_update(dpgo_problem_s* p) {
-  // (the partial sums of the last k_grad launch and of the last k_retract / k_hess launch that wrote pH(): their grids)
-  const int ge = p->nb_grad > 0 ? p->nb_grad : p->grid_s(), gh = p->nb_hess > 0 ? p->nb_hess : p->grid_s();
+  // (the partial sums of the last k_grad launch and of the last k_retract / k_hess launch that wrote region H)
+  CHK(sums_ready(p->pE));
+  CHK(sums_ready(p->pH));
   CHK(dispatch_dr(p->d, p->r, [&](auto D, auto R) {
-    return launch(k_rtr_update<D, R>, p->grid_flat(), 0, p->stream, p->x1, p->x2, p->g1, p->g2, p->S1, p->S2, p->pE(), ge,
-                  p->pH(), gh, p->dstate + p->cur, p->dstate + (p->cur ^ 1), p->n);
+    return launch(k_rtr_update<D, R>, p->grid_flat(), 0, p->stream, p->x1, p->x2, p->g1, p->g2, p->S1, p->S2, p->pE.in(),
+                  p->pE.count(), p->pH.in(), p->pH.count(), p->state.in(), p->state.out(), p->n);
   }));
   HIPC(hipGetLastError());
-  p->cur ^= 1;
+  p->state.advance();
   // the other half of the kernel's contract: whatever it decides, the pair it called (g2, S2) holds the current point's
   // gradient and S when it is done -- every later launch finds them under the names g1, S1.  (Both pairs are the handle's
   // own buffers and nothing keeps their addresses across launches.)
@@ -329,10 +332,9 @@ int launch_precond(dpgo_problem_s* p, const double* X, const double* V, const do
 }
 
 int launch_rtr_begin(dpgo_problem_s* p, double tol, double Delta0, double Dmax, int max_inner, int tiny) {
-  launch(k_rtr_begin, 1, 0, p->stream, p->pE(), p->nb_grad > 0 ? p->nb_grad : p->grid_s(), p->dstate, tol, Delta0, Dmax,
-         max_inner, tiny);
+  CHK(sums_ready(p->pE));
+  launch(k_rtr_begin, 1, 0, p->stream, p->pE.in(), p->pE.count(), p->state.rewind(), tol, Delta0, Dmax, max_inner, tiny);
   HIPC(hipGetLastError());
-  p->cur = 0;
   return DPGO_OK;
 }
 
@@ -448,9 +450,12 @@ int dpgo_problem_create(dpgo_problem_t* out, int r, int d, int n, int device) {
     CHK(p->S1.alloc((size_t)n * d * d));
     CHK(p->S2.alloc((size_t)n * d * d));
     CHK(p->dinv.alloc((size_t)n * p->b * p->b));
-    CHK(p->partials.alloc(5 * kPartialCap * kNP));
-    HIPC(hipMemsetAsync(p->partials, 0, sizeof(double) * 5 * kPartialCap * kNP, p->stream));
-    CHK(p->dstate.alloc(2));
+    CHK(p->partial_mem.alloc(4 * kPartialCap * kNP));
+    HIPC(hipMemsetAsync(p->partial_mem, 0, sizeof(double) * 4 * kPartialCap * kNP, p->stream));
+    int q = 0;
+    for (Partials* R : {&p->pE, &p->pA, &p->pB, &p->pH}) R->base = p->partial_mem + (q++) * kPartialCap * kNP;
+    CHK(p->state_mem.alloc(2));
+    p->state.base = p->state_mem;
     // (host-coherent, device-visible: the one-launch solve's commit kernel writes its report straight into them)
     CHK(p->hstate.alloc(1, hipHostMallocCoherent | hipHostMallocMapped));
     CHK(p->pctrl.alloc(1));
@@ -772,7 +777,7 @@ int dpgo_problem_rie_hess(dpgo_problem_t p, const double* X, const double* V, do
   CHK(eval_common(p, X));
   CHK(h2d(p, p->eta, V));
   CHK(launch_grad(p, p->x2, nullptr, p->S2, nullptr));
-  CHK(launch_hess(p, p->x2, p->S2, p->eta, nullptr, p->g2, p->pH(), nullptr, 0));
+  CHK(launch_hess(p, p->x2, p->S2, p->eta, nullptr, p->g2, nullptr, 0));
   return d2h(p, HV, p->g2);
 }
 

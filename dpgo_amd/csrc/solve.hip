@@ -7,6 +7,10 @@ int launch_tcg_update(dpgo_problem_s* p, const double* dinv, int first, double* 
                       double ml_omega) {
   const bool ml_mode = ml_omega > 0.0;
   const int g = p->grid_u(ml_mode);
+  // <delta, H delta> of the last Hessian step from region A (with `first` the kernel sums nothing: no test), <r,r>, <z,r> to B
+  if (!first) CHK(sums_ready(p->pA));
+  double* pb = nullptr;
+  CHK(sums_out(p->pB, g, &pb));
   double* zt = z_out ? z_out : p->z;
   // (the pre-smoothed iterate of a cycle that keeps its internal vectors in fp32 goes to that buffer instead)
   float* z32 = (ml_omega > 0.0 && !p->ml.empty() && z_out == p->ml[0].x1 && p->ml_vec32_active()) ? p->ml[0].x1f : nullptr;
@@ -17,8 +21,8 @@ int launch_tcg_update(dpgo_problem_s* p, const double* dinv, int first, double* 
     const bool def = p->dirs_on;
     auto go = [&](auto kernel, auto... z32_arg) {
       return launch(kernel, g, 0, p->stream, p->x1, p->g1, dinv, def ? nullptr : p->delta.get(), p->Hd,
-                    def ? nullptr : p->eta.get(), p->rr, zt, p->pA(), p->grid_s(), p->pB(), p->dstate + p->cur,
-                    p->dstate + (p->cur ^ 1), first, p->n, p->hflag, p->gen, ml_omega, def ? p->dirs_coef.get() : nullptr,
+                    def ? nullptr : p->eta.get(), p->rr, zt, p->pA.in(), p->pA.count(), pb, p->state.in(),
+                    p->state.out(), first, p->n, p->hflag, p->gen, ml_omega, def ? p->dirs_coef.get() : nullptr,
                     z32_arg...);
     };
     if constexpr (Span<D, R, 1>::kOk) {
@@ -33,7 +37,7 @@ int launch_tcg_update(dpgo_problem_s* p, const double* dinv, int first, double* 
     }
   }));
   HIPC(hipGetLastError());
-  p->cur ^= 1;
+  p->state.advance();
   return DPGO_OK;
 }
 
@@ -60,19 +64,24 @@ int launch_tcg_hess_with(dpgo_problem_s* p, const DevState* sin, DevState* sout,
                          unsigned gen) {  // (the state slots and the progress word of the caller's choice: kernel probes)
   if (p->dirs_on && !p->dirs) return fail(DPGO_ERR_STATE, "deferred tCG launch without a direction ring");
   double* dl = p->dirs_on ? p->dirs.get() : p->delta.get();
+  // <r,r>, <z,r> from region B (the update kernel's or, in the V-cycle, the level-0 post-smoothing's), <delta, H delta> to A
+  CHK(sums_ready(p->pB));
+  const int g = p->grid_s();
+  double* pa = nullptr;
+  CHK(sums_out(p->pA, g, &pa));
   CHK(dispatch_dr(p->d, p->r, [&](auto Dc, auto Rc) {
     constexpr int D = decltype(Dc)::value, R = decltype(Rc)::value;
     return dispatch_tcg_hess<D, R>(p, [&](auto kernel, const auto& Q) {
-      return launch(kernel, p->grid_s(), 0, p->stream, Q, p->x1, p->S1, p->z, dl, p->Hd, p->pB(), p->nb_zr(), p->pA(),
-                    sin, sout, first, p->n, hflag, gen);
+      return launch(kernel, g, 0, p->stream, Q, p->x1, p->S1, p->z, dl, p->Hd, p->pB.in(), p->pB.count(), pa, sin, sout,
+                    first, p->n, hflag, gen);
     });
   }));
   HIPC(hipGetLastError());
   return DPGO_OK;
 }
 int launch_tcg_hess(dpgo_problem_s* p, int first) {
-  CHK(launch_tcg_hess_with(p, p->dstate + p->cur, p->dstate + (p->cur ^ 1), first, p->hflag, p->gen));
-  p->cur ^= 1;
+  CHK(launch_tcg_hess_with(p, p->state.in(), p->state.out(), first, p->hflag, p->gen));
+  p->state.advance();
   return DPGO_OK;
 }
 
@@ -339,18 +348,17 @@ int launch_rtr_persistent(dpgo_problem_s* p, const dpgo_ropt_params* prm, const 
         }
       }
       return launch(kernel, p->persist_wgs, lds, p->stream, p->Q.dev(), p->x1, Glin, dinv, p->x2, p->eta, p->z, p->pgran, salt,
-                    p->dstate, p->pctrl, p->n, p->hflag, p->gen, poll, ra, add);
+                    p->state.slot(0), p->pctrl, p->n, p->hflag, p->gen, poll, ra, add);
     });
   }));
   {  // the iterate reaches the caller's X only if the launch completed on every participant (k_persist_commit)
     const size_t count = (size_t)p->n * p->T;
     const int grid = (int)std::min<size_t>(1024, (count + kBlock - 1) / kBlock);
-    // (p->cur = 0 below: dstate[0] is the record the solve leaves; the commit kernel also writes it and the control block
-    // into the host-coherent copies the caller reads after synchronising)
-    launch(k_persist_commit, grid, 0, p->stream, p->dstate, p->pctrl, p->x2, p->x1, count, p->hstate, p->hctrl);
+    // (rewind: slot 0 is the record the solve leaves; the commit kernel also writes it and the control block into the
+    // host-coherent copies the caller reads after synchronising)
+    launch(k_persist_commit, grid, 0, p->stream, p->state.rewind(), p->pctrl, p->x2, p->x1, count, p->hstate, p->hctrl);
   }
   HIPC(hipGetLastError());
-  p->cur = 0;
   *used = true;
   return DPGO_OK;
 }
@@ -377,7 +385,6 @@ int rtr_outer_iteration(dpgo_problem_s* p, const dpgo_ropt_params* prm, const do
   // (additive: where the persistent kernel cannot run -- no free slots, an earlier time-out -- the V-cycle on the same
   // two-level hierarchy takes over)
   const bool ml = prm->precond == DPGO_PRECOND_MULTILEVEL || add;
-  p->zr_from_post = ml;
   if (add) cnt.vcycle_for_additive = true;
   // multilevel: the update kernel writes the pre-smoothing step of level 0 instead of the block-Jacobi z; the cycle's
   // last kernel produces z and the partial sums <r,r>, <z,r>
@@ -385,7 +392,7 @@ int rtr_outer_iteration(dpgo_problem_s* p, const dpgo_ropt_params* prm, const do
     if (ml) {
       CHK(launch_tcg_update(p, dinv, first, p->ml[0].x1, p->ml_omega));
       const bool early_stop = options().ml_early_stop != 0;
-      return launch_ml_tail(p, p->x1, p->rr, p->z, p->pB(), p->dstate + p->cur, early_stop && !first);
+      return launch_ml_tail(p, p->x1, p->rr, p->z, &p->pB, p->state.in(), early_stop && !first);
     }
     return launch_tcg_update(p, dinv, first);
   };
@@ -456,12 +463,12 @@ int rtr_outer_iteration(dpgo_problem_s* p, const dpgo_ropt_params* prm, const do
   // DPGO_RHO_EXACT=1: from a fresh H eta instead, one more pass over Q (the reference path of the tests).
   const bool rho_exact = options().rho_exact != 0;
   // (a solve that kept its directions: the retraction forms eta from them, and leaves it in p->eta for the exact tail)
-  CHK(launch_retract(p, p->x1, p->eta, 1.0, p->x2, p->dstate + p->cur, rho_exact ? nullptr : p->rr.get(),
+  CHK(launch_retract(p, p->x1, p->eta, 1.0, p->x2, p->state.in(), rho_exact ? nullptr : p->rr.get(),
                      rho_exact ? nullptr : p->g1.get(), p->dirs_on));
-  CHK(launch_grad(p, p->x2, p->g2, p->S2, nullptr, p->dstate + p->cur, p->tcg_sym && outer_sym_enabled()));
+  CHK(launch_grad(p, p->x2, p->g2, p->S2, nullptr, p->state.in(), p->tcg_sym && outer_sym_enabled()));
   cnt.spmm += 1;
   if (rho_exact) {
-    CHK(launch_hess(p, p->x1, p->S1, p->eta, p->g1, p->Hd, p->pH(), p->dstate + p->cur, 0, p->tcg_sym && outer_sym_enabled()));
+    CHK(launch_hess(p, p->x1, p->S1, p->eta, p->g1, p->Hd, p->state.in(), 0, p->tcg_sym && outer_sym_enabled()));
     cnt.spmm += 1;
   }
   CHK(launch_rtr_update(p));  // (exchanges the roles of g1 / g2 and S1 / S2)

@@ -17,7 +17,7 @@ import numpy as np
 import pytest
 
 import certificate_reference as ref
-from conftest import DATA, tiles_to_matrix, to_product_measurements
+from conftest import DATA, device_tcg_mode, matrix_to_tiles, tiles_to_matrix, to_product_measurements
 from test_parity_gpu import RTOL_ELEM, _random_graph, relerr
 
 pytestmark = pytest.mark.gpu
@@ -27,7 +27,7 @@ SPLITS = (1, 2, 4)
 SENTINEL = 0x7FF4DEADBEEF0BAD  # a signalling-NaN bit pattern no kernel writes
 GEOMETRY_VARS = ("DPGO_SPLIT", "DPGO_SPMM_SYMMETRIC", "DPGO_GRID_UPDATE", "DPGO_GRID_HESS", "DPGO_GRID_HESS_SYM",
                  "DPGO_GRID_RETRACT", "DPGO_GRID_OUTER_SYM", "DPGO_GRID_SPMM_SYM", "DPGO_GRID_ML", "DPGO_COARSE_GRID",
-                 "DPGO_DENSE_CHUNK", "DPGO_PERSIST")
+                 "DPGO_DENSE_CHUNK", "DPGO_PERSIST", "DPGO_RHO_EXACT", "DPGO_TCG_DIRS")
 
 
 def tile_poses(d, split):
@@ -400,6 +400,74 @@ def test_certificate_under_split_2_and_caps_matches_default(oracle):
             assert got.status == want.status, (env, got.status, want.status)
             assert abs(got.lambda_min - want.lambda_min) <= 1e-10, (env, got.lambda_min, want.lambda_min)
             del prob
+
+
+HANDOFF_CAPS = {"DPGO_GRID_UPDATE": "7", "DPGO_GRID_HESS": "3", "DPGO_GRID_RETRACT": "5"}
+_SPHERE = {}
+
+
+def _sphere_oracle(oracle, precond):
+    """sphere2500 at r = 5 and the oracle's solves of test_optimize_matches_oracle_at_matched_settings from the lifted
+    chordal initialisation (the device's tCG arithmetic, and the reference's); computed once per preconditioner."""
+    if "graph" not in _SPHERE:
+        om, n = oracle.read_g2o(os.path.join(DATA, "sphere2500.g2o"))
+        Q = oracle.construct_Q(n, om.d, om)
+        _SPHERE["graph"] = (om, n, Q, oracle.lift(oracle.chordal_initialization(om, n), 5))
+    om, n, Q, X0 = _SPHERE["graph"]
+    if precond not in _SPHERE:
+        op = oracle.QuadraticProblem(Q, None, 5, om.d, precond=precond)
+        oopt = oracle.QuadraticOptimizer(op, oracle.ROptParameters(), hess_recurrence=device_tcg_mode(n, om.d, 5))
+        Xo = oopt.optimize(X0)
+        ref_opt = oracle.QuadraticOptimizer(oracle.QuadraticProblem(Q, None, 5, om.d, precond=precond), oracle.ROptParameters())
+        Xr = ref_opt.optimize(X0)
+        Xa = np.abs(X0).reshape(-1, 5)
+        _SPHERE[precond] = (oopt.result, Xo, ref_opt.result, Xr, float((Xa * (abs(op.Qs) @ Xa)).sum()))
+    return (om, n, X0) + _SPHERE[precond]
+
+
+@pytest.mark.parametrize("precond", ["jacobi", "none"])
+def test_multi_launch_solve_hands_partial_sums_across_different_grids(oracle, precond):
+    """sphere2500 on the multi-launch solve (one-launch solve off) without the V-cycle, under caps that bind on every kernel
+    family -- 40 workgroup tiles for the update family, 157 at four lane groups per pose; update 7, Hessian step / k_grad /
+    k_hess 3, retraction 5 -- with the rho test from tCG's residual (k_retract writes region H) and from a fresh H eta
+    (k_hess does), with and without kept directions: every writer / reader pair of the partial-sum regions E, A, B and H
+    runs on two different grids.  Each solve is the oracle's, by the counts, status and tolerances of
+    test_optimize_matches_oracle_at_matched_settings; so is a second solve on the same handle, which starts from regions
+    the first one left written."""
+    import dpgo_amd
+    om, n, X0, ro, Xo, rr, Xr, scale = _sphere_oracle(oracle, precond)
+    d, r = om.d, 5
+    for rho_exact, dirs in [(a, b) for a in (0, 1) for b in (0, 1)]:
+        # (the defaults -- DPGO_RHO_EXACT 0, DPGO_TCG_DIRS 1 -- by leaving the switch unset: library_options unsets both)
+        env = dict(HANDOFF_CAPS, **({"DPGO_RHO_EXACT": "1"} if rho_exact else {}), **({} if dirs else {"DPGO_TCG_DIRS": "0"}))
+        with library_options(env):
+            text = dpgo_amd.lib.describe_options()
+            assert "DPGO_RHO_EXACT=%d" % rho_exact in text and "DPGO_TCG_DIRS=%d" % dirs in text, text
+            pg = dpgo_amd.PoseGraph(0, r, d)
+            pg.setMeasurements(to_product_measurements(om))
+            prob = dpgo_amd.QuadraticProblem(pg)
+            prob.setPersistent(False)
+            assert "lane groups per pose 4;" in prob.describe()
+            gopt = dpgo_amd.QuadraticOptimizer(prob, dpgo_amd.ROptParameters(precond=precond))
+            for solve in (1, 2):
+                Xg = matrix_to_tiles(gopt.optimize(tiles_to_matrix(X0)), d)
+                rg = gopt.getOptResult()
+                try:
+                    assert rg.success
+                    assert abs(rg.fInit - ro.fInit) <= 1e-14 * scale
+                    assert abs(rg.gradNormInit - ro.gradNormInit) <= 1e-10 * ro.gradNormInit
+                    assert rg.rtr_iterations == ro.outer_iters
+                    assert rg.tcg_iterations == ro.tcg_iters
+                    assert rg.tCGStatus == oracle.TCG_NAMES[ro.tCGStatus]
+                    assert abs(rg.fOpt - ro.fOpt) <= 1e-9 * abs(ro.fOpt) + 1e-14 * scale
+                    assert relerr(Xg, Xo) < 1e-7
+                    assert abs(prob.f(tiles_to_matrix(Xg)) - rg.fOpt) <= 1e-12 * abs(rg.fOpt) + 1e-14 * scale
+                    assert rr.outer_iters == rg.rtr_iterations
+                    assert abs(rg.fOpt - rr.fOpt) <= 1e-7 * abs(rr.fOpt) + 1e-14 * scale
+                    assert relerr(Xg, Xr) < 1e-5
+                except AssertionError as e:
+                    raise AssertionError("%s solve %d under %s: %s" % (precond, solve, env, e)) from e
+            del gopt, prob
 
 
 # ---------------------------------------------------------------- C. caller pointers at an 8-byte offset
