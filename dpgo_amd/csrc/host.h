@@ -10,10 +10,18 @@
 //   align.hip       frame alignment of agents that start in their own frames: candidates, robust average, lift
 //   bench_probes.hip  kernel timing probes used by bench.py
 //   certify.hip     certificate of global optimality (LOBPCG on C(X) = Q - Lambda(X)) and the staircase escape
-// handoff.h (host compiler only, no HIP): the partial-sum regions and the state slots one launch leaves for the next.
+// Host compiler only, no HIP (each has a stand-alone test program under tests/cxx or is included by one):
+//   handoff.h        the partial-sum regions and the state slots one launch leaves for the next
+//   options.h        the DPGO_* switches: one table, read from the environment once
+//   taskpool.h       the set-up code's worker threads (TaskPool), setup_threads, parallel_ranges, pattern_by_ranges
+//   aggregation.h / aggregation.cpp  the hierarchy's set-up over index vectors: aggregates (growth, merge, index runs),
+//                    block patterns of A P and of the next level, run / tile / chunk tables, the additive layout's search
 #pragma once
 #include "kernels.h"
 #include "handoff.h"
+#include "options.h"
+#include "taskpool.h"
+#include "aggregation.h"
 
 #include <algorithm>
 #include <atomic>
@@ -220,85 +228,6 @@ struct Bsr {
   BsrDev dev() const { return BsrDev{rowptr, colidx, vals}; }
 };
 
-// Every tuning / A-B switch of the library in ONE place: read from the environment once (first use; dpgo_options_reload
-// reads again), printed by dpgo_describe_options / dpgo_problem_describe.  -1 (or 0 where noted) = not set: the size rules
-// decide.  The kernel-selecting ones are exercised by tests/test_parity_gpu.py::test_kernel_selecting_switches_*.
-//        field              variable                  unset  meaning
-#define DPGO_OPTIONS(X)                                                                                                  \
-  X(split,             "DPGO_SPLIT",              0,  "lane groups per pose of the SpMM-family kernels: 1, 2, 4 (0: by size)")       \
-  X(spmm_symmetric,    "DPGO_SPMM_SYMMETRIC",    -1,  "symmetric storage of Q for blocks beyond the Infinity Cache: 0 / 1")          \
-  X(stream_nt,         "DPGO_STREAM_NT",         -1,  "non-temporal single-use operands in the tCG-step kernels: 0 / 1")             \
-  X(outer_sym,         "DPGO_OUTER_SYM",          1,  "outer RTR iteration (k_grad / k_hess) reads the symmetric copy when tCG does") \
-  X(rho_exact,         "DPGO_RHO_EXACT",          0,  "rho test from a fresh H eta (k_hess, one more pass over Q) instead of tCG's residual: reference path") \
-  X(tcg_dirs,          "DPGO_TCG_DIRS",           1,  "multi-launch tCG keeps its directions and k_retract sums eta once (0: eta += alpha delta every iteration: reference path)") \
-  X(tcg_dirs_max_mb,   "DPGO_TCG_DIRS_MAX_MB", 4096,  "largest direction ring (RTR_tCG_iterations pose vectors) a solve may hold; beyond it the solve runs the reference path") \
-  X(tile_walk,         "DPGO_TILE_WALK",          1,  "symmetric-storage kernels walk each XCD's tiles breadth-first over the tile graph (0: index order)") \
-  X(tcg_ahead,         "DPGO_TCG_AHEAD",          0,  "iterations the just-in-time feed stays ahead (0: 2 multilevel / 4 otherwise)") \
-  X(grid_update,       "DPGO_GRID_UPDATE",        0,  "launch cap of k_tcg_update (0: resident count)")                              \
-  X(grid_hess,         "DPGO_GRID_HESS",          0,  "launch cap of k_tcg_hess (0: resident count)")                                \
-  X(grid_hess_sym,     "DPGO_GRID_HESS_SYM",      0,  "launch cap of k_tcg_hess_sym (0: resident count)")                            \
-  X(grid_retract,      "DPGO_GRID_RETRACT",       0,  "launch cap of k_retract (0: 1024)")                                           \
-  X(grid_outer_sym,    "DPGO_GRID_OUTER_SYM",     0,  "launch cap of k_grad / k_hess on the symmetric storage (0: resident count)")  \
-  X(grid_spmm_sym,     "DPGO_GRID_SPMM_SYM",      0,  "launch cap of k_spmm_sym (0: resident count, at most 1024)")                  \
-  X(grid_ml,           "DPGO_GRID_ML",            0,  "launch cap of the level-0 restriction / post-smoothing (0: resident count)")  \
-  X(grid_edges,        "DPGO_GRID_EDGES",         0,  "launch cap of k_edge_robust, GNC and robust re-weighting alike (0: 1024)")    \
-  X(persist,           "DPGO_PERSIST",           -1,  "one-launch solve (k_rtr_persist) off / on whatever the size: 0 / 1")          \
-  X(persist_max_poses, "DPGO_PERSIST_MAX_POSES",  0,  "largest block the one-launch solve takes (0: every block it can hold)")       \
-  X(persist_split,     "DPGO_PERSIST_SPLIT",      0,  "lane groups per pose of the one-launch solve: 1, 4 (0: by size)")             \
-  X(persist_mt,        "DPGO_PERSIST_MT",         0,  "tiles per workgroup of the one-launch solve: 1, 2 (0: by size)")              \
-  X(additive_tiles,    "DPGO_ADDITIVE_TILES",     1,  "workgroup tiles per aggregate of the additive one-launch solve: 1, 2 (opt-in: blocks up to ~28 000 poses)") \
-  X(poll_first,        "DPGO_POLL_FIRST",        -1,  "s_sleep units before the first sweep of the in-kernel all-reduce")            \
-  X(poll_sleep,        "DPGO_POLL_SLEEP",        -1,  "s_sleep units between sweeps of the in-kernel all-reduce")                    \
-  X(poll_first_pay,    "DPGO_POLL_FIRST_PAY",    -1,  "the same before the first sweep of a reduction that carries a payload")       \
-  X(persist_verbose,   "DPGO_PERSIST_VERBOSE",    0,  "per-solve phase report of the one-launch solve on stderr")                    \
-  X(setup_timing,      "DPGO_SETUP_TIMING",       0,  "section times of the hierarchy's symbolic set-up on stderr")                  \
-  X(setup_threads,     "DPGO_SETUP_THREADS",      0,  "host threads of the hierarchy's symbolic set-up (0: min(8, cores); 1: serial)") \
-  X(setup_pin,         "DPGO_SETUP_PIN",          1,  "set-up worker threads placed in the CPU group of the thread that first used them") \
-  X(auto_cost_rule,    "DPGO_AUTO_COST_RULE",     1,  "DPGO_PRECOND_AUTO on coupled blocks: cost rule (0: tCG-budget hysteresis only)") \
-  X(ml_graph,          "DPGO_ML_GRAPH",           1,  "graph aggregates in the default hierarchy (0: index runs)")                   \
-  X(ml_graph_size,     "DPGO_ML_GRAPH_SIZE",      0,  "growth size of the default graph aggregates (0: by size)")                    \
-  X(ml_growth_chunks,  "DPGO_ML_GROWTH_CHUNKS",   0,  "index ranges the graph aggregates grow and merge in (0: 8 from 65 536 poses, else 1)") \
-  X(ml_ap,             "DPGO_ML_AP",              1,  "two-level post-smoothing through A P (0: gather through Q; index runs only)") \
-  X(ml_dense_sym,      "DPGO_ML_DENSE_SYM",      -1,  "dense level from the packed lower triangle on the matrix cores: 0 / 1")       \
-  X(ml_early_stop,     "DPGO_ML_EARLY_STOP",      1,  "tCG's residual test in the restriction kernel, one kernel early")             \
-  X(ml_operator_bits,  "DPGO_ML_OPERATOR_BITS",   0,  "level-0 operator copies of the cycle on HBM-bound blocks: 32 / 64 (0: 32)")   \
-  X(ml_vector_bits,    "DPGO_ML_VECTOR_BITS",     0,  "cycle-internal vectors (pre-smoothed iterate, kept residual) beside fp32 operator copies: 32 / 64 (0: 32)") \
-  X(ml_dense_bits,     "DPGO_ML_DENSE_BITS",      0,  "dense level beside fp32 cycle vectors: 32 / 64 (0: 64 -- fp32 measured neutral)") \
-  X(gj_mfma,           "DPGO_GJ_MFMA",            1,  "rank-64 updates of the dense inverse on the fp64 matrix cores")               \
-  X(dense_chunk,       "DPGO_DENSE_CHUNK",        0,  "tiles per workgroup of k_dense_sym_apply (0: default)")                       \
-  X(coarse_nodes,      "DPGO_COARSE_NODES",       0,  "nodes per workgroup of k_ml_coarse_prolong: 1-4 (0: by size)")                \
-  X(coarse_grid,       "DPGO_COARSE_GRID",        0,  "launch cap of k_ml_coarse_prolong (0: default)")                              \
-  X(coarse_nt,         "DPGO_COARSE_NT",         -1,  "non-temporal loads of the dense inverse: 0 / 1")
-struct Options {
-#define X(field, var, unset, text) int field = unset;
-  DPGO_OPTIONS(X)
-#undef X
-};
-inline Options& options_storage() {
-  static Options o;
-  return o;
-}
-inline void options_read(Options& o) {
-  o = Options();
-#define X(field, var, unset, text) \
-  if (const char* e_ = std::getenv(var)) o.field = (*e_ == 0) ? 1 : std::atoi(e_);
-  DPGO_OPTIONS(X)
-#undef X
-}
-inline const Options& options() {
-  static const bool once = (options_read(options_storage()), true);
-  (void)once;
-  return options_storage();
-}
-inline std::string options_describe() {
-  const Options& o = options();
-  std::string s;
-#define X(field, var, unset, text) s += std::string(var) + "=" + std::to_string(o.field) + (o.field == (unset) ? "" : " [set]") + "  # " + text + "\n";
-  DPGO_OPTIONS(X)
-#undef X
-  return s;
-}
-
 // What a solve has decided before its first launch (plan_solve, solve.hip): kept by a begin / end solve between the calls.
 struct SolvePlan {
   dpgo_ropt_params prm{};  // the caller's, DPGO_PRECOND_AUTO resolved to what the handle currently runs
@@ -367,7 +296,7 @@ struct dpgo_problem_s {
     // r - A (x1 + P xc) = (r - A x1) - (A P) xc
     Bsr AP;
     DevBuf<double> res1;
-    // level 0 of a two-level hierarchy with GRAPH aggregates (ml_graph_aggregates): label of every pose, members of every
+    // level 0 of a two-level hierarchy with GRAPH aggregates (grow_aggregates, aggregation.h): label of every pose, members of every
     // aggregate in discovery order, the spanning tree the prolongation is composed along, P_i^T res_i of every pose
     bool graph = false;
     DevBuf<int32_t> lab, agg_ptr, agg_mem, parent, pslot;
@@ -388,7 +317,8 @@ struct dpgo_problem_s {
     AggMap agg() const { return AggMap{graph ? lab : nullptr, k}; }
   };
   std::vector<MlLevel> ml;
-  std::vector<int32_t> h_rowptr, h_colidx;  // host copy of Q's block pattern (symbolic setup of the hierarchy)
+  Pattern h_pattern;  // host copy of Q's block pattern (symbolic setup of the hierarchy)
+  bool has_pattern() const { return h_pattern.n() == n; }
   bool ml_symbolic = false, ml_ready = false, ml_user_ks = false;
   bool ml_additive_layout = false;  // the hierarchy is the one the additive preconditioner needs (one aggregate per workgroup tile)
   // layout of the additive preconditioner's one-launch solve for this block pattern (additive_plan): lane groups per pose
@@ -405,8 +335,8 @@ struct dpgo_problem_s {
   // the aggregation the plan was found with (host arrays), reused by the symbolic setup that follows: growing and merging
   // the aggregates of a 12 500-pose block is 1.4 ms of host time
   struct AggCache {
+    Aggregates agg;
     int S = 0, cap = 0;
-    std::vector<int32_t> lab, ptr, mem, parent, pslot;
   } add_agg;
   double ml_omega = 0.7, ml_shift = 1e-1;
   // the dense level of the hierarchy: what lives and dies with it (ml_free assigns an empty one)
@@ -603,120 +533,6 @@ struct Counters {
   bool vcycle_for_additive = false;  // an outer iteration of an "additive" solve ran the V-cycle instead
 };
 
-// Host worker threads of the set-up code (the hierarchy's symbolic set-up): created once per process and kept -- in a
-// process that has the HIP runtime and an ML framework loaded pthread_create costs 0.2-0.4 ms (static TLS of every loaded
-// library), more than the sections it would run.  A batch = fn(0 .. count-1); whoever waits for a batch executes its items
-// too, so batches may be started from inside items (nested sections) without a deadlock.
-class TaskPool {
- public:
-  struct Batch {
-    std::function<void(int)> fn;
-    int count = 0;
-    std::atomic<int> next{0}, done{0};
-  };
-  using Job = std::shared_ptr<Batch>;
-  static TaskPool& get() {
-    static TaskPool* pool = new TaskPool();  // never destroyed: the workers are detached
-    return *pool;
-  }
-  // starts fn(0 .. count-1) on the workers; the caller goes on and later calls wait()
-  Job submit(int count, std::function<void(int)> fn, int max_threads) {
-    Job b = std::make_shared<Batch>();
-    b->fn = std::move(fn);
-    b->count = count;
-    const int helpers = std::max(0, std::min(count, max_threads - 1));
-    if (helpers > 0) {
-      {
-        std::lock_guard<std::mutex> lk(mu_);
-        while ((int)nworkers_ < std::min(kMaxWorkers, std::max(helpers, (int)nworkers_))) {
-          const int id = (int)nworkers_;
-          std::thread([this, id] {
-            pin(id);
-            loop();
-          }).detach();
-          ++nworkers_;
-        }
-        for (int k = 0; k < helpers; ++k) queue_.push_back(b);
-      }
-      cv_.notify_all();
-    }
-    return b;
-  }
-  // executes what is left of the batch, then waits for the items other threads are still running
-  void wait(const Job& b) {
-    if (!b) return;
-    help(*b);
-    while (b->done.load(std::memory_order_acquire) < b->count) std::this_thread::yield();
-  }
-  void run(int count, const std::function<void(int)>& fn, int max_threads) {
-    if (count <= 0) return;
-    if (count == 1 || max_threads <= 1) {
-      for (int k = 0; k < count; ++k) fn(k);
-      return;
-    }
-    wait(submit(count, fn, max_threads));
-  }
-  // creates the workers ahead of their first use, from a helper thread (the caller pays one pthread_create)
-  void warm(int threads) {
-    bool expected = false;
-    if (threads <= 1 || !warmed_.compare_exchange_strong(expected, true)) return;
-    std::thread([this, threads] { wait(submit(threads - 1, [](int) {}, threads)); }).detach();
-  }
-
- private:
-  static constexpr int kMaxWorkers = 15;
-  // Workers next to the thread that created the pool (DPGO_SETUP_PIN=0: wherever the scheduler puts them): the sections
-  // they run share arrays of a few MB that thread has just written -- on a multi-socket host a worker on another socket
-  // (or another L3 slice) reads them across the fabric.  Heuristic: the aligned group of 8 consecutive CPU numbers around
-  // the creator's CPU (one core complex on current server parts), restricted to the process's affinity mask; a worker may
-  // run on any CPU of the group.  Purely a placement hint: failures are ignored.
-  int home_cpu_ = -1;
-  void pin(int) {
-    if (!pin_enabled() || home_cpu_ < 0) return;
-    cpu_set_t allowed, want;
-    CPU_ZERO(&allowed);
-    CPU_ZERO(&want);
-    if (sched_getaffinity(0, sizeof(allowed), &allowed) != 0) return;
-    const int lo = home_cpu_ & ~7;
-    int cnt = 0;
-    for (int c = lo; c < lo + 8; ++c)
-      if (c < CPU_SETSIZE && CPU_ISSET(c, &allowed)) CPU_SET(c, &want), ++cnt;
-    if (cnt >= 2) (void)pthread_setaffinity_np(pthread_self(), sizeof(want), &want);
-  }
-  static bool pin_enabled() { return options().setup_pin != 0; }
-  TaskPool() { home_cpu_ = sched_getcpu(); }
-  static void help(Batch& b) {
-    for (;;) {
-      const int k = b.next.fetch_add(1, std::memory_order_relaxed);
-      if (k >= b.count) return;
-      b.fn(k);
-      b.done.fetch_add(1, std::memory_order_release);
-    }
-  }
-  void loop() {
-    for (;;) {
-      Job b;
-      {
-        std::unique_lock<std::mutex> lk(mu_);
-        cv_.wait(lk, [this] { return !queue_.empty(); });
-        b = std::move(queue_.front());
-        queue_.erase(queue_.begin());
-      }
-      help(*b);
-    }
-  }
-  std::mutex mu_;
-  std::condition_variable cv_;
-  std::vector<Job> queue_;
-  unsigned nworkers_ = 0;
-  std::atomic<bool> warmed_{false};
-};
-// waits for a job when the scope is left, whichever way
-struct JobGuard {
-  TaskPool::Job job;
-  ~JobGuard() { TaskPool::get().wait(job); }
-};
-
 struct PersistGeo {
   int split = 0, mt = 0, wgs = 0, slots = 0;
 };
@@ -760,14 +576,7 @@ int ml_level_split(int n);
 int ml_default_graph_size(int n, int b);
 std::vector<int> ml_default_ks(int n, int b, int split0);
 void ml_free(dpgo_problem_s* p);
-int ml_graph_aggregates(const std::vector<int32_t>& rowptr, const std::vector<int32_t>& colidx, int n, int S,
-                        std::vector<int32_t>& lab, std::vector<int32_t>& ptr, std::vector<int32_t>& mem,
-                        std::vector<int32_t>& parent, std::vector<int32_t>& pslot);
-int ml_merge_small_aggregates(const std::vector<int32_t>& rowptr, const std::vector<int32_t>& colidx, int n, int S, int cap,
-                              std::vector<int32_t>& lab, std::vector<int32_t>& ptr, std::vector<int32_t>& mem,
-                              std::vector<int32_t>& parent, std::vector<int32_t>& pslot);
 int ml_symbolic_setup(dpgo_problem_s* p, const std::vector<int>& ks_in, int perm_tile = 0);
-int setup_threads();  // host threads of the symbolic set-up (DPGO_SETUP_THREADS)
 int flat_grid(size_t items);
 bool gj_use_mfma();
 int dense_spd_inverse(hipStream_t s, double* M, int lda, double* W, double* Rx, bool mfma);

@@ -15,7 +15,7 @@
 // `gate`: the solver's state record -- launches enqueued after tCG finished return at once.
 
 // Which aggregate (node of the next level) a node belongs to: runs of k consecutive nodes, or -- level 0 of a two-level
-// hierarchy with GRAPH aggregates (host: ml_graph_aggregates) -- a label per pose.
+// hierarchy with GRAPH aggregates (host: grow_aggregates, aggregation.h) -- a label per pose.
 struct AggMap {
   const int32_t* lab;
   int k;

@@ -16,7 +16,7 @@ int ml_level_split(int n) { return n < 40000 ? 4 : 1; }
 // what it takes to get there in one coarsening; otherwise one more level.
 constexpr int kMlDense = 3200, kMlDenseMax = 6400;
 // Two-level hierarchies use GRAPH aggregates (a single negative entry -S: breadth-first-grown aggregates of at most S
-// poses, ml_graph_aggregates) whenever one coarsening with S <= kMlGraphMax reaches a dense level of about 2 500
+// poses, grow_aggregates) whenever one coarsening with S <= kMlGraphMax reaches a dense level of about 2 500
 // unknowns: compact aggregates need 40-60 % of the Hessian-vector products that index runs of the same size need
 // (DESIGN.md section 5), and the dense level can then be small.  DPGO_ML_GRAPH=0: index runs as before.
 constexpr int kMlGraphMax = 512, kMlGraphUnknownsPerPose = 1600;
@@ -28,7 +28,7 @@ int ml_default_graph_size(int n, int b) {
 }
 // Blocks whose plain greedy growth would use aggregates of >= kMlMergeFrom poses (n (d+1) >= ~100 000 unknowns: >= 25 600
 // poses in 3-D) grow them to S = ceil(n (d+1) / 2 200) instead and MERGE the growth's fragments up to 3 S / 2
-// (ml_merge_small_aggregates): the aggregates come out uniform (mean ~ S instead of ~0.55 S with a tail of fragments), the
+// (merge_small_aggregates): the aggregates come out uniform (mean ~ S instead of ~0.55 S with a tail of fragments), the
 // same coarse-space quality needs a quarter fewer of them -- 100k poses: 546 aggregates / 70 products to |rgrad| < 1e-2
 // against 732 / 77, a dense level of 38 MB instead of 69 MB; 25k: 536 / 87 against 589 / 93 (oracle, round 4).  Round 5:
 // from a plain growth size of 12 on (n (d+1) > ~17 600 unknowns: >= 4 400 poses in 3-D) -- torus3D 38 -> 35 products
@@ -79,369 +79,13 @@ void ml_free(dpgo_problem_s* p) {
   p->ml_ops32_ready = false;
 }
 
-// Large blocks grow (and merge) their aggregates independently inside `chunks` contiguous index ranges -- [n c / chunks,
-// n (c + 1) / chunks): a seed's search does not leave its range, a fragment joins a neighbour of its own range -- one host
-// thread each; the ranges' aggregates are numbered one range after the other.  This is the RULE (restated in the oracle:
-// amg_growth_chunks / the lo, hi arguments of amg_graph_aggregates and amg_merge_small_aggregates), not a schedule: the
-// result does not depend on the number of threads that execute it.  100k poses: growth + merge 3.7 -> 0.6 ms.
-int ml_growth_chunks(int n) {
-  const int forced = options().ml_growth_chunks;
-  if (forced > 0) return std::max(1, std::min(forced, std::max(1, n / 64)));
-  return n >= 65536 ? 8 : 1;
-}
-namespace {
-// growth inside [lo, hi): lab (aggregate ids local to the range, from 0), parent, pslot written at the range's indices;
-// mem / ptr local to the range
-int grow_range(const std::vector<int32_t>& rowptr, const std::vector<int32_t>& colidx, int lo, int hi, int S,
-               std::vector<int32_t>& lab, std::vector<int32_t>& ptr, std::vector<int32_t>& mem,
-               std::vector<int32_t>& parent, std::vector<int32_t>& pslot) {
-  mem.clear();
-  mem.reserve(hi - lo);
-  ptr.assign(1, 0);
-  int na = 0;
-  for (int s = lo; s < hi; ++s) {
-    if (lab[s] >= 0) continue;
-    const size_t first = mem.size();
-    lab[s] = na;
-    mem.push_back(s);
-    for (size_t head = first; head < mem.size() && (int)(mem.size() - first) < S; ++head) {
-      const int u = mem[head];
-      for (int t = rowptr[u]; t < rowptr[u + 1] && (int)(mem.size() - first) < S; ++t) {
-        const int v = colidx[t];
-        if (v < lo || v >= hi || lab[v] >= 0) continue;
-        lab[v] = na;
-        parent[v] = u;
-        pslot[v] = t;
-        mem.push_back(v);
-      }
-    }
-    ptr.push_back((int32_t)mem.size());
-    ++na;
-  }
-  return na;
-}
-
-// merge inside [lo, hi) (lab: ids local to the range); in place; returns the number of aggregates of the range
-int merge_range(const std::vector<int32_t>& rowptr, const std::vector<int32_t>& colidx, int lo, int hi, int S, int cap,
-                std::vector<int32_t>& lab, std::vector<int32_t>& ptr, std::vector<int32_t>& mem,
-                std::vector<int32_t>& parent, std::vector<int32_t>& pslot) {
-  const int na = (int)ptr.size() - 1;
-  const int n = hi - lo;
-  std::vector<std::vector<int32_t>> members(na);
-  for (int a = 0; a < na; ++a) members[a].assign(mem.begin() + ptr[a], mem.begin() + ptr[a + 1]);
-  std::vector<int> cnt(na, 0);
-  std::vector<int> touched;
-  for (bool changed = true; changed;) {
-    changed = false;
-    for (int a = 0; a < na; ++a) {
-      if (members[a].empty() || 2 * (int)members[a].size() > S) continue;
-      touched.clear();
-      for (int i : members[a])
-        for (int t = rowptr[i]; t < rowptr[i + 1]; ++t) {
-          const int v = colidx[t];
-          if (v < lo || v >= hi) continue;
-          const int c = lab[v];
-          if (c == a) continue;
-          if (cnt[c]++ == 0) touched.push_back(c);
-        }
-      std::sort(touched.begin(), touched.end());
-      int best = -1, best_n = 0;
-      for (int c : touched) {
-        if ((int)(members[c].size() + members[a].size()) <= cap && cnt[c] > best_n) best = c, best_n = cnt[c];
-        cnt[c] = 0;
-      }
-      if (best >= 0) {
-        members[best].insert(members[best].end(), members[a].begin(), members[a].end());
-        for (int i : members[a]) lab[i] = best;
-        members[a].clear();
-        changed = true;
-      }
-    }
-  }
-  // Members of the surviving aggregates in index order (one counting pass over the poses instead of a sort per aggregate),
-  // `grew` = absorbed at least one other aggregate.
-  std::vector<char> grew(na, 0);
-  for (int a = 0; a < na; ++a)
-    if (!members[a].empty() && (int)members[a].size() != ptr[a + 1] - ptr[a]) grew[a] = 1;
-  std::vector<int32_t> first_member(na, -1);
-  for (int i = hi - 1; i >= lo; --i) first_member[lab[i]] = i;
-  std::vector<int> alive;
-  for (int a = 0; a < na; ++a)
-    if (!members[a].empty()) alive.push_back(a);
-  std::sort(alive.begin(), alive.end(), [&](int x, int y) { return first_member[x] < first_member[y]; });
-  std::vector<int32_t> sorted_mem, sorted_ptr(na + 1, 0);
-  {  // only the aggregates that grew need their members sorted (the roots of the search below)
-    for (int a = 0; a < na; ++a) sorted_ptr[a + 1] = sorted_ptr[a] + (grew[a] ? (int32_t)members[a].size() : 0);
-    sorted_mem.resize(sorted_ptr[na]);
-    std::vector<int32_t> fill(sorted_ptr.begin(), sorted_ptr.end() - 1);
-    for (int i = lo; i < hi; ++i)
-      if (grew[lab[i]]) sorted_mem[fill[lab[i]]++] = i;
-  }
-  std::vector<int32_t> new_lab(n, -1), new_mem;  // (new_lab indexed by pose - lo)
-  std::vector<int32_t> old_parent(parent.begin() + lo, parent.begin() + hi), old_pslot(pslot.begin() + lo, pslot.begin() + hi);
-  std::fill(parent.begin() + lo, parent.begin() + hi, -1);
-  std::fill(pslot.begin() + lo, pslot.begin() + hi, 0);
-  new_mem.reserve(n);
-  std::vector<int32_t> new_ptr(1, 0);
-  for (size_t k = 0; k < alive.size(); ++k) {
-    const int a = alive[k];
-    if (!grew[a]) {
-      // untouched by the merge: the growth's own search started from the aggregate's smallest member (seeds are taken in
-      // index order) and claimed exactly these poses in exactly the order the search below would -- keep its tree
-      for (int m = ptr[a]; m < ptr[a + 1]; ++m) {
-        const int v = mem[m];
-        new_lab[v - lo] = (int32_t)k;
-        parent[v] = old_parent[v - lo];
-        pslot[v] = old_pslot[v - lo];
-        new_mem.push_back(v);
-      }
-      new_ptr.push_back((int32_t)new_mem.size());
-      continue;
-    }
-    // (a merged aggregate is connected by construction, so the search from its smallest member reaches everything; should
-    // the pattern not be symmetric, the members it misses become further roots in index order)
-    for (int q = sorted_ptr[a]; q < sorted_ptr[a + 1]; ++q) {
-      const int root = sorted_mem[q];
-      if (new_lab[root - lo] >= 0) continue;
-      size_t head = new_mem.size();
-      new_lab[root - lo] = (int32_t)k;
-      new_mem.push_back(root);
-      for (; head < new_mem.size(); ++head) {
-        const int u = new_mem[head];
-        for (int t = rowptr[u]; t < rowptr[u + 1]; ++t) {
-          const int v = colidx[t];
-          if (v < lo || v >= hi || lab[v] != a || new_lab[v - lo] >= 0) continue;
-          new_lab[v - lo] = (int32_t)k;
-          parent[v] = u;
-          pslot[v] = t;
-          new_mem.push_back(v);
-        }
-      }
-    }
-    new_ptr.push_back((int32_t)new_mem.size());
-  }
-  mem.swap(new_mem);
-  ptr.swap(new_ptr);
-  std::copy(new_lab.begin(), new_lab.end(), lab.begin() + lo);
-  return (int)alive.size();
-}
-}  // namespace
-
-template <class F>
-void parallel_ranges(int n, int chunks, F&& fn);
-int setup_threads();
-
-// Symbolic setup: level sizes, block patterns of the Galerkin operators, buffers.
-// Graph aggregates of at most S nodes, grown greedily: seeds in index order; a seed's aggregate takes unassigned nodes in
-// breadth-first order (queue; a node's neighbours in the order of its block row) until it holds S.  lab = aggregate of
-// every node, mem / ptr = members in discovery order, parent / pslot = the breadth-first tree (slot of block
-// (parent, node) in the pattern).  cap > 0: followed by the merge of the fragments (below), both inside the index ranges of
-// ml_growth_chunks.  Restated in oracle/dpgo_oracle.py (amg_graph_aggregates, amg_merge_small_aggregates).
-//
-// The merge: the greedy growth leaves fragments (pockets between full aggregates); where an aggregate is a WORKGROUP of the
-// one-launch solve (additive preconditioner) every fragment costs a whole workgroup.  Passes over the aggregates in index
-// order until nothing changes: an aggregate of at most S / 2 nodes joins the neighbouring aggregate (one it shares a block
-// with) it has the most blocks in common with among those that still have room (sizes add up to at most `cap`; ties: the
-// lower index).  Afterwards the aggregates are renumbered in the order of their smallest member and every aggregate's
-// breadth-first tree is rebuilt from that member (neighbours in block-row order).
-int ml_grow_and_merge(const std::vector<int32_t>& rowptr, const std::vector<int32_t>& colidx, int n, int S, int cap,
-                      bool do_grow, std::vector<int32_t>& lab, std::vector<int32_t>& ptr, std::vector<int32_t>& mem,
-                      std::vector<int32_t>& parent, std::vector<int32_t>& pslot, int chunks) {
-  chunks = std::max(1, std::min(chunks, std::max(1, n)));
-  if (do_grow) {
-    lab.assign(n, -1);
-    parent.assign(n, -1);
-    pslot.assign(n, 0);
-  }
-  struct Part {
-    std::vector<int32_t> ptr, mem;
-    int na = 0;
-  };
-  std::vector<Part> parts(chunks);
-  auto bound = [&](int c) { return (int)((long long)n * c / chunks); };
-  if (!do_grow) {
-    // the caller's aggregates (ml_graph_aggregates' output: numbered range after range, none across a range boundary) are
-    // split by range, ids local to the range; anything else is merged as ONE range
-    const int na_in = (int)ptr.size() - 1;
-    std::vector<int> first_agg(chunks + 1, na_in);
-    bool split_ok = chunks > 1;
-    if (split_ok) {
-      int c = 0;
-      first_agg[0] = 0;
-      for (int a = 0; a < na_in && split_ok; ++a) {
-        if (ptr[a + 1] <= ptr[a]) { split_ok = false; break; }
-        int lo_m = n, hi_m = -1;
-        for (int m = ptr[a]; m < ptr[a + 1]; ++m) lo_m = std::min(lo_m, (int)mem[m]), hi_m = std::max(hi_m, (int)mem[m]);
-        while (c + 1 < chunks && lo_m >= bound(c + 1)) first_agg[++c] = a;
-        if (lo_m < bound(c) || hi_m >= bound(c + 1)) split_ok = false;
-      }
-      while (c + 1 < chunks) first_agg[++c] = na_in;
-      first_agg[chunks] = na_in;
-    }
-    if (!split_ok) {
-      chunks = 1;
-      parts.resize(1);
-      parts[0].ptr = ptr;
-      parts[0].mem = mem;
-      parts[0].na = na_in;
-    } else {
-      for (int c = 0; c < chunks; ++c) {
-        const int a0 = first_agg[c], a1 = first_agg[c + 1];
-        Part& P = parts[c];
-        P.na = a1 - a0;
-        P.ptr.assign(1, 0);
-        for (int a = a0; a < a1; ++a) P.ptr.push_back(ptr[a + 1] - ptr[a0]);
-        P.mem.assign(mem.begin() + ptr[a0], mem.begin() + ptr[a1]);
-        if (a0 > 0)
-          for (int i = bound(c); i < bound(c + 1); ++i) lab[i] -= a0;
-      }
-    }
-  }
-  const bool timing_ = options().setup_timing > 1;
-  const auto tA = std::chrono::steady_clock::now();
-  std::vector<double> tch(chunks, 0.0);
-  parallel_ranges(chunks, std::min(chunks, setup_threads()), [&](int, int c0, int c1) {
-    for (int c = c0; c < c1; ++c) {
-      const auto t0 = std::chrono::steady_clock::now();
-      Part& P = parts[c];
-      const int lo = bound(c), hi = bound(c + 1);
-      if (do_grow) P.na = grow_range(rowptr, colidx, lo, hi, S, lab, P.ptr, P.mem, parent, pslot);
-      if (cap > 0) P.na = merge_range(rowptr, colidx, lo, hi, S, cap, lab, P.ptr, P.mem, parent, pslot);
-      tch[c] = 1e3 * std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-    }
-  });
-  const auto tB = std::chrono::steady_clock::now();
-  // the ranges' aggregates one after the other
-  std::vector<int> agg_off(chunks + 1, 0);
-  std::vector<size_t> mem_off(chunks + 1, 0);
-  for (int c = 0; c < chunks; ++c) agg_off[c + 1] = agg_off[c] + parts[c].na, mem_off[c + 1] = mem_off[c] + parts[c].mem.size();
-  const int na = agg_off[chunks];
-  mem.resize(mem_off[chunks]);
-  ptr.assign((size_t)na + 1, 0);
-  parallel_ranges(chunks, std::min(chunks, setup_threads()), [&](int, int c0, int c1) {
-    for (int c = c0; c < c1; ++c) {
-      const Part& P = parts[c];
-      if (agg_off[c] > 0)
-        for (int i = bound(c); i < bound(c + 1); ++i) lab[i] += agg_off[c];
-      for (int a = 0; a < P.na; ++a) ptr[(size_t)agg_off[c] + a + 1] = (int32_t)(mem_off[c] + P.ptr[a + 1]);
-      if (!P.mem.empty()) std::memcpy(mem.data() + mem_off[c], P.mem.data(), sizeof(int32_t) * P.mem.size());
-    }
-  });
-  if (timing_) {
-    std::fprintf(stderr, "dpgo_hip: grow / merge (%d ranges): parallel section %.3f ms, join %.3f ms; per range:", chunks,
-                 1e3 * std::chrono::duration<double>(tB - tA).count(),
-                 1e3 * std::chrono::duration<double>(std::chrono::steady_clock::now() - tB).count());
-    for (double t : tch) std::fprintf(stderr, " %.3f", t);
-    std::fprintf(stderr, "\n");
-  }
-  return na;
-}
-int ml_graph_aggregates(const std::vector<int32_t>& rowptr, const std::vector<int32_t>& colidx, int n, int S,
-                        std::vector<int32_t>& lab, std::vector<int32_t>& ptr, std::vector<int32_t>& mem,
-                        std::vector<int32_t>& parent, std::vector<int32_t>& pslot) {
-  return ml_grow_and_merge(rowptr, colidx, n, S, 0, true, lab, ptr, mem, parent, pslot, ml_growth_chunks(n));
-}
-int ml_merge_small_aggregates(const std::vector<int32_t>& rowptr, const std::vector<int32_t>& colidx, int n, int S, int cap,
-                              std::vector<int32_t>& lab, std::vector<int32_t>& ptr, std::vector<int32_t>& mem,
-                              std::vector<int32_t>& parent, std::vector<int32_t>& pslot) {
-  return ml_grow_and_merge(rowptr, colidx, n, S, cap, false, lab, ptr, mem, parent, pslot, ml_growth_chunks(n));
-}
-
-// Host threads of the symbolic set-up (DPGO_SETUP_THREADS; the results do not depend on the count: every parallel section
-// below works on disjoint row ranges and is joined in range order).
-int setup_threads() {
-  const int want = options().setup_threads;
-  if (want > 0) return std::min(want, 64);
-  const unsigned hw = std::thread::hardware_concurrency();
-  return (int)std::max(1u, std::min(8u, hw ? hw : 1u));
-}
-// fn(chunk, begin, end) over `chunks` contiguous ranges of [0, n) on the process's worker threads (TaskPool, host.h)
-template <class F>
-void parallel_ranges(int n, int chunks, F&& fn) {
-  chunks = std::max(1, std::min(chunks, n > 0 ? n : 1));
-  TaskPool::get().run(chunks, [&](int c) {
-    fn(c, (int)((long long)n * c / chunks), (int)((long long)n * (c + 1) / chunks));
-  }, setup_threads());
-}
-// rows [lo, hi) of a row-wise pattern built by `row(i, out)` (appends row i's sorted columns) into per-range pieces, joined
-// in range order: rowptr / colidx identical to the serial loop
-template <class F>
-void pattern_by_ranges(int n, int threads, int grain, size_t reserve_hint, F&& row, std::vector<int32_t>& rowptr_out,
-                       std::vector<int32_t>& col_out) {
-  const int chunks = std::max(1, std::min(threads, n / grain + 1));
-  std::vector<std::vector<int32_t>> cols(chunks), cnt(chunks);
-  parallel_ranges(n, chunks, [&](int c, int lo, int hi) {
-    auto& cc = cols[c];
-    auto& nn = cnt[c];
-    cc.reserve(reserve_hint / chunks + 16);
-    nn.resize(hi - lo);
-    for (int i = lo; i < hi; ++i) {
-      const size_t first = cc.size();
-      row(c, i, cc);
-      nn[i - lo] = (int32_t)(cc.size() - first);
-    }
-  });
-  rowptr_out.assign(n + 1, 0);
-  size_t total = 0;
-  for (auto& cc : cols) total += cc.size();
-  col_out.resize(total);
-  std::vector<size_t> base(chunks + 1, 0);
-  for (int c = 0; c < chunks; ++c) base[c + 1] = base[c] + cols[c].size();
-  parallel_ranges(chunks, chunks, [&](int, int c0, int c1) {
-    for (int c = c0; c < c1; ++c) {
-      const int lo = (int)((long long)n * c / chunks);
-      if (!cols[c].empty()) std::memcpy(col_out.data() + base[c], cols[c].data(), sizeof(int32_t) * cols[c].size());
-      size_t at = base[c];
-      for (size_t k = 0; k < cnt[c].size(); ++k) {
-        at += cnt[c][k];
-        rowptr_out[lo + k + 1] = (int32_t)at;
-      }
-    }
-  });
-}
-
-// Pattern of A P for labelled aggregates: row i holds the sorted, distinct labels of its block columns.  (Inserting into
-// the sorted row instead of sort + unique was measured: no gain, the labels' gather is what it costs.)  Row ranges in parallel.
-void ml_ap_pattern(const std::vector<int32_t>& rowptr, const std::vector<int32_t>& colidx, const std::vector<int32_t>& lab,
-                   int n, std::vector<int32_t>& arow, std::vector<int32_t>& acol) {
-  pattern_by_ranges(n, setup_threads(), 1024, colidx.size(), [&](int, int i, std::vector<int32_t>& out) {
-    const size_t first = out.size();
-    for (int t = rowptr[i]; t < rowptr[i + 1]; ++t) out.push_back(lab[colidx[t]]);
-    std::sort(out.begin() + first, out.end());
-    out.erase(std::unique(out.begin() + first, out.end()), out.end());
-  }, arow, acol);
-}
-
-// Runs of equal labels inside chunks of G consecutive poses (what one wave of the level-0 kernels adds up before it
-// writes): seg_info[first pose of a run] = 32 * slot + length (-1 elsewhere), the slots ordered by aggregate and, inside
-// an aggregate, by pose (a counting sort over the runs), seg_ptr = the aggregates' slot ranges.  Returns the run count.
-int ml_run_table(const std::vector<int32_t>& lab, int n, int na, int G, std::vector<int32_t>& seg_info,
-                 std::vector<int32_t>& seg_ptr) {
-  seg_info.assign(n, -1);
-  seg_ptr.assign(na + 1, 0);
-  int nruns = 0;
-  for (int i = 0; i < n;) {
-    int j = i + 1;
-    while (j < n && j % G != 0 && lab[j] == lab[i]) ++j;
-    seg_info[i] = j - i;  // (length for now)
-    seg_ptr[lab[i] + 1] += 1;
-    ++nruns;
-    i = j;
-  }
-  for (int a = 0; a < na; ++a) seg_ptr[a + 1] += seg_ptr[a];
-  std::vector<int32_t> next(seg_ptr.begin(), seg_ptr.end() - 1);
-  for (int i = 0; i < n;) {
-    const int len = seg_info[i];
-    seg_info[i] = len + 32 * next[lab[i]]++;
-    i += len;
-  }
-  return nruns;
-}
-
+// Symbolic setup: level sizes, block patterns of the Galerkin operators, buffers.  The aggregates, patterns and tables are
+// aggregation.h's (plain C++ over index vectors); this function decodes the shape, sizes the buffers, starts the jobs that
+// overlap, calls those functions and uploads what they return.
 // ks_in: aggregate sizes per coarsening; {-S}: two levels, graph aggregates of at most S poses; {-S, -cap}: the same with
-// the fragments of the greedy growth merged up to `cap` poses (ml_merge_small_aggregates).  perm_tile > 0 (graph
-// aggregates): also build the (aggregate, slot) -> pose table of the additive preconditioner's persistent layout with
-// that many slots per aggregate.
+// the fragments of the greedy growth merged up to `cap` poses (HierarchySpec).  perm_tile > 0 (graph aggregates): also
+// build the (aggregate, slot) -> pose table of the additive preconditioner's persistent layout with that many slots per
+// aggregate.
 int ml_symbolic_setup(dpgo_problem_s* p, const std::vector<int>& ks_in, int perm_tile) {
   // DPGO_SETUP_TIMING=1: host section times on stderr (where the once-per-pattern cost of the hierarchy goes)
   const bool timing = options().setup_timing != 0;
@@ -455,31 +99,23 @@ int ml_symbolic_setup(dpgo_problem_s* p, const std::vector<int>& ks_in, int perm
   };
   ml_free(p);
   lap("previous hierarchy freed");
-  if ((int)p->h_rowptr.size() != p->n + 1) return fail(DPGO_ERR_STATE, "multilevel: Q's block pattern is not set");
+  if (!p->has_pattern()) return fail(DPGO_ERR_STATE, "multilevel: Q's block pattern is not set");
+  HierarchySpec spec;
+  std::string why;
+  if (!spec.decode(ks_in, &why)) return fail(DPGO_ERR_INVALID, "multilevel: " + why);
+  const std::vector<int>& ks = spec.ks;
   const int b = p->b, bb = b * b;
   const size_t nt = p->T;  // doubles per node
-  std::vector<int32_t> rowptr = p->h_rowptr, colidx = p->h_colidx;
+  Pattern P = p->h_pattern;  // the current level's operator; every coarsening replaces it by the next level's
   int cur = p->n;
-  // a single negative entry -S: two levels, graph aggregates of at most S poses; two negative entries: merged up to -ks[1]
-  const bool merged = ks_in.size() == 2 && ks_in[0] < 0 && ks_in[1] < 0;
-  const bool graph = (ks_in.size() == 1 && ks_in[0] < 0) || merged;
-  std::vector<int> ks = ks_in;
-  if (merged) ks.pop_back();
-  if (graph) ks[0] = -ks_in[0];
-  const int merge_cap = merged ? -ks_in[1] : 0;
-  if (merged && merge_cap < ks[0]) return fail(DPGO_ERR_INVALID, "multilevel: the merge bound is at least the growth size");
-  for (int k : ks)
-    if (k < 0) return fail(DPGO_ERR_INVALID, "multilevel: graph aggregates (a negative size) make a two-level hierarchy");
   p->ml.resize(ks.size() + 1);
   for (size_t l = 0; l <= ks.size(); ++l) {
     auto& L = p->ml[l];
     L.n = cur;
     L.split = (l == 0) ? p->split : ml_level_split(cur);
     L.k = (l < ks.size()) ? ks[l] : 0;
-    if (l == 0 && graph) {
-      if (L.k < 2) return fail(DPGO_ERR_INVALID, "multilevel: graph aggregates hold at least 2 poses");
-      std::vector<int32_t> lab, ptr, mem, parent, pslot;
-      int na;
+    if (l == 0 && spec.graph) {
+      Aggregates agg;
       // the level-0 buffers whose sizes are known up front are allocated by a helper thread while the aggregates grow
       int alloc_rc = DPGO_OK;
       std::string alloc_msg;  // (the helper's error text is thread-local to the helper)
@@ -497,82 +133,57 @@ int ml_symbolic_setup(dpgo_problem_s* p, const std::vector<int>& ks_in, int perm
         }();
         if (alloc_rc != DPGO_OK) alloc_msg = g_err;
       }, nthreads)};
-      if (p->add_plan_known && p->add_agg.S == L.k && p->add_agg.cap == merge_cap && (int)p->add_agg.lab.size() == cur) {
-        const auto& A = p->add_agg;  // (the additive plan of this pattern was found with exactly these aggregates)
-        lab = A.lab, ptr = A.ptr, mem = A.mem, parent = A.parent, pslot = A.pslot;
-        na = (int)ptr.size() - 1;
+      if (p->add_plan_known && p->add_agg.S == L.k && p->add_agg.cap == spec.cap && (int)p->add_agg.agg.lab.size() == cur) {
+        agg = p->add_agg.agg;  // (the additive plan of this pattern was found with exactly these aggregates)
       } else {
-        na = ml_graph_aggregates(rowptr, colidx, cur, L.k, lab, ptr, mem, parent, pslot);
+        agg = grow_aggregates(P, L.k, ml_growth_chunks(cur));
         lap("greedy growth of the aggregates");
-        if (merge_cap) na = ml_merge_small_aggregates(rowptr, colidx, cur, L.k, merge_cap, lab, ptr, mem, parent, pslot);
+        if (spec.cap) merge_small_aggregates(P, L.k, spec.cap, ml_growth_chunks(cur), agg);
         lap("merge of the growth's fragments");
       }
+      const int na = agg.count();
       L.graph = true;
-      L.merge_cap = merge_cap;
+      L.merge_cap = spec.cap;
       // the patterns that follow from the labels -- A P (rows in parallel) and the dense level's operator (aggregates in
       // parallel) -- are built by worker threads while this one uploads the labels and builds the run and tile tables
-      std::vector<int32_t> arow, acol, crow, ccol;
+      Pattern AP, C;
       JobGuard pattern_job{TaskPool::get().submit(2, [&](int which) {
-        if (which == 0) {  // pattern of A P: the aggregates every row's block columns fall into
-          ml_ap_pattern(rowptr, colidx, lab, cur, arow, acol);
-          return;
-        }
-        // pattern of the dense level's operator: the aggregates of the block columns of every member's row
-        const int chunks = std::max(1, std::min(std::max(1, nthreads / 2), na / 16 + 1));
-        std::vector<std::vector<int32_t>> marks(chunks);
-        pattern_by_ranges(na, chunks, 16, colidx.size() / 8, [&](int c, int a, std::vector<int32_t>& out) {
-          auto& mark = marks[c];
-          if (mark.empty()) mark.assign(na, -1);
-          const size_t first = out.size();
-          for (int m = ptr[a]; m < ptr[a + 1]; ++m) {
-            const int i = mem[m];
-            for (int t = rowptr[i]; t < rowptr[i + 1]; ++t) {
-              const int cl = lab[colidx[t]];
-              if (mark[cl] != a) {
-                mark[cl] = a;
-                out.push_back(cl);
-              }
-            }
-          }
-          std::sort(out.begin() + first, out.end());
-        }, crow, ccol);
+        if (which == 0)
+          AP = ap_pattern(P, agg);
+        else
+          C = coarse_pattern(P, agg, nthreads / 2);
       }, nthreads)};
-      CHK(upload(L.lab, lab.data(), lab.size(), p->stream));
-      CHK(upload(L.agg_ptr, ptr.data(), ptr.size(), p->stream));
-      CHK(upload(L.agg_mem, mem.data(), mem.size(), p->stream));
-      CHK(upload(L.parent, parent.data(), parent.size(), p->stream));
-      CHK(upload(L.pslot, pslot.data(), pslot.size(), p->stream));
-      std::vector<int32_t> mpos(cur);
-      for (int m = 0; m < cur; ++m) mpos[mem[m]] = m;
+      CHK(upload(L.lab, agg.lab.data(), agg.lab.size(), p->stream));
+      CHK(upload(L.agg_ptr, agg.ptr.data(), agg.ptr.size(), p->stream));
+      CHK(upload(L.agg_mem, agg.mem.data(), agg.mem.size(), p->stream));
+      CHK(upload(L.parent, agg.parent.data(), agg.parent.size(), p->stream));
+      CHK(upload(L.pslot, agg.pslot.data(), agg.pslot.size(), p->stream));
+      const std::vector<int32_t> mpos = member_positions(agg);
       CHK(upload(L.mem_pos, mpos.data(), mpos.size(), p->stream));
       lap("labels, members, trees uploaded");
-      std::vector<int32_t> seg_info, seg_ptr;
-      L.nseg = ml_run_table(lab, cur, na, 64 / (b * L.split), seg_info, seg_ptr);
+      std::vector<int32_t> seg_info, seg_ptr, tperm;
+      L.nseg = run_table(agg.lab, na, 64 / (b * L.split), seg_info, seg_ptr);
       CHK(upload(L.seg_info, seg_info.data(), seg_info.size(), p->stream));
       CHK(upload(L.seg_ptr, seg_ptr.data(), seg_ptr.size(), p->stream));
-      std::vector<int32_t> tperm;
       // the layout of the additive preconditioner's persistent kernel: aggregate = workgroup tile of `perm_tile` slots
-      if (!perm_tile && !merge_cap && L.k == additive_tile(p)) perm_tile = L.k;
+      if (!perm_tile && !spec.cap && L.k == additive_tile(p)) perm_tile = L.k;
       if (perm_tile) {
-        if (std::max(L.k, merge_cap) > perm_tile) return fail(DPGO_ERR_INVALID, "multilevel: aggregates larger than the tile");
-        tperm.assign((size_t)na * perm_tile, -1);
-        for (int a = 0; a < na; ++a)
-          for (int m = ptr[a]; m < ptr[a + 1]; ++m) tperm[(size_t)a * perm_tile + (m - ptr[a])] = mem[m];
+        if (std::max(L.k, spec.cap) > perm_tile) return fail(DPGO_ERR_INVALID, "multilevel: aggregates larger than the tile");
+        tperm = tile_table(agg, perm_tile);
         CHK(upload(L.tile_perm, tperm.data(), tperm.size(), p->stream));
         L.perm_tile = perm_tile;
       }
       lap("run table, tile table");
       TaskPool::get().wait(pattern_job.job);
       lap("patterns of A P and of the dense level joined");
-      CHK(upload_bsr(L.AP, cur, na, (int)acol.size(), b, arow.data(), acol.data(), nullptr, p->stream));
+      CHK(upload_bsr(L.AP, cur, na, (int)AP.colidx.size(), b, AP.rowptr.data(), AP.colidx.data(), nullptr, p->stream));
       lap("A P allocated, pattern uploaded");
       TaskPool::get().wait(alloc_job.job);
       if (alloc_rc != DPGO_OK) return fail(alloc_rc, "level-0 buffers: " + alloc_msg);
       lap("level-0 vectors joined");
       HIPC(hipStreamSynchronize(p->stream));  // the host vectors go out of scope
       lap("stream synchronised");
-      rowptr.swap(crow);
-      colidx.swap(ccol);
+      P = std::move(C);
       cur = na;
       continue;
     }
@@ -582,54 +193,26 @@ int ml_symbolic_setup(dpgo_problem_s* p, const std::vector<int>& ks_in, int perm
                                           std::to_string(ml_tile(b, L.split)) + " nodes)");
     }
     if (l > 0) {
-      CHK(upload_bsr(L.A, cur, cur, (int)colidx.size(), b, rowptr.data(), colidx.data(), nullptr, p->stream));
-      std::vector<int32_t> srow(colidx.size());
-      for (int i = 0; i < cur; ++i)
-        for (int t = rowptr[i]; t < rowptr[i + 1]; ++t) srow[t] = i;
+      CHK(upload_bsr(L.A, cur, cur, (int)P.colidx.size(), b, P.rowptr.data(), P.colidx.data(), nullptr, p->stream));
+      const std::vector<int32_t> srow = slot_rows(P);
       CHK(upload(L.slot_row, srow.data(), srow.size(), p->stream));
       HIPC(hipStreamSynchronize(p->stream));  // srow goes out of scope at the end of this block
       CHK(L.r.alloc(nt * cur));
       if (!L.k) CHK(L.x.alloc(nt * cur));  // dense level: its solution, read by the level above
     }
-    if (l == 0 && L.k) {  // pattern of A P: the aggregates the block columns of every row fall into
-      const int k = L.k;
-      std::vector<int32_t> arow(cur + 1, 0), acol;
-      acol.reserve(colidx.size());
-      for (int i = 0; i < cur; ++i) {
-        const size_t first = acol.size();
-        for (int t = rowptr[i]; t < rowptr[i + 1]; ++t) acol.push_back(colidx[t] / k);
-        std::sort(acol.begin() + first, acol.end());
-        acol.erase(std::unique(acol.begin() + first, acol.end()), acol.end());
-        arow[i + 1] = (int32_t)acol.size();
+    if (L.k) {  // index runs of k nodes: the same two patterns from their labels
+      const Aggregates runs = Aggregates::index_runs(cur, L.k);
+      if (l == 0) {
+        const Pattern AP = ap_pattern(P, runs);
+        CHK(upload_bsr(L.AP, cur, runs.count(), (int)AP.colidx.size(), b, AP.rowptr.data(), AP.colidx.data(), nullptr, p->stream));
+        CHK(L.res1.alloc(nt * cur));
       }
-      CHK(upload_bsr(L.AP, cur, (cur + k - 1) / k, (int)acol.size(), b, arow.data(), acol.data(), nullptr, p->stream));
-      CHK(L.res1.alloc(nt * cur));
-    }
-    if (L.k) {
       if (l > 0) CHK(L.dinv.alloc((size_t)cur * bb));
       CHK(L.Pb.alloc((size_t)cur * bb));
       CHK(L.x1.alloc(nt * cur));
       CHK(L.x.alloc(nt * cur));
-      // pattern of the next level: block columns j / k of the rows of every aggregate
-      const int k = L.k, nc = (cur + k - 1) / k;
-      std::vector<int32_t> crow(nc + 1, 0), ccol;
-      std::vector<int32_t> mark(nc, -1);
-      for (int a = 0; a < nc; ++a) {
-        const size_t first = ccol.size();
-        for (int i = a * k; i < std::min(cur, a * k + k); ++i)
-          for (int t = rowptr[i]; t < rowptr[i + 1]; ++t) {
-            const int c = colidx[t] / k;
-            if (mark[c] != a) {
-              mark[c] = a;
-              ccol.push_back(c);
-            }
-          }
-        std::sort(ccol.begin() + first, ccol.end());
-        crow[a + 1] = (int32_t)ccol.size();
-      }
-      rowptr.swap(crow);
-      colidx.swap(ccol);
-      cur = nc;
+      P = coarse_pattern(P, runs, setup_threads());
+      cur = runs.count();
     }
   }
   const int N = cur * b;
@@ -641,15 +224,9 @@ int ml_symbolic_setup(dpgo_problem_s* p, const std::vector<int>& ks_in, int perm
   CHK(p->dense.inv32.alloc((size_t)p->dense.lda * (p->dense.lda + 8)));
   if (p->ml.size() == 2) {  // two levels: the packed lower triangle and the bookkeeping of k_dense_sym_apply
     const int nT = p->dense.lda / kNB;
-    int chunk = kDenseChunk;
-    if (options().dense_chunk > 0) chunk = options().dense_chunk;  // tuning knob
     std::vector<DenseChunk> chunks;
-    std::vector<int> first(nT + 1, 0);
-    for (int I = 0; I < nT; ++I) {
-      first[I] = (int)chunks.size();
-      for (int J0 = 0; J0 <= I; J0 += chunk) chunks.push_back(DenseChunk{I, J0, std::min(chunk, I + 1 - J0), 0});
-    }
-    first[nT] = (int)chunks.size();
+    std::vector<int> first;
+    dense_chunk_table(nT, options().dense_chunk > 0 ? options().dense_chunk : kDenseChunk, chunks, first);  // (tuning knob)
     p->dense.nchunks = (int)chunks.size();
     CHK(upload(p->dense.chunks, chunks.data(), chunks.size(), p->stream));
     CHK(upload(p->dense.chunk_first, first.data(), first.size(), p->stream));
@@ -795,20 +372,25 @@ const dpgo_problem_s::AddPlan& additive_plan(dpgo_problem_s* p) {
   if (p->add_plan_known) return p->add_plan;
   p->add_plan = dpgo_problem_s::AddPlan();
   p->add_plan_known = true;
-  p->add_agg = dpgo_problem_s::AggCache();
-  if (p->split != 4 || (int)p->h_rowptr.size() != p->n + 1) return p->add_plan;
-  const int P4 = ml_tile(p->b, 4), P1 = ml_tile(p->b, 1), n = p->n;
+  auto& A = p->add_agg;
+  A = dpgo_problem_s::AggCache();
+  if (p->split != 4 || !p->has_pattern()) return p->add_plan;
+  const int P4 = ml_tile(p->b, 4), P1 = ml_tile(p->b, 1), P2 = 2 * P1, n = p->n;
   const bool graph_ok = options().ml_graph != 0;
+  const Pattern& Q = p->h_pattern;
+  const int chunks = ml_growth_chunks(n);
+  // the plan of the graph aggregates in A (cases 1, 2, 4)
+  auto found = [&](int split, int tile, int na) -> const dpgo_problem_s::AddPlan& {
+    p->add_plan = dpgo_problem_s::AddPlan{split, tile, A.S, A.cap, na, true};
+    return p->add_plan;
+  };
+  // the search for at most `want` merged aggregates starts where nine tenths of them hold the block (256: ceil(n / 230))
+  auto first_size = [&](int want) { return std::max(8, (n + (want * 9) / 10 - 1) / ((want * 9) / 10)); };
   if (graph_ok) {
-    auto& A = p->add_agg;
-    auto &lab = A.lab, &ptr = A.ptr, &mem = A.mem, &parent = A.parent, &pslot = A.pslot;
     if ((long long)n <= (long long)kPersistMax * P4) {
-      const int na = ml_graph_aggregates(p->h_rowptr, p->h_colidx, n, P4, lab, ptr, mem, parent, pslot);
-      if (na <= kPersistMax) {
-        p->add_plan = dpgo_problem_s::AddPlan{4, P4, P4, 0, na, true};
-        A.S = P4, A.cap = 0;
-        return p->add_plan;
-      }
+      A.agg = grow_aggregates(Q, P4, chunks);
+      A.S = P4, A.cap = 0;
+      if (A.agg.count() <= kPersistMax) return found(4, P4, A.agg.count());
     }
     if ((long long)n <= (long long)kPersistMax * P1) {
       // A handle that is solved next to other handles of the device (dpgo_optimize_device_many: persist_share > 1 when the
@@ -816,50 +398,22 @@ const dpgo_problem_s::AddPlan& additive_plan(dpgo_problem_s* p) {
       // so two such solves run side by side instead of taking turns; the product count is a weak function of the aggregate
       // size, the time of an iteration is not a function of how full the tiles are.
       const int want = (p->persist_share > 1 && (long long)n * 10 <= (long long)(kPersistMax / 2) * P1 * 8) ? kPersistMax / 2 : kPersistMax;
-      for (int S = std::max(8, (n + (want * 9) / 10 - 1) / ((want * 9) / 10)); S <= P1; S += std::max(2, S / 8)) {
-        const int cap = std::min(P1, S + S / 2);
-        ml_graph_aggregates(p->h_rowptr, p->h_colidx, n, S, lab, ptr, mem, parent, pslot);
-        const int na = ml_merge_small_aggregates(p->h_rowptr, p->h_colidx, n, S, cap, lab, ptr, mem, parent, pslot);
-        if (na <= want) {
-          p->add_plan = dpgo_problem_s::AddPlan{1, P1, S, cap, na, true};
-          A.S = S, A.cap = cap;
-          return p->add_plan;
-        }
-      }
-      if (want < kPersistMax) {  // (no growth size reaches half the chip: the whole-chip plan)
-        for (int S = std::max(8, (n + 229) / 230); S <= P1; S += std::max(2, S / 8)) {
-          const int cap = std::min(P1, S + S / 2);
-          ml_graph_aggregates(p->h_rowptr, p->h_colidx, n, S, lab, ptr, mem, parent, pslot);
-          const int na = ml_merge_small_aggregates(p->h_rowptr, p->h_colidx, n, S, cap, lab, ptr, mem, parent, pslot);
-          if (na <= kPersistMax) {
-            p->add_plan = dpgo_problem_s::AddPlan{1, P1, S, cap, na, true};
-            A.S = S, A.cap = cap;
-            return p->add_plan;
-          }
-        }
-      }
+      int na = search_merged_aggregates(Q, first_size(want), P1, want, chunks, A.agg, &A.S, &A.cap);
+      if (!na && want < kPersistMax)  // (no growth size reaches half the chip: the whole-chip plan)
+        na = search_merged_aggregates(Q, first_size(kPersistMax), P1, kPersistMax, chunks, A.agg, &A.S, &A.cap);
+      if (na) return found(1, P1, na);
     }
-    p->add_agg = dpgo_problem_s::AggCache();
+    A = dpgo_problem_s::AggCache();
   }
   if ((n + P4 - 1) / P4 <= kPersistMax)
     p->add_plan = dpgo_problem_s::AddPlan{4, P4, P4, 0, (n + P4 - 1) / P4, false};
   else if ((n + P1 - 1) / P1 <= kPersistMax)
     p->add_plan = dpgo_problem_s::AddPlan{1, P1, P1, 0, (n + P1 - 1) / P1, false};
-  const int P2 = 2 * P1;
   if (!p->add_plan.split && graph_ok && additive_tiles(p) == 2 && (long long)n <= (long long)kPersistMax * P2) {
-    auto& A = p->add_agg;
-    for (int S = std::max(8, (n + 229) / 230); S <= P2; S += std::max(2, S / 8)) {
-      const int cap = std::min(P2, S + S / 2);
-      ml_graph_aggregates(p->h_rowptr, p->h_colidx, n, S, A.lab, A.ptr, A.mem, A.parent, A.pslot);
-      const int na = ml_merge_small_aggregates(p->h_rowptr, p->h_colidx, n, S, cap, A.lab, A.ptr, A.mem, A.parent, A.pslot);
-      if (na <= kPersistMax) {
-        if (!additive_lds_fits(p, 1, 2, na)) break;  // (static + coarse-row LDS beyond the CU's: no plan)
-        p->add_plan = dpgo_problem_s::AddPlan{1, P2, S, cap, na, true};
-        A.S = S, A.cap = cap;
-        return p->add_plan;
-      }
-    }
-    p->add_agg = dpgo_problem_s::AggCache();
+    const int na = search_merged_aggregates(Q, first_size(kPersistMax), P2, kPersistMax, chunks, A.agg, &A.S, &A.cap);
+    // (static + coarse-row LDS beyond the CU's: no plan)
+    if (na && additive_lds_fits(p, 1, 2, na)) return found(1, P2, na);
+    A = dpgo_problem_s::AggCache();
   }
   return p->add_plan;
 }
@@ -1160,14 +714,13 @@ int dpgo_multilevel_default_ks(int n, int d, int* ks, int* nks) {
 int dpgo_multilevel_graph_aggregates(int n, const int32_t* rowptr, const int32_t* colidx, int max_size, int32_t* label,
                                      int32_t* parent, int* n_aggregates) {
   if (n <= 0 || !rowptr || !colidx || max_size < 2 || !label) return fail(DPGO_ERR_INVALID, "bad arguments");
-  const std::vector<int32_t> rp(rowptr, rowptr + n + 1), ci(colidx, colidx + rowptr[n]);
-  for (int32_t c : ci)
+  const Pattern P{{rowptr, rowptr + n + 1}, {colidx, colidx + rowptr[n]}};
+  for (int32_t c : P.colidx)
     if (c < 0 || c >= n) return fail(DPGO_ERR_INVALID, "block column out of range");
-  std::vector<int32_t> lab, ptr, mem, par, pslot;
-  const int na = ml_graph_aggregates(rp, ci, n, max_size, lab, ptr, mem, par, pslot);
-  std::copy(lab.begin(), lab.end(), label);
-  if (parent) std::copy(par.begin(), par.end(), parent);
-  if (n_aggregates) *n_aggregates = na;
+  const Aggregates agg = grow_aggregates(P, max_size, ml_growth_chunks(n));
+  std::copy(agg.lab.begin(), agg.lab.end(), label);
+  if (parent) std::copy(agg.parent.begin(), agg.parent.end(), parent);
+  if (n_aggregates) *n_aggregates = agg.count();
   return DPGO_OK;
 }
 
@@ -1175,14 +728,13 @@ int dpgo_multilevel_graph_aggregates(int n, const int32_t* rowptr, const int32_t
 int dpgo_multilevel_merged_aggregates(int n, const int32_t* rowptr, const int32_t* colidx, int max_size, int merge_cap,
                                       int32_t* label, int32_t* parent, int* n_aggregates) {
   if (n <= 0 || !rowptr || !colidx || max_size < 2 || merge_cap < max_size || !label) return fail(DPGO_ERR_INVALID, "bad arguments");
-  const std::vector<int32_t> rp(rowptr, rowptr + n + 1), ci(colidx, colidx + rowptr[n]);
-  for (int32_t c : ci)
+  const Pattern P{{rowptr, rowptr + n + 1}, {colidx, colidx + rowptr[n]}};
+  for (int32_t c : P.colidx)
     if (c < 0 || c >= n) return fail(DPGO_ERR_INVALID, "block column out of range");
-  std::vector<int32_t> lab, ptr, mem, par, pslot;
-  ml_graph_aggregates(rp, ci, n, max_size, lab, ptr, mem, par, pslot);
-  const int na = ml_merge_small_aggregates(rp, ci, n, max_size, merge_cap, lab, ptr, mem, par, pslot);
-  std::copy(lab.begin(), lab.end(), label);
-  if (parent) std::copy(par.begin(), par.end(), parent);
+  Aggregates agg = grow_aggregates(P, max_size, ml_growth_chunks(n));
+  const int na = merge_small_aggregates(P, max_size, merge_cap, ml_growth_chunks(n), agg);
+  std::copy(agg.lab.begin(), agg.lab.end(), label);
+  if (parent) std::copy(agg.parent.begin(), agg.parent.end(), parent);
   if (n_aggregates) *n_aggregates = na;
   return DPGO_OK;
 }
@@ -1191,7 +743,7 @@ int dpgo_multilevel_merged_aggregates(int n, const int32_t* rowptr, const int32_
 int dpgo_problem_additive_plan(dpgo_problem_t p, int* lane_groups, int* tile, int* growth, int* merge_cap, int* aggregates,
                                int* graph) {
   if (!p) return fail(DPGO_ERR_INVALID, "null handle");
-  if ((int)p->h_rowptr.size() != p->n + 1) return fail(DPGO_ERR_STATE, "Q's block pattern is not set");
+  if (!p->has_pattern()) return fail(DPGO_ERR_STATE, "Q's block pattern is not set");
   const auto& plan = additive_plan(p);
   if (lane_groups) *lane_groups = plan.split;
   if (tile) *tile = plan.tile;

@@ -84,9 +84,9 @@ int sym_symbolic_setup(dpgo_problem_s* p) {
   auto& S = p->sym;
   S.symbolic = true;
   const int n = p->n;
-  if ((int)p->h_rowptr.size() != n + 1) return DPGO_OK;
-  const auto& rp = p->h_rowptr;
-  const auto& ci = p->h_colidx;
+  if (!p->has_pattern()) return DPGO_OK;
+  const auto& rp = p->h_pattern.rowptr;
+  const auto& ci = p->h_pattern.colidx;
   std::vector<int32_t> urow(n + 1, 0), lrow(n + 1, 0), ucol, usrc, lcol, lslot, lsrc;
   ucol.reserve(ci.size() / 2 + n);
   for (int i = 0; i < n; ++i) {
@@ -563,12 +563,13 @@ int dpgo_problem_set_Q_bsr(dpgo_problem_t p, int nnzb, const int32_t* rowptr, co
   // registered re-weightable edges index into the old pattern: drop them (the caller re-registers)
   if (p->gnc.e_w) p->gnc = dpgo_problem_s::GncEdges();
   CHK(upload_bsr(p->Q, p->n, p->n, nnzb, p->b, rowptr, colidx, vals, p->stream));
-  const bool same_pattern = (int)p->h_rowptr.size() == p->n + 1 && (int)p->h_colidx.size() == nnzb &&
-                            std::equal(rowptr, rowptr + p->n + 1, p->h_rowptr.begin()) &&
-                            std::equal(colidx, colidx + nnzb, p->h_colidx.begin());
+  Pattern& hp = p->h_pattern;
+  const bool same_pattern = p->has_pattern() && (int)hp.colidx.size() == nnzb &&
+                            std::equal(rowptr, rowptr + p->n + 1, hp.rowptr.begin()) &&
+                            std::equal(colidx, colidx + nnzb, hp.colidx.begin());
   if (!same_pattern) {
-    p->h_rowptr.assign(rowptr, rowptr + p->n + 1);
-    p->h_colidx.assign(colidx, colidx + nnzb);
+    hp.rowptr.assign(rowptr, rowptr + p->n + 1);
+    hp.colidx.assign(colidx, colidx + nnzb);
     p->add_plan_known = false;
     if (p->ml_user_ks && p->ml_symbolic) {  // keep the caller's aggregate sizes across a pattern change
       const int perm_tile = p->ml[0].perm_tile;

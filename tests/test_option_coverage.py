@@ -1,4 +1,4 @@
-"""Every library switch that selects a kernel, a storage or a launch geometry (csrc/host.h, DPGO_OPTIONS) is exercised by
+"""Every library switch that selects a kernel, a storage or a launch geometry (csrc/options.h, DPGO_OPTIONS) is exercised by
 some GPU test: a switch added without one fails here, on a machine without a GPU.  Switches that change only timing or
 reporting, or that are covered through another handle of the same choice, are listed below with the reason."""
 import glob
@@ -27,7 +27,7 @@ EXEMPT = {
 
 
 def _options():
-    text = open(os.path.join(ROOT, "dpgo_amd", "csrc", "host.h")).read()
+    text = open(os.path.join(ROOT, "dpgo_amd", "csrc", "options.h")).read()
     block = text[text.index("#define DPGO_OPTIONS(X)"):]
     block = block[:block.index("struct Options")]
     names = re.findall(r'X\(\s*\w+\s*,\s*"(DPGO_\w+)"', block)
