@@ -477,6 +477,11 @@ struct dpgo_problem_s {
   PinBuf<unsigned long long> hflag;  // host-coherent: host-coherent: device-published tCG progress word
   unsigned gen = 0;
   bool saw_rtr_stop = false;  // set from the progress word in just-in-time mode
+  // what the last solve's tCG feed enqueued (dpgo_problem_feed_counters; host counts only): tCG steps (Hessian step + update
+  // [+ cycle]) enqueued, tCG runs started, runs that were fed at least one step, Hessian-vector products executed
+  struct FeedCounts {
+    long long steps = 0, runs = 0, runs_fed = 0, products = 0;
+  } feed;
   // re-weightable edges (GNC): registered, replaced and dropped together (assigning an empty one releases them)
   struct GncEdges {
     int em = 0;

@@ -31,12 +31,19 @@ struct DevState {
 // store).  The host feeds tCG-step kernels just-in-time, a few iterations ahead of `j`, instead of
 // synchronising every few iterations; it is a HINT only -- the device state above is the truth and
 // kernels enqueued after tCG finished exit in their prologue.
-//   [63:32] generation (one per tCG run)   [31:8] tcg_j   [1] rtr_stop   [0] tcg_done
+//   [63:32] generation (one per tCG run)   [31:8] tcg_j   [2] go   [1] rtr_stop   [0] tcg_done
+// go (the "ticket" of iteration tcg_j): every test that could end the run in iteration tcg_j has been passed, so the
+// Hessian step of iteration tcg_j + 1 will execute unless the iteration cap, which the host knows, stops it.  Published by
+// the restriction's stop check (TcgStopCheck, multilevel.h), the last such test of a V-cycle iteration; nothing publishes
+// again before the next Hessian step, whose word carries tcg_j + 1 without the bit.
+constexpr unsigned long long kProgressDone = 1ull, kProgressRtrStop = 2ull, kProgressGo = 4ull;
+__device__ __forceinline__ unsigned long long progress_word(unsigned gen, int tcg_j, unsigned long long bits) {
+  return ((unsigned long long)gen << 32) | ((unsigned long long)((unsigned)tcg_j & 0xFFFFFFu) << 8) | bits;
+}
 __device__ __forceinline__ void publish_progress(unsigned long long* hflag, unsigned gen, const DevState& st) {
   if (hflag) {
-    const unsigned long long w = ((unsigned long long)gen << 32) |
-                                 ((unsigned long long)((unsigned)st.tcg_j & 0xFFFFFFu) << 8) |
-                                 (st.rtr_stop ? 2ull : 0ull) | (st.tcg_done ? 1ull : 0ull);
+    const unsigned long long w =
+        progress_word(gen, st.tcg_j, (st.rtr_stop ? kProgressRtrStop : 0ull) | (st.tcg_done ? kProgressDone : 0ull));
     __hip_atomic_store(hflag, w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
   }
 }

@@ -64,7 +64,8 @@ __global__ __launch_bounds__(kBlock) void k_ml_presmooth(const double* __restric
 // holds it raises tcg_done in the state record the rest of the cycle and the next Hessian-step kernel are gated on and
 // publishes it to the host: the final iteration of a converged tCG run no longer pays for a dense solve and a
 // post-smoothing pass whose result nobody reads, and the host learns one cycle sooner that it can enqueue the outer
-// iteration's launches (what it had already enqueued of the next tCG iteration exits in its prologues, as before).
+// iteration's launches.  When it does not hold, nothing later in the iteration can end the run: the same lane publishes
+// the iteration's go ticket (progress word, common.h), on which the host enqueues the next iteration (solve.hip, the feed).
 struct TcgStopCheck {
   DevState* state = nullptr;  // the record `gate` points to; NULL: no check
   const double* pin = nullptr;
@@ -112,15 +113,16 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(Restrict
       const double norm_r = sqrt(rr_sum[0]), nr0 = st->norm_r0, theta = st->theta, kappa = st->kappa;
       const double pw = (theta == 1.0) ? nr0 : pow(nr0, theta);
       const int j = st->tcg_j;
-      if (j >= st->min_inner && norm_r <= nr0 * (pw < kappa ? pw : kappa)) {
+      const bool met = j >= st->min_inner && norm_r <= nr0 * (pw < kappa ? pw : kappa);
+      if (met) {
         stop.state->tcg_status = (kappa < pw) ? TCG_LCON : TCG_SCON;
         stop.state->tcg_done = 1;
-        if (stop.hflag) {
-          const unsigned g_ = stop.gen ? stop.gen : (unsigned)st->pad0;  // (0: the one in the record, see state_gen)
-          const unsigned long long w = ((unsigned long long)g_ << 32) |
-                                       ((unsigned long long)((unsigned)j & 0xFFFFFFu) << 8) | 1ull;
-          __hip_atomic_store(stop.hflag, w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        }
+      }
+      // (not met: this was the last test that could end the run in iteration j -- the go ticket, common.h)
+      if (stop.hflag) {
+        const unsigned g_ = stop.gen ? stop.gen : (unsigned)st->pad0;  // (0: the one in the record, see state_gen)
+        const unsigned long long w = progress_word(g_, j, met ? kProgressDone : kProgressGo);
+        __hip_atomic_store(stop.hflag, w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
       }
     }
     __syncthreads();  // (t_s is reused by the tiles below)

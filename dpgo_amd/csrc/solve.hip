@@ -397,8 +397,11 @@ int rtr_outer_iteration(dpgo_problem_s* p, const dpgo_ropt_params* prm, const do
     return launch_tcg_update(p, dinv, first);
   };
   CHK(update(1));
+  p->feed.runs += 1;
   const int max_inner = prm->RTR_tCG_iterations;
   auto step = [&](int j) -> int {
+    if (j == 0) p->feed.runs_fed += 1;
+    p->feed.steps += 1;
     CHK(launch_tcg_hess(p, j == 0 ? 1 : 0));
     return update(0);
   };
@@ -426,25 +429,43 @@ int rtr_outer_iteration(dpgo_problem_s* p, const dpgo_ropt_params* prm, const do
     // tried in round 4, the watchdog fires.)
     int kAhead = ml ? 2 : 4;
     if (options().tcg_ahead > 0) kAhead = std::max(2, options().tcg_ahead);  // tuning knob (>= 2, see above)
-    int enq = 0, last_j = -1;
+    // The two-level V-cycle with the restriction's stop check (DPGO_ML_EARLY_STOP, the default) is fed on TICKETS instead:
+    // the device says whether an iteration will run before the host enqueues it.
+    //  * step 0 waits for this run's generation in the word: the opening update's prologue publishes it, with rtr_stop when
+    //    the previous outer iteration met the stop test -- such a run costs its opening launches and nothing else; otherwise
+    //    step 0 is enqueued while the opening cycle runs;
+    //  * step s + 1 waits for the go ticket of iteration s (kProgressGo, common.h), which the restriction of step s publishes
+    //    once its residual test has not held: the rest of that restriction, the aggregate sum, the dense level and the
+    //    post-smoothing are still queued then, so the queue does not run dry, and a run that ends in iteration s has nothing
+    //    of iteration s + 1 behind it.
+    // Every wait is for a launch that is already enqueued and that completes without the host (each publishes the ticket,
+    // tcg_done or rtr_stop), so a wait ends whatever other streams do.  The shrink loop, deeper hierarchies and every other
+    // preconditioner keep the rule above.
+    const bool tickets = ml && !poll_at_end && options().ml_early_stop != 0 && p->ml.size() == 2;
+    int enq = 0;
+    unsigned long long last_w = ~0ull;
     auto t_progress = std::chrono::steady_clock::now();
     while (true) {
       const unsigned long long w = __atomic_load_n(p->hflag.get(), __ATOMIC_ACQUIRE);
+      const bool current = (unsigned)(w >> 32) == p->gen;
       int dev_j = 0;
-      if ((unsigned)(w >> 32) == p->gen) {
+      if (current) {
         dev_j = (int)((w >> 8) & 0xFFFFFFu);
-        if (w & 3ull) {
+        if (w & (kProgressDone | kProgressRtrStop)) {
           done = true;
-          if (w & 2ull) p->saw_rtr_stop = true;
+          if (w & kProgressRtrStop) p->saw_rtr_stop = true;
           break;
         }
       }
       if (enq >= max_inner) break;
-      if (dev_j != last_j) {  // the watchdog measures time WITHOUT progress, not time since the loop started
-        last_j = dev_j;
+      // the watchdog measures time WITHOUT progress (a word of this run that changes), not time since the loop started
+      const unsigned long long w_run = current ? w : 0ull;
+      if (w_run != last_w) {
+        last_w = w_run;
         t_progress = std::chrono::steady_clock::now();
       }
-      if (enq < dev_j + kAhead) {
+      const bool feed = tickets ? (current && (enq == 0 || ((w & kProgressGo) && dev_j >= enq - 1))) : (enq < dev_j + kAhead);
+      if (feed) {
         CHK(step(enq));
         enq += 1;
       } else {
@@ -678,6 +699,8 @@ int one_launch_collect(dpgo_problem_s* p, const SolvePlan& plan, dpgo_ropt_resul
   res->rtr_accepted = h.n_accept;
   res->latest_step_accepted = h.accepted_last;
   res->tcg_iterations = h.n_hess;
+  p->feed = dpgo_problem_s::FeedCounts();  // (nothing is fed: the launch runs the loop itself)
+  p->feed.products = h.n_hess;
   res->precond_used = plan.prm.precond;
   res->spmm_count = 1 + 2 * h.outer_iter + h.n_hess;
   if (plan.is_auto) auto_update(p, &plan.prm, plan.prm.precond, h.n_hess);
@@ -693,6 +716,7 @@ int multi_launch_solve(dpgo_problem_s* p, const SolvePlan& plan, dpgo_ropt_resul
   Counters cnt;
   std::memset(res, 0, sizeof(*res));
   res->tCGStatus = DPGO_TCG_MAXITER;
+  p->feed = dpgo_problem_s::FeedCounts();
   // whether this solve's tCG runs keep their directions (every launch follows it)
   p->dirs_on = false;
   if (prm->method == DPGO_METHOD_RTR) CHK(tcg_dirs_ensure(p, prm->RTR_tCG_iterations));
@@ -780,6 +804,7 @@ int multi_launch_solve(dpgo_problem_s* p, const SolvePlan& plan, dpgo_ropt_resul
     return fail(DPGO_ERR_INVALID, "unknown method");
   }
   res->tcg_iterations = n_hess_total;
+  p->feed.products = n_hess_total;
   res->precond_used = (prm->precond == DPGO_PRECOND_ADDITIVE && cnt.vcycle_for_additive) ? DPGO_PRECOND_MULTILEVEL : prm->precond;
   if (plan.is_auto && prm->method == DPGO_METHOD_RTR) auto_update(p, prm, res->precond_used, n_hess_total);
   res->spmm_count = cnt.spmm + n_hess_total;
@@ -1210,6 +1235,16 @@ int dpgo_problem_persistent_phases(dpgo_problem_t p, double us_per_iteration[4],
   for (int k = 0; k < 4; ++k)  // (100 MHz wall-clock ticks of participant 0, summed over the iterations after the first)
     us_per_iteration[k] = (p->hctrl && it > 0.0 && p->hctrl->members) ? 0.01 * (double)p->hctrl->ticks[k] / it : 0.0;
   if (iterations) *iterations = (p->hctrl && p->hctrl->members) ? (int)p->hctrl->iters : 0;
+  return DPGO_OK;
+}
+
+
+int dpgo_problem_feed_counters(dpgo_problem_t p, long long counts[4]) {
+  if (!p || !counts) return fail(DPGO_ERR_INVALID, "null handle / pointer");
+  counts[0] = p->feed.steps;
+  counts[1] = p->feed.runs;
+  counts[2] = p->feed.runs_fed;
+  counts[3] = p->feed.products;
   return DPGO_OK;
 }
 

@@ -208,6 +208,7 @@ SIGNATURES = {
     "dpgo_problem_set_persistent": ([_P, _I], _I),
     "dpgo_problem_persistent_info": ([_P, C.POINTER(_I), C.POINTER(_I), C.POINTER(_I), C.POINTER(_I), C.POINTER(_I)], _I),
     "dpgo_problem_persistent_phases": ([_P, _P, C.POINTER(_I)], _I),
+    "dpgo_problem_feed_counters": ([_P, _P], _I),
     "dpgo_chordal_initialization": ([_I, _I, _I, _P, _P, _P, _P, _P, _P, _D, _I, _P, _P, _I], _I),
     "dpgo_odometry_initialization": ([_I, _I, _I, _P, _P, _P, _P, _P], _I),
     "dpgo_device_malloc": ([C.POINTER(_P), C.c_size_t, _I], _I),

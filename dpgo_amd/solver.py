@@ -549,6 +549,14 @@ class QuadraticProblem:
         L.check(self._lib.dpgo_problem_persistent_phases(self._h, v, C.byref(it)))
         return dict(hessian=v[0], reduce_after_hessian=v[1], update=v[2], reduce_after_update=v[3], iterations=it.value)
 
+    def feedCounters(self) -> dict:
+        """What the host fed the tCG loops of the last optimize call (dpgo_problem_feed_counters): steps enqueued, runs
+        started, runs fed at least one step, products executed; dead_iterations = steps - products, the steps that
+        were enqueued behind the end of a run and exited in their prologues."""
+        v = (C.c_longlong * 4)()
+        L.check(self._lib.dpgo_problem_feed_counters(self._h, v))
+        return dict(steps=v[0], runs=v[1], runs_fed=v[2], products=v[3], dead_iterations=v[0] - v[3])
+
     # ---- multilevel preconditioner (built on the device; lazily by the first solve, like
     # PoseGraph::constructPreconditioner inside the first PreConditioner call, src/PoseGraph.cpp:582-586) ----
     def multilevelPath(self) -> dict:

@@ -546,6 +546,13 @@ int dpgo_problem_persistent_info(dpgo_problem_t h, int* enabled, int* workgroups
  * form: + restriction), [3] the reduction(s) behind it (additive: coarse solve, correction, projection and two reductions);
  * all 0 when the last call ran the multi-launch scheme.  *iterations (optional) = tCG iterations of that launch. */
 int dpgo_problem_persistent_phases(dpgo_problem_t h, double us_per_iteration[4], int* iterations);
+/* What the host fed the tCG loops of the LAST optimize call (host counts; no device work, no synchronisation): [0] tCG steps
+ * enqueued (a step = Hessian step + update [+ preconditioner cycle]), [1] tCG runs started, [2] runs that were fed at least
+ * one step, [3] Hessian-vector products executed (= tcg_iterations of the result).  [0] - [3] = steps that were enqueued
+ * behind the end of a run and exited in their prologues: at most one per fed run on the two-level V-cycle with the
+ * restriction's stop check (a step is enqueued only once the device has published that it will run), kAhead per run on the
+ * other multi-launch paths.  A one-launch solve feeds nothing: [0] = [1] = [2] = 0. */
+int dpgo_problem_feed_counters(dpgo_problem_t h, long long counts[4]);
 
 /* ---- pose order for HBM-bound blocks (host only; no reference counterpart: Eigen's product has no such notion) ----
  * The block-SpMM kernels gather the tiles of a pose's graph neighbours; each XCD's workgroups sweep one contiguous eighth
