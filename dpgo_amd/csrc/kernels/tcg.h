@@ -615,7 +615,16 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(DPGO_SYM
 // DEF = 1 (kept directions, see above k_tcg_hess): delta and eta are not touched (null), the step length goes to `coef`.
 // (3, 5): the multilevel instance drops from 147 to 119 VGPRs; it stays at DPGO_UPDATE_WAVES_ML waves -- a fourth workgroup
 // per CU does not fit the LDS (4 x 41 088 bytes), and the grid, hence the order of the partial sums, is the reference's.
-template <int D, int R, int ML = 0, int DEF = 0>
+// PIPE = 1 (DPGO_UPDATE_PIPE, the default; 0 = the reference order, same bits): the next tile is requested while this one is
+// still being finished, see request_next below.  It costs the registers of a second tile's geometry and block-Jacobi row
+// and whatever the compiler then keeps live: (3, 5) DEF = 1 goes from 119 to 157 VGPRs, still three waves, no scratch.  The
+// instances that do not hold their occupancy that way have no PIPE = 1 form (kUpdatePipe: the launch picks PIPE = 0):
+//  * ML = 1, DEF = 0 at 20 and more doubles per pose, (3, 5) and (3, 6): four piece sets (eta, delta, H delta, r) in flight
+//    need 168 VGPRs and 180 / 232 bytes of scratch per lane; up to 16 doubles per pose it fits (115-164 VGPRs);
+//  * every ML = 0 instance: (3, 5) goes from 209 VGPRs to 256 + 20 AGPRs (2 -> 1 wave), (3, 3) DEF = 1 from 4 waves to 2.
+template <int D, int R, int DEF>
+constexpr int kUpdatePipe = (DEF || Geo<D, R>::T <= 16) ? 1 : 0;
+template <int D, int R, int ML = 0, int DEF = 0, int PIPE = 0>
 __global__ __launch_bounds__(kBlock)
     __attribute__((amdgpu_waves_per_eu(ML ? DPGO_UPDATE_WAVES_ML : (DPGO_UPDATE_WAVES ? DPGO_UPDATE_WAVES : 1),
                                        ML ? DPGO_UPDATE_WAVES_ML : (DPGO_UPDATE_WAVES ? DPGO_UPDATE_WAVES : 8))))
@@ -650,13 +659,17 @@ void k_tcg_update_span(const double* __restrict__ X, const double* __restrict__ 
   double drow[GEO::B];
   int p0 = 0, valid = 0, i = 0;
   bool ok = false;
-  auto prefetch = [&](int tile) {
-    p0 = tile * GEO::P + L.wave * GEO::G;
-    const int npose = (n - p0) < GEO::G ? (n - p0) : GEO::G;
-    valid = npose > 0 ? npose * GEO::T : 0;
-    i = p0 + L.g;
-    ok = (L.g < GEO::G) && (i < n);
-    const size_t base = (size_t)p0 * GEO::T;
+  // (PIPE: the geometry and the block-Jacobi row of the tile in flight, beside the ones of the tile being finished)
+  [[maybe_unused]] double drow_n[GEO::B];
+  [[maybe_unused]] int p0_n = 0, valid_n = 0, i_n = 0;
+  [[maybe_unused]] bool ok_n = false;
+  auto request = [&](int tile, int& p0_, int& valid_, int& i_, bool& ok_, double (&drow_)[GEO::B]) {
+    p0_ = tile * GEO::P + L.wave * GEO::G;
+    const int npose = (n - p0_) < GEO::G ? (n - p0_) : GEO::G;
+    valid_ = npose > 0 ? npose * GEO::T : 0;
+    i_ = p0_ + L.g;
+    ok_ = (L.g < GEO::G) && (i_ < n);
+    const size_t base = (size_t)p0_ * GEO::T;
     const dbl2* X2 = reinterpret_cast<const dbl2*>(X + base);
     const dbl2* g2 = reinterpret_cast<const dbl2*>(g + base);
     [[maybe_unused]] const dbl2* e2 = reinterpret_cast<const dbl2*>(eta + base);
@@ -666,7 +679,7 @@ void k_tcg_update_span(const double* __restrict__ X, const double* __restrict__ 
 #pragma unroll
     for (int it = 0; it < SPN::NIT; ++it) {
       const int pc = lane + 64 * it;
-      if (2 * pc < valid) {
+      if (2 * pc < valid_) {
         // (the iterate is only needed by the tangent projection of the block-Jacobi / unpreconditioned z; the multilevel
         // pre-smoothing step x1 = w Dinv r is not projected: 16 MB less per launch at 100k poses)
         if (!ml_mode) xv[it] = X2[pc];
@@ -682,9 +695,21 @@ void k_tcg_update_span(const double* __restrict__ X, const double* __restrict__ 
         }
       }
     }
-    if (ok && dinv) {
+    if (ok_ && dinv) {
 #pragma unroll
-      for (int k = 0; k < GEO::B; ++k) drow[k] = dinv[(size_t)i * GEO::BB + L.c * GEO::B + k];
+      for (int k = 0; k < GEO::B; ++k) drow_[k] = dinv[(size_t)i_ * GEO::BB + L.c * GEO::B + k];
+    }
+  };
+  auto prefetch = [&](int tile) { request(tile, p0, valid, i, ok, drow); };
+  // PIPE = 1: the next tile is requested as soon as the piece registers of this one are consumed -- behind the first
+  // per-piece loop, which is the last reader of xv / ev / dv / hv / rv -- so its round trip runs under the block-Jacobi
+  // step, the LDS passes and the stores of z instead of starting behind them.  The pieces it loads are other addresses
+  // than the ones just stored; the arithmetic, its order and every store are those of PIPE = 0 (DPGO_UPDATE_PIPE=0).
+  auto request_next = [&](int& tile, bool& have) {
+    if constexpr (PIPE) {
+      tile += ti_.step;
+      have = tile < ti_.last;
+      if (have) request(tile, p0_n, valid_n, i_n, ok_n, drow_n);
     }
   };
   DPGO_TL_DECL;
@@ -738,6 +763,7 @@ void k_tcg_update_span(const double* __restrict__ X, const double* __restrict__ 
           r2[pc] = rr;
         }
       }
+      request_next(tile, have);
     } else {
       dbl2* r2 = reinterpret_cast<dbl2*>(r + base);
 #pragma unroll
@@ -769,6 +795,7 @@ void k_tcg_update_span(const double* __restrict__ X, const double* __restrict__ 
           part[0] = fma(rr.y, rr.y, part[0]);
         }
       }
+      request_next(tile, have);
       wave_sync();
       double zz[R];
       if (ok) {
@@ -817,9 +844,20 @@ void k_tcg_update_span(const double* __restrict__ X, const double* __restrict__ 
       wave_sync();
     }
     DPGO_STAMP(1, 5);
-    tile += ti_.step;
-    have = tile < ti_.last;
-    if (have) prefetch(tile);
+    if constexpr (PIPE) {
+      if (have) {
+        p0 = p0_n;
+        valid = valid_n;
+        i = i_n;
+        ok = ok_n;
+#pragma unroll
+        for (int k = 0; k < GEO::B; ++k) drow[k] = drow_n[k];
+      }
+    } else {
+      tile += ti_.step;
+      have = tile < ti_.last;
+      if (have) prefetch(tile);
+    }
   }
   if (mode != 1) store_partials<2>(part, pout, red);
   DPGO_STAMP(1, 6);

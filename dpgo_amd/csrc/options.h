@@ -20,6 +20,7 @@ namespace dpgo_host {
   X(rho_exact,         "DPGO_RHO_EXACT",          0,  "rho test from a fresh H eta (k_hess, one more pass over Q) instead of tCG's residual: reference path") \
   X(tcg_dirs,          "DPGO_TCG_DIRS",           1,  "multi-launch tCG keeps its directions and k_retract sums eta once (0: eta += alpha delta every iteration: reference path)") \
   X(tcg_dirs_max_mb,   "DPGO_TCG_DIRS_MAX_MB", 4096,  "largest direction ring (RTR_tCG_iterations pose vectors) a solve may hold; beyond it the solve runs the reference path") \
+  X(update_pipe,       "DPGO_UPDATE_PIPE",        1,  "k_tcg_update_span requests its next tile behind the first per-piece loop (0: behind the tile's last store: reference order)") \
   X(tile_walk,         "DPGO_TILE_WALK",          1,  "symmetric-storage kernels walk each XCD's tiles breadth-first over the tile graph (0: index order)") \
   X(tcg_ahead,         "DPGO_TCG_AHEAD",          0,  "iterations the just-in-time feed stays ahead (0: 2 multilevel / 4 otherwise)") \
   X(grid_update,       "DPGO_GRID_UPDATE",        0,  "launch cap of k_tcg_update (0: resident count)")                              \

@@ -27,8 +27,14 @@ int launch_tcg_update(dpgo_problem_s* p, const double* dinv, int first, double* 
     };
     if constexpr (Span<D, R, 1>::kOk) {
       // (its own instance for the multilevel mode: 3 waves per SIMD)
-      if (def) return go(ml_mode ? k_tcg_update_span<D, R, 1, 1> : k_tcg_update_span<D, R, 0, 1>, z32);
-      return go(ml_mode ? k_tcg_update_span<D, R, 1> : k_tcg_update_span<D, R, 0>, z32);
+      // (DPGO_UPDATE_PIPE=0: the instances that request the next tile behind the last store -- same bits, kernels/tcg.h)
+      // (only the multilevel instances that hold their three waves with a tile in flight have a PIPE = 1 form)
+      if (!ml_mode) return def ? go(k_tcg_update_span<D, R, 0, 1, 0>, z32) : go(k_tcg_update_span<D, R, 0, 0, 0>, z32);
+      // (... and only a launch in which a workgroup can hold a second tile has one to request early: with a tile per
+      // workgroup -- every block up to the resident count, sphere2500's 40 tiles -- the reference-order instance runs)
+      const bool pipe = options().update_pipe != 0 && pose_tiles(p->n, p->b) > g;
+      if (def) return go(pipe ? k_tcg_update_span<D, R, 1, 1, kUpdatePipe<D, R, 1>> : k_tcg_update_span<D, R, 1, 1, 0>, z32);
+      return go(pipe ? k_tcg_update_span<D, R, 1, 0, kUpdatePipe<D, R, 0>> : k_tcg_update_span<D, R, 1, 0, 0>, z32);
     } else {
       // (odd tile size: the generic kernel has no fp32 output -- resolve_tcg_storage keeps such blocks off the symmetric
       // storage, hence off the cycle's fp32 vectors; a state that says otherwise is refused instead of dropping z32)
@@ -871,8 +877,9 @@ int tune_launch_caps(dpgo_problem_s* p) {
   CHK(dispatch_dr(p->d, p->r, [&](auto Dc, auto Rc) {
     constexpr int D = decltype(Dc)::value, R = decltype(Rc)::value;
     if constexpr (Span<D, R, 1>::kOk) {
-      CHK(resident_blocks(k_tcg_update_span<D, R, 0>, &p->cap_u));
-      CHK(resident_blocks(k_tcg_update_span<D, R, 1>, &p->cap_u_ml));
+      // (the reference-order instances, PIPE = 0: the grids do not follow DPGO_UPDATE_PIPE; both orders have these counts)
+      CHK(resident_blocks(k_tcg_update_span<D, R, 0, 0, 0>, &p->cap_u));
+      CHK(resident_blocks(k_tcg_update_span<D, R, 1, 0, 0>, &p->cap_u_ml));
       // cap_hs: the non-temporal instance <D, R, 1>, also when <D, R, 0> runs
       CHK(resident_blocks(k_tcg_hess_sym<D, R, 1>, &p->cap_hs));
     } else {
