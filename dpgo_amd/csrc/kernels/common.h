@@ -449,6 +449,18 @@ __device__ __forceinline__ void proj_col(const double* ys, const double* ws, int
   }
 }
 
+// S-correction of the Euclidean Hessian, column c < D of one pose:  h[:,c] -= sum_a V[:,a] * S[a][c]   (S symmetric: srow =
+// row c of S_i, in registers or in global memory); vt = the pose's tile of V in LDS ([col][R]).
+template <int D, int R, class SROW>
+__device__ __forceinline__ void s_correct_col(const double* vt, const SROW& srow, double (&h)[R]) {
+#pragma unroll
+  for (int a = 0; a < D; ++a) {
+    const double sac = srow[a];
+#pragma unroll
+    for (int k = 0; k < R; ++k) h[k] = fma(-vt[a * R + k], sac, h[k]);
+  }
+}
+
 // Block-Jacobi: z[:,c] = sum_k v[:,k] * Dinv[k][c]   (Dinv symmetric; lane reads row c)
 template <int D, int R>
 __device__ __forceinline__ void jacobi_col(const double* vs /* LDS tile */, const double* __restrict__ dinv_row,

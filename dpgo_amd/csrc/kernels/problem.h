@@ -208,15 +208,7 @@ __global__ __launch_bounds__(kBlock) void k_hess(MAT Q, const double* __restrict
     }
     wave_sync();
     if (ok) {
-      if (L.c < D) {
-        // h[:,c] -= sum_a V[:,a] * S[a][c]   (S symmetric: row c of S_i)
-#pragma unroll
-        for (int a = 0; a < D; ++a) {
-          const double sac = S[(size_t)i * D * D + L.c * D + a];
-#pragma unroll
-          for (int k = 0; k < R; ++k) h[k] = fma(-vs[a * R + k], sac, h[k]);
-        }
-      }
+      if (L.c < D) s_correct_col<D, R>(vs, S + ((size_t)i * D * D + L.c * D), h);
       store_col<R>(hs + L.c * R, h);
     }
     wave_sync();

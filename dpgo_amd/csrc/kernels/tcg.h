@@ -1,5 +1,12 @@
 // kernels/tcg.h -- the two kernels of the tCG loop (fused Hessian step and residual / iterate update): shared scalar prologues,
 // the generic-layout kernels (odd tile size) and the span kernels (even tile size: every 3-D case).
+// What the kernels share exists once, as force-inlined helpers (each kernel keeps its own load placement):
+//   entry         tcg_idle, tcg_publish                          early-exit test; thread 0 of workgroup 0 stores the state and publishes
+//   tile          TileGeo, tile_geo                              p0 / valid / i / okp / ok of a wave's share of a pose tile (span layout)
+//   Hessian step  tcg_ring_slots, hess_stage, hess_project,      DEF ring slots; X, z to LDS; S-correction (s_correct_col, common.h: shared
+//                 hess_direction_update                          with k_hess) + projection; delta / H delta update and <delta, H delta>
+//   update        tcg_step_span, tcg_step_col                    eta += c delta (unless DEF), r += c H delta, for c = alpha and c = tau
+//                 (the z tail is span_from_lds, common.h: fp64 or fp32 destination)
 // Part of kernels.h (included inside namespace dpgo, in this order: common.h, problem.h, tcg.h, persist.h, multilevel.h, dense.h, manifold.h, rtr.h, agent.h, init.h).
 #pragma once
 
@@ -114,6 +121,156 @@ __device__ __forceinline__ void tcg_store_coef(double* __restrict__ coef, const 
     }
   }
 }
+// The ring slots a Hessian step reads and writes, from the iteration index the prologue has just computed: slot k of the
+// ring receives delta_k, slot k - 1 holds delta_{k-1} (a slot is n * T doubles).  DEF = 0: both are `delta`, updated in place.
+template <int DEF, int T>
+__device__ __forceinline__ void tcg_ring_slots(double* delta, int first, int tcg_j, int n, const double*& din, double*& dout) {
+  dout = delta;
+  if constexpr (DEF) dout = delta + (size_t)(first ? 0 : tcg_j) * ((size_t)n * T);
+  din = (DEF && !first) ? dout - (size_t)n * T : dout;
+}
+
+// ---------------------------------------------------------------- entry: early exit, state record and progress word
+// A launch has nothing to do once the outer iteration has stopped or the tCG run is over (`done_counts` = false: the update
+// kernel's initialisation launch, first = 1, starts a run whatever the record says about the last one).
+__device__ __forceinline__ bool tcg_idle(const DevState& st, bool done_counts = true) {
+  return st.rtr_stop || (done_counts && st.tcg_done);
+}
+// One thread of the launch stores the state record and publishes the progress word; `between` runs between the two (the
+// update kernels store the step length there, tcg_store_coef).
+struct TcgNothing {
+  __device__ __forceinline__ void operator()() const {}
+};
+template <class F = TcgNothing>
+__device__ __forceinline__ void tcg_publish(DevState* sout, const DevState& st, unsigned long long* hflag, unsigned gen,
+                                            F between = F()) {
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    store_state(sout, st);
+    between();
+    publish_progress(hflag, gen, st);
+  }
+}
+
+// ---------------------------------------------------------------- span layout: a wave's share of a pose tile
+// p0 = its first pose, valid = entries of its span that exist (ragged last tile), i = this lane's pose, okp = the pose exists,
+// ok = ... and this lane group is the one that owns it (SPLIT > 1: group 0).
+struct TileGeo {
+  int p0, valid, i;
+  bool okp, ok;
+};
+template <class GEO>
+__device__ __forceinline__ TileGeo tile_geo(int tile, int n, const LaneId& L) {
+  TileGeo t;
+  t.p0 = tile * GEO::P + L.wave * GEO::G;
+  const int npose = (n - t.p0) < GEO::G ? (n - t.p0) : GEO::G;
+  t.valid = npose > 0 ? npose * GEO::T : 0;
+  t.i = t.p0 + L.g;
+  t.okp = (L.g < GEO::G) && (t.i < n);
+  t.ok = t.okp && (L.s == 0);
+  return t;
+}
+
+// ---------------------------------------------------------------- Hessian-step tile phases (span and symmetric kernels)
+// Own-tile X and z pieces to the wave's LDS tiles.
+template <int NIT>
+__device__ __forceinline__ void hess_stage(double* ys, double* vs, const dbl2 (&xv)[NIT], const dbl2 (&zv)[NIT], int valid,
+                                           int lane) {
+#pragma unroll
+  for (int it = 0; it < NIT; ++it) {
+    const int pc = lane + 64 * it;
+    if (2 * pc < valid) {
+      reinterpret_cast<dbl2*>(ys)[pc] = xv[it];
+      reinterpret_cast<dbl2*>(vs)[pc] = zv[it];
+    }
+  }
+}
+// h = column c of z Q (the gather's result) -> os = proj_X(h - z_rot S); hs is the tile in between.  Runs between two
+// wave_sync() of the caller (vs staged before it, os read after it).
+template <int D, int R>
+__device__ __forceinline__ void hess_project(const double* ys, const double* vs, double* hs, double* os,
+                                             const double (&srow)[D], const LaneId& L, bool ok, double (&h)[R]) {
+  constexpr int T = Geo<D, R>::T;
+  if (ok) {
+    if (L.c < D) s_correct_col<D, R>(vs + L.g * T, srow, h);
+    store_col<R>(hs + L.g * T + L.c * R, h);
+  }
+  wave_sync();
+  if (ok) {
+    double hz[R], sdummy[D];
+    proj_col<D, R>(ys + L.g * T, hs + L.g * T, L.c, h, hz, sdummy);
+    store_col<R>(os + L.g * T + L.c * R, hz);
+  }
+}
+// z of piece `it`: from the registers that staged it (k_tcg_hess_span) or re-read from its LDS tile (k_tcg_hess_sym).
+template <int NIT>
+__device__ __forceinline__ dbl2 hess_z_piece(const dbl2 (&zv)[NIT], int it, int) { return zv[it]; }
+__device__ __forceinline__ dbl2 hess_z_piece(const double* vs, int, int pc) { return reinterpret_cast<const dbl2*>(vs)[pc]; }
+// Row-local direction update in span layout: delta <- beta delta - z, H delta <- beta H delta - Hz (Hz from os), stored to
+// dtile / htile (the wave's spans of the output slot and of H delta), and the <delta, H delta> partial.
+template <int NTS, int NIT, class Z>
+__device__ __forceinline__ void hess_direction_update(double* dtile, double* htile, const double* os, const Z& z,
+                                                      const dbl2 (&dv)[NIT], const dbl2 (&hv)[NIT], double beta, int first,
+                                                      int valid, int lane, double& part) {
+  dbl2* d2 = reinterpret_cast<dbl2*>(dtile);
+  dbl2* h2 = reinterpret_cast<dbl2*>(htile);
+#pragma unroll
+  for (int it = 0; it < NIT; ++it) {
+    const int pc = lane + 64 * it;
+    if (2 * pc < valid) {
+      const dbl2 hzv = reinterpret_cast<const dbl2*>(os)[pc];
+      const dbl2 zl = hess_z_piece(z, it, pc);
+      dbl2 dn, hn;
+      if (first) {
+        dn.x = -zl.x;
+        dn.y = -zl.y;
+        hn.x = -hzv.x;
+        hn.y = -hzv.y;
+      } else {
+        dn.x = fma(beta, dv[it].x, -zl.x);
+        dn.y = fma(beta, dv[it].y, -zl.y);
+        hn.x = fma(beta, hv[it].x, -hzv.x);
+        hn.y = fma(beta, hv[it].y, -hzv.y);
+      }
+      st_stream<NTS>(d2 + pc, dn);
+      st_stream<NTS>(h2 + pc, hn);
+      part = fma(dn.x, hn.x, part);
+      part = fma(dn.y, hn.y, part);
+    }
+  }
+}
+
+// ---------------------------------------------------------------- update-kernel recurrences
+// eta += c delta (not with DEF: the directions are kept and eta is formed once, in k_retract) and r += c H delta, for the
+// regular step (c = alpha) and the boundary step (c = tau).  Span layout: one piece, eta stored, r left to the caller.
+template <int DEF>
+__device__ __forceinline__ void tcg_step_span(double c, const dbl2& ev, const dbl2& dv, const dbl2& hv, dbl2* eta_pc, dbl2& rr) {
+  if constexpr (!DEF) {
+    dbl2 e = ev;
+    e.x = fma(c, dv.x, e.x);
+    e.y = fma(c, dv.y, e.y);
+    *eta_pc = e;
+  }
+  rr.x = fma(c, hv.x, rr.x);
+  rr.y = fma(c, hv.y, rr.y);
+}
+// Column layout: loads included (eta, delta, H delta, r at this lane's column), eta stored, r left to the caller.
+template <int R, int DEF>
+__device__ __forceinline__ void tcg_step_col(double c, double* eta_c, const double* delta_c, const double* Hd_c,
+                                             const double* r_c, double (&rr)[R]) {
+  double hd[R];
+  if constexpr (!DEF) {
+    double e[R], dl[R];
+    load_col<R>(eta_c, e);
+    load_col<R>(delta_c, dl);
+#pragma unroll
+    for (int a = 0; a < R; ++a) e[a] = fma(c, dl[a], e[a]);
+    store_col<R>(eta_c, e);
+  }
+  load_col<R>(Hd_c, hd);
+  load_col<R>(r_c, rr);
+#pragma unroll
+  for (int a = 0; a < R; ++a) rr[a] = fma(c, hd[a], rr[a]);
+}
 
 template <int D, int R, int SPLIT, int DEF = 0>
 __global__ __launch_bounds__(kBlock, DPGO_LB_HESS) void k_tcg_hess(BsrDev Q, const double* __restrict__ X,
@@ -130,24 +287,17 @@ __global__ __launch_bounds__(kBlock, DPGO_LB_HESS) void k_tcg_hess(BsrDev Q, con
   DevState st;
   load_state(st, sin);
   gen = state_gen(st, gen);
-  if (st.rtr_stop || st.tcg_done) {
-    if (blockIdx.x == 0 && threadIdx.x == 0) {
-      store_state(sout, st);
-      publish_progress(hflag, gen, st);
-    }
+  if (tcg_idle(st)) {
+    tcg_publish(sout, st, hflag, gen);
     return;
   }
   double beta;
   const bool go = tcg_hess_prologue(st, pin, nb_in, first, red, beta);
-  if (blockIdx.x == 0 && threadIdx.x == 0) {
-    store_state(sout, st);
-    publish_progress(hflag, gen, st);
-  }
+  tcg_publish(sout, st, hflag, gen);
   if (!go) return;
-  // (DEF: slot k of the ring receives delta_k, slot k - 1 holds delta_{k-1})
-  double* dout = delta;
-  if constexpr (DEF) dout = delta + (size_t)(first ? 0 : st.tcg_j) * ((size_t)n * GEO::T);
-  const double* din = (DEF && !first) ? dout - (size_t)n * GEO::T : dout;
+  const double* din;
+  double* dout;
+  tcg_ring_slots<DEF, GEO::T>(delta, first, st.tcg_j, n, din, dout);
 
   const LaneId L = lane_id<D, SPLIT>();
   const int ntiles = (n + GEO::P - 1) / GEO::P;
@@ -183,13 +333,7 @@ __global__ __launch_bounds__(kBlock, DPGO_LB_HESS) void k_tcg_hess(BsrDev Q, con
     }
     wave_sync();
     if (ok) {
-      if (L.c < D) {
-#pragma unroll
-        for (int a = 0; a < D; ++a) {
-#pragma unroll
-          for (int k = 0; k < R; ++k) h[k] = fma(-vs[a * R + k], srow[a], h[k]);
-        }
-      }
+      if (L.c < D) s_correct_col<D, R>(vs, srow, h);
       store_col<R>(hs + L.c * R, h);
     }
     wave_sync();
@@ -250,28 +394,22 @@ __global__ __launch_bounds__(kBlock) void k_tcg_hess_span(BsrDev Q, const double
   RowIdx ri;
   dbl2 xv[SPN::NIT], zv[SPN::NIT], dv[SPN::NIT], hv[SPN::NIT];
   double srow[D];
-  int p0 = 0, valid = 0, i = 0;
-  bool okp = false, ok = false;
+  TileGeo tg{};
   // (DEF: the ring slots this launch reads and writes follow from the prologue: the first tile's piece of delta_{k-1} is
   // requested behind it -- an early-exit launch must not touch the ring, its tcg_j may equal the number of slots)
   const double* din = DEF ? nullptr : delta;
   double* dout = delta;
   auto prefetch = [&](int tile) {
-    p0 = tile * GEO::P + L.wave * GEO::G;
-    const int npose = (n - p0) < GEO::G ? (n - p0) : GEO::G;
-    valid = npose > 0 ? npose * GEO::T : 0;
-    i = p0 + L.g;
-    okp = (L.g < GEO::G) && (i < n);
-    ok = okp && (L.s == 0);
-    ri = row_idx_load<D, SPLIT>(Q.rowptr, Q.colidx, i, L.s, L.c, okp);
-    const size_t base = (size_t)p0 * GEO::T;
+    tg = tile_geo<GEO>(tile, n, L);
+    ri = row_idx_load<D, SPLIT>(Q.rowptr, Q.colidx, tg.i, L.s, L.c, tg.okp);
+    const size_t base = (size_t)tg.p0 * GEO::T;
     const dbl2* X2 = reinterpret_cast<const dbl2*>(X + base);
     const dbl2* z2 = reinterpret_cast<const dbl2*>(z + base);
     const dbl2* h2 = reinterpret_cast<const dbl2*>(Hd + base);
 #pragma unroll
     for (int it = 0; it < SPN::NIT; ++it) {
       const int pc = lane + 64 * it;
-      if (2 * pc < valid) {
+      if (2 * pc < tg.valid) {
         xv[it] = ld_stream<NTS>(X2 + pc);
         zv[it] = z2[pc];
         if (!first) {
@@ -280,9 +418,9 @@ __global__ __launch_bounds__(kBlock) void k_tcg_hess_span(BsrDev Q, const double
         }
       }
     }
-    if (ok && L.c < D) {
+    if (tg.ok && L.c < D) {
 #pragma unroll
-      for (int a = 0; a < D; ++a) srow[a] = ld_stream<NTS>(S + (size_t)i * D * D + L.c * D + a);
+      for (int a = 0; a < D; ++a) srow[a] = ld_stream<NTS>(S + (size_t)tg.i * D * D + L.c * D + a);
     }
   };
   // ---- everything the prologue needs is requested before the first wait: state record (scalar loads), the
@@ -302,97 +440,39 @@ __global__ __launch_bounds__(kBlock) void k_tcg_hess_span(BsrDev Q, const double
 
   DPGO_STAMP(0, 1);
   // ---- scalar prologue
-  if (st.rtr_stop || st.tcg_done) {
-    if (blockIdx.x == 0 && threadIdx.x == 0) {
-      store_state(sout, st);
-      publish_progress(hflag, gen, st);
-    }
+  if (tcg_idle(st)) {
+    tcg_publish(sout, st, hflag, gen);
     return;
   }
   double beta;
   const bool go = tcg_hess_prologue(st, pin, nb_in, first, red, beta, (SPLIT > 1) ? &praw : nullptr);
-  if (blockIdx.x == 0 && threadIdx.x == 0) {
-    store_state(sout, st);
-    publish_progress(hflag, gen, st);
-  }
+  tcg_publish(sout, st, hflag, gen);
   if (!go) return;
   DPGO_STAMP(0, 2);
+  tcg_ring_slots<DEF, GEO::T>(delta, first, st.tcg_j, n, din, dout);
   if constexpr (DEF) {
-    dout = delta + (size_t)(first ? 0 : st.tcg_j) * ((size_t)n * GEO::T);
-    if (!first) {
-      din = dout - (size_t)n * GEO::T;
-      if (have) {
-        const dbl2* d2 = reinterpret_cast<const dbl2*>(din + (size_t)p0 * GEO::T);
+    if (!first && have) {
+      const dbl2* d2 = reinterpret_cast<const dbl2*>(din + (size_t)tg.p0 * GEO::T);
 #pragma unroll
-        for (int it = 0; it < SPN::NIT; ++it) {
-          const int pc = lane + 64 * it;
-          if (2 * pc < valid) dv[it] = ld_stream<NTS>(d2 + pc);
-        }
+      for (int it = 0; it < SPN::NIT; ++it) {
+        const int pc = lane + 64 * it;
+        if (2 * pc < tg.valid) dv[it] = ld_stream<NTS>(d2 + pc);
       }
     }
   }
 
   double part[1] = {0.0};
   while (have) {
-#pragma unroll
-    for (int it = 0; it < SPN::NIT; ++it) {
-      const int pc = lane + 64 * it;
-      if (2 * pc < valid) {
-        reinterpret_cast<dbl2*>(ys)[pc] = xv[it];
-        reinterpret_cast<dbl2*>(vs)[pc] = zv[it];
-      }
-    }
+    hess_stage(ys, vs, xv, zv, tg.valid, lane);
     DPGO_STAMP(0, 3);
     double h[R];
     spmm_col_pre<D, R, SPLIT>(ri, Q.colidx, Q.vals, z, L.s, L.c, h);
     wave_sync();
     DPGO_STAMP(0, 4);
-    if (ok) {
-      if (L.c < D) {
-        const double* vt = vs + L.g * GEO::T;
-#pragma unroll
-        for (int a = 0; a < D; ++a) {
-#pragma unroll
-          for (int k = 0; k < R; ++k) h[k] = fma(-vt[a * R + k], srow[a], h[k]);
-        }
-      }
-      store_col<R>(hs + L.g * GEO::T + L.c * R, h);
-    }
+    hess_project<D, R>(ys, vs, hs, os, srow, L, tg.ok, h);
     wave_sync();
-    if (ok) {
-      double hz[R], sdummy[D];
-      proj_col<D, R>(ys + L.g * GEO::T, hs + L.g * GEO::T, L.c, h, hz, sdummy);
-      store_col<R>(os + L.g * GEO::T + L.c * R, hz);
-    }
-    wave_sync();
-    {
-      const size_t base = (size_t)p0 * GEO::T;
-      dbl2* d2 = reinterpret_cast<dbl2*>(dout + base);
-      dbl2* h2 = reinterpret_cast<dbl2*>(Hd + base);
-#pragma unroll
-      for (int it = 0; it < SPN::NIT; ++it) {
-        const int pc = lane + 64 * it;
-        if (2 * pc < valid) {
-          const dbl2 hzv = reinterpret_cast<const dbl2*>(os)[pc];
-          dbl2 dn, hn;
-          if (first) {
-            dn.x = -zv[it].x;
-            dn.y = -zv[it].y;
-            hn.x = -hzv.x;
-            hn.y = -hzv.y;
-          } else {
-            dn.x = fma(beta, dv[it].x, -zv[it].x);
-            dn.y = fma(beta, dv[it].y, -zv[it].y);
-            hn.x = fma(beta, hv[it].x, -hzv.x);
-            hn.y = fma(beta, hv[it].y, -hzv.y);
-          }
-          st_stream<NTS>(d2 + pc, dn);
-          st_stream<NTS>(h2 + pc, hn);
-          part[0] = fma(dn.x, hn.x, part[0]);
-          part[0] = fma(dn.y, hn.y, part[0]);
-        }
-      }
-    }
+    hess_direction_update<NTS>(dout + (size_t)tg.p0 * GEO::T, Hd + (size_t)tg.p0 * GEO::T, os, zv, dv, hv, beta, first,
+                               tg.valid, lane, part[0]);
     wave_sync();
     DPGO_STAMP(0, 5);
     tile += ti_.step;
@@ -439,31 +519,24 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(DPGO_SYM
   SymIdx si;
   dbl2 xv[SPN::NIT], zv[SPN::NIT];
   double srow[D];
-  int p0 = 0, valid = 0, i = 0;
-  bool okp = false, ok = false;
+  TileGeo tg{};
   auto prefetch = [&](int tk) {
-    const int tile = tile_of(Q, tk);  // (the walk over the tiles: BsrSymDevT::tord)
-    p0 = tile * GEO::P + L.wave * GEO::G;
-    const int npose = (n - p0) < GEO::G ? (n - p0) : GEO::G;
-    valid = npose > 0 ? npose * GEO::T : 0;
-    i = p0 + L.g;
-    okp = (L.g < GEO::G) && (i < n);
-    ok = okp && (L.s == 0);
-    si = sym_idx_load<D>(Q, i, L.c, okp);
-    const size_t base = (size_t)p0 * GEO::T;
+    tg = tile_geo<GEO>(tile_of(Q, tk), n, L);  // (the walk over the tiles: BsrSymDevT::tord)
+    si = sym_idx_load<D>(Q, tg.i, L.c, tg.okp);
+    const size_t base = (size_t)tg.p0 * GEO::T;
     const dbl2* X2 = reinterpret_cast<const dbl2*>(X + base);
     const dbl2* z2 = reinterpret_cast<const dbl2*>(z + base);
 #pragma unroll
     for (int it = 0; it < SPN::NIT; ++it) {
       const int pc = lane + 64 * it;
-      if (2 * pc < valid) {
+      if (2 * pc < tg.valid) {
         xv[it] = ld_stream<NTS>(X2 + pc);
         zv[it] = z2[pc];
       }
     }
-    if (ok && L.c < D) {
+    if (tg.ok && L.c < D) {
 #pragma unroll
-      for (int a = 0; a < D; ++a) srow[a] = ld_stream<NTS>(S + (size_t)i * D * D + L.c * D + a);
+      for (int a = 0; a < D; ++a) srow[a] = ld_stream<NTS>(S + (size_t)tg.i * D * D + L.c * D + a);
     }
   };
   // ---- everything the prologue needs is requested before the first wait: state record (scalar loads), the
@@ -483,24 +556,17 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(DPGO_SYM
 
   DPGO_STAMP(0, 1);
   // ---- scalar prologue
-  if (st.rtr_stop || st.tcg_done) {
-    if (blockIdx.x == 0 && threadIdx.x == 0) {
-      store_state(sout, st);
-      publish_progress(hflag, gen, st);
-    }
+  if (tcg_idle(st)) {
+    tcg_publish(sout, st, hflag, gen);
     return;
   }
   double beta;
   const bool go = tcg_hess_prologue(st, pin, nb_in, first, red, beta, (SPLIT > 1) ? &praw : nullptr);
-  if (blockIdx.x == 0 && threadIdx.x == 0) {
-    store_state(sout, st);
-    publish_progress(hflag, gen, st);
-  }
+  tcg_publish(sout, st, hflag, gen);
   if (!go) return;
-  // (DEF: slot k of the ring receives delta_k, slot k - 1 holds delta_{k-1})
-  double* dout = delta;
-  if constexpr (DEF) dout = delta + (size_t)(first ? 0 : st.tcg_j) * ((size_t)n * GEO::T);
-  const double* din = (DEF && !first) ? dout - (size_t)n * GEO::T : dout;
+  const double* din;
+  double* dout;
+  tcg_ring_slots<DEF, GEO::T>(delta, first, st.tcg_j, n, din, dout);
   DPGO_STAMP(0, 2);
   DPGO_STAMP_ENTRY;
   DPGO_STAMP_AT(1);
@@ -508,14 +574,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(DPGO_SYM
   double part[1] = {0.0};
   while (have) {
     DPGO_STAMP_TILE(0);
-#pragma unroll
-    for (int it = 0; it < SPN::NIT; ++it) {
-      const int pc = lane + 64 * it;
-      if (2 * pc < valid) {
-        reinterpret_cast<dbl2*>(ys)[pc] = xv[it];
-        reinterpret_cast<dbl2*>(vs)[pc] = zv[it];
-      }
-    }
+    hess_stage(ys, vs, xv, zv, tg.valid, lane);
     DPGO_STAMP(0, 3);
     DPGO_STAMP_TILE(1);
     double h[R];
@@ -526,13 +585,13 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(DPGO_SYM
     // the projection
     dbl2 dv[SPN::NIT], hv[SPN::NIT];
     if (!first) {
-      const size_t base = (size_t)p0 * GEO::T;
+      const size_t base = (size_t)tg.p0 * GEO::T;
       const dbl2* d2 = reinterpret_cast<const dbl2*>(din + base);
       const dbl2* h2 = reinterpret_cast<const dbl2*>(Hd + base);
 #pragma unroll
       for (int it = 0; it < SPN::NIT; ++it) {
         const int pc = lane + 64 * it;
-        if (2 * pc < valid) {
+        if (2 * pc < tg.valid) {
           dv[it] = ld_stream<NTS>(d2 + pc);
           hv[it] = ld_stream<NTS>(h2 + pc);
         }
@@ -541,54 +600,11 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(DPGO_SYM
     wave_sync();
     DPGO_STAMP(0, 4);
     DPGO_STAMP_TILE(3);
-    if (ok) {
-      if (L.c < D) {
-        const double* vt = vs + L.g * GEO::T;
-#pragma unroll
-        for (int a = 0; a < D; ++a) {
-#pragma unroll
-          for (int k = 0; k < R; ++k) h[k] = fma(-vt[a * R + k], srow[a], h[k]);
-        }
-      }
-      store_col<R>(hs + L.g * GEO::T + L.c * R, h);
-    }
-    wave_sync();
-    if (ok) {
-      double hz[R], sdummy[D];
-      proj_col<D, R>(ys + L.g * GEO::T, hs + L.g * GEO::T, L.c, h, hz, sdummy);
-      store_col<R>(os + L.g * GEO::T + L.c * R, hz);
-    }
+    hess_project<D, R>(ys, vs, hs, os, srow, L, tg.ok, h);
     wave_sync();
     DPGO_STAMP_TILE(4);
-    {
-      const size_t base = (size_t)p0 * GEO::T;
-      dbl2* d2 = reinterpret_cast<dbl2*>(dout + base);
-      dbl2* h2 = reinterpret_cast<dbl2*>(Hd + base);
-#pragma unroll
-      for (int it = 0; it < SPN::NIT; ++it) {
-        const int pc = lane + 64 * it;
-        if (2 * pc < valid) {
-          const dbl2 hzv = reinterpret_cast<const dbl2*>(os)[pc];
-          const dbl2 zl = reinterpret_cast<const dbl2*>(vs)[pc];
-          dbl2 dn, hn;
-          if (first) {
-            dn.x = -zl.x;
-            dn.y = -zl.y;
-            hn.x = -hzv.x;
-            hn.y = -hzv.y;
-          } else {
-            dn.x = fma(beta, dv[it].x, -zl.x);
-            dn.y = fma(beta, dv[it].y, -zl.y);
-            hn.x = fma(beta, hv[it].x, -hzv.x);
-            hn.y = fma(beta, hv[it].y, -hzv.y);
-          }
-          st_stream<NTS>(d2 + pc, dn);
-          st_stream<NTS>(h2 + pc, hn);
-          part[0] = fma(dn.x, hn.x, part[0]);
-          part[0] = fma(dn.y, hn.y, part[0]);
-        }
-      }
-    }
+    hess_direction_update<NTS>(dout + (size_t)tg.p0 * GEO::T, Hd + (size_t)tg.p0 * GEO::T, os, vs, dv, hv, beta, first,
+                               tg.valid, lane, part[0]);
     wave_sync();
     DPGO_STAMP(0, 5);
     tile += ti_.step;
@@ -657,19 +673,13 @@ void k_tcg_update_span(const double* __restrict__ X, const double* __restrict__ 
   const bool ml_mode = ML ? true : (ml_omega > 0.0);  // (ML: compile-time)
   dbl2 xv[SPN::NIT], ev[SPN::NIT], dv[SPN::NIT], hv[SPN::NIT], rv[SPN::NIT];
   double drow[GEO::B];
-  int p0 = 0, valid = 0, i = 0;
-  bool ok = false;
+  TileGeo tg{};  // (one lane group per pose: okp is the whole test)
   // (PIPE: the geometry and the block-Jacobi row of the tile in flight, beside the ones of the tile being finished)
   [[maybe_unused]] double drow_n[GEO::B];
-  [[maybe_unused]] int p0_n = 0, valid_n = 0, i_n = 0;
-  [[maybe_unused]] bool ok_n = false;
-  auto request = [&](int tile, int& p0_, int& valid_, int& i_, bool& ok_, double (&drow_)[GEO::B]) {
-    p0_ = tile * GEO::P + L.wave * GEO::G;
-    const int npose = (n - p0_) < GEO::G ? (n - p0_) : GEO::G;
-    valid_ = npose > 0 ? npose * GEO::T : 0;
-    i_ = p0_ + L.g;
-    ok_ = (L.g < GEO::G) && (i_ < n);
-    const size_t base = (size_t)p0_ * GEO::T;
+  [[maybe_unused]] TileGeo tg_n{};
+  auto request = [&](int tile, TileGeo& t, double (&drow_)[GEO::B]) {
+    t = tile_geo<GEO>(tile, n, L);
+    const size_t base = (size_t)t.p0 * GEO::T;
     const dbl2* X2 = reinterpret_cast<const dbl2*>(X + base);
     const dbl2* g2 = reinterpret_cast<const dbl2*>(g + base);
     [[maybe_unused]] const dbl2* e2 = reinterpret_cast<const dbl2*>(eta + base);
@@ -679,7 +689,7 @@ void k_tcg_update_span(const double* __restrict__ X, const double* __restrict__ 
 #pragma unroll
     for (int it = 0; it < SPN::NIT; ++it) {
       const int pc = lane + 64 * it;
-      if (2 * pc < valid_) {
+      if (2 * pc < t.valid) {
         // (the iterate is only needed by the tangent projection of the block-Jacobi / unpreconditioned z; the multilevel
         // pre-smoothing step x1 = w Dinv r is not projected: 16 MB less per launch at 100k poses)
         if (!ml_mode) xv[it] = X2[pc];
@@ -695,12 +705,12 @@ void k_tcg_update_span(const double* __restrict__ X, const double* __restrict__ 
         }
       }
     }
-    if (ok_ && dinv) {
+    if (t.okp && dinv) {
 #pragma unroll
-      for (int k = 0; k < GEO::B; ++k) drow_[k] = dinv[(size_t)i_ * GEO::BB + L.c * GEO::B + k];
+      for (int k = 0; k < GEO::B; ++k) drow_[k] = dinv[(size_t)t.i * GEO::BB + L.c * GEO::B + k];
     }
   };
-  auto prefetch = [&](int tile) { request(tile, p0, valid, i, ok, drow); };
+  auto prefetch = [&](int tile) { request(tile, tg, drow); };
   // PIPE = 1: the next tile is requested as soon as the piece registers of this one are consumed -- behind the first
   // per-piece loop, which is the last reader of xv / ev / dv / hv / rv -- so its round trip runs under the block-Jacobi
   // step, the LDS passes and the stores of z instead of starting behind them.  The pieces it loads are other addresses
@@ -709,7 +719,7 @@ void k_tcg_update_span(const double* __restrict__ X, const double* __restrict__ 
     if constexpr (PIPE) {
       tile += ti_.step;
       have = tile < ti_.last;
-      if (have) request(tile, p0_n, valid_n, i_n, ok_n, drow_n);
+      if (have) request(tile, tg_n, drow_n);
     }
   };
   DPGO_TL_DECL;
@@ -724,25 +734,18 @@ void k_tcg_update_span(const double* __restrict__ X, const double* __restrict__ 
   bool have = tile < ti_.last;
   if (have) prefetch(tile);
 
-  if (st.rtr_stop || (!first && st.tcg_done)) {
-    if (blockIdx.x == 0 && threadIdx.x == 0) {
-      store_state(sout, st);
-      publish_progress(hflag, gen, st);
-    }
+  if (tcg_idle(st, !first)) {
+    tcg_publish(sout, st, hflag, gen);
     return;
   }
   double alpha, tau;
   const int mode = tcg_update_prologue(st, pin, nb_in, first, red, alpha, tau, &praw);
-  if (blockIdx.x == 0 && threadIdx.x == 0) {
-    store_state(sout, st);
-    tcg_store_coef<DEF>(coef, st, mode, alpha, tau);
-    publish_progress(hflag, gen, st);
-  }
+  tcg_publish(sout, st, hflag, gen, [&] { tcg_store_coef<DEF>(coef, st, mode, alpha, tau); });
 
   DPGO_STAMP(1, 2);
   double part[2] = {0.0, 0.0};
   while (have) {
-    const size_t base = (size_t)p0 * GEO::T;
+    const size_t base = (size_t)tg.p0 * GEO::T;
     [[maybe_unused]] dbl2* eta2 = reinterpret_cast<dbl2*>(eta + base);
     if (mode == 1) {  // workgroup-uniform: eta += tau * delta, then tCG stops
       // (r += tau * H delta with it: r = g + H eta holds at every exit of tCG, which is what the rho test reads, k_retract)
@@ -750,16 +753,9 @@ void k_tcg_update_span(const double* __restrict__ X, const double* __restrict__ 
 #pragma unroll
       for (int it = 0; it < SPN::NIT; ++it) {
         const int pc = lane + 64 * it;
-        if (2 * pc < valid) {
+        if (2 * pc < tg.valid) {
           dbl2 rr = rv[it];
-          if constexpr (!DEF) {
-            dbl2 e = ev[it];
-            e.x = fma(tau, dv[it].x, e.x);
-            e.y = fma(tau, dv[it].y, e.y);
-            eta2[pc] = e;
-          }
-          rr.x = fma(tau, hv[it].x, rr.x);
-          rr.y = fma(tau, hv[it].y, rr.y);
+          tcg_step_span<DEF>(tau, ev[it], dv[it], hv[it], eta2 + pc, rr);
           r2[pc] = rr;
         }
       }
@@ -769,7 +765,7 @@ void k_tcg_update_span(const double* __restrict__ X, const double* __restrict__ 
 #pragma unroll
       for (int it = 0; it < SPN::NIT; ++it) {
         const int pc = lane + 64 * it;
-        if (2 * pc < valid) {
+        if (2 * pc < tg.valid) {
           if (!ml_mode) reinterpret_cast<dbl2*>(ys)[pc] = xv[it];
           dbl2 rr = rv[it];
           if (mode == 2) {
@@ -780,14 +776,7 @@ void k_tcg_update_span(const double* __restrict__ X, const double* __restrict__ 
               eta2[pc] = zero;
             }
           } else {
-            if constexpr (!DEF) {
-              dbl2 e = ev[it];
-              e.x = fma(alpha, dv[it].x, e.x);
-              e.y = fma(alpha, dv[it].y, e.y);
-              eta2[pc] = e;
-            }
-            rr.x = fma(alpha, hv[it].x, rr.x);
-            rr.y = fma(alpha, hv[it].y, rr.y);
+            tcg_step_span<DEF>(alpha, ev[it], dv[it], hv[it], eta2 + pc, rr);
           }
           r2[pc] = rr;
           reinterpret_cast<dbl2*>(rs)[pc] = rr;
@@ -798,7 +787,7 @@ void k_tcg_update_span(const double* __restrict__ X, const double* __restrict__ 
       request_next(tile, have);
       wave_sync();
       double zz[R];
-      if (ok) {
+      if (tg.okp) {
         const double* rt = rs + L.g * GEO::T;
         if (dinv) {
           jacobi_col<D, R>(rt, drow, zz);
@@ -809,7 +798,7 @@ void k_tcg_update_span(const double* __restrict__ X, const double* __restrict__ 
         store_col<R>(zs + L.g * GEO::T + L.c * R, zz);
       }
       wave_sync();
-      if (ok) {
+      if (tg.okp) {
         double out[R], sdummy[D];
         if (ml_mode) {
 #pragma unroll
@@ -823,33 +812,16 @@ void k_tcg_update_span(const double* __restrict__ X, const double* __restrict__ 
         store_col<R>(os + L.g * GEO::T + L.c * R, out);
       }
       wave_sync();
-      if (z32) {
-        float2* zf = reinterpret_cast<float2*>(z32 + base);
-#pragma unroll
-        for (int it = 0; it < SPN::NIT; ++it) {
-          const int pc = lane + 64 * it;
-          if (2 * pc < valid) {
-            const dbl2 v = reinterpret_cast<const dbl2*>(os)[pc];
-            zf[pc] = make_float2((float)v.x, (float)v.y);
-          }
-        }
-      } else {
-        dbl2* z2 = reinterpret_cast<dbl2*>(z + base);
-#pragma unroll
-        for (int it = 0; it < SPN::NIT; ++it) {
-          const int pc = lane + 64 * it;
-          if (2 * pc < valid) z2[pc] = reinterpret_cast<const dbl2*>(os)[pc];
-        }
-      }
+      if (z32)
+        span_from_lds<D, R>(z32 + base, os, tg.valid);
+      else
+        span_from_lds<D, R>(z + base, os, tg.valid);
       wave_sync();
     }
     DPGO_STAMP(1, 5);
     if constexpr (PIPE) {
       if (have) {
-        p0 = p0_n;
-        valid = valid_n;
-        i = i_n;
-        ok = ok_n;
+        tg = tg_n;
 #pragma unroll
         for (int k = 0; k < GEO::B; ++k) drow[k] = drow_n[k];
       }
@@ -887,20 +859,13 @@ __global__ __launch_bounds__(kBlock, DPGO_LB_UPDATE) void k_tcg_update(const dou
   DevState st;
   load_state(st, sin);
   gen = state_gen(st, gen);
-  if (st.rtr_stop || (!first && st.tcg_done)) {
-    if (blockIdx.x == 0 && threadIdx.x == 0) {
-      store_state(sout, st);
-      publish_progress(hflag, gen, st);
-    }
+  if (tcg_idle(st, !first)) {
+    tcg_publish(sout, st, hflag, gen);
     return;
   }
   double alpha, tau;
   const int mode = tcg_update_prologue(st, pin, nb_in, first, red, alpha, tau);  // 0: step, 1: boundary step, 2: init
-  if (blockIdx.x == 0 && threadIdx.x == 0) {
-    store_state(sout, st);
-    tcg_store_coef<DEF>(coef, st, mode, alpha, tau);
-    publish_progress(hflag, gen, st);
-  }
+  tcg_publish(sout, st, hflag, gen, [&] { tcg_store_coef<DEF>(coef, st, mode, alpha, tau); });
 
   const LaneId L = lane_id<D>();
   const int ntiles = (n + GEO::P - 1) / GEO::P;
@@ -913,19 +878,8 @@ __global__ __launch_bounds__(kBlock, DPGO_LB_UPDATE) void k_tcg_update(const dou
     if (mode == 1) {  // workgroup-uniform
       if (ok) {
         // (r += tau * H delta with it: r = g + H eta holds at every exit of tCG, which is what the rho test reads)
-        double hd[R], rr[R];
-        if constexpr (!DEF) {
-          double e[R], dl[R];
-          load_col<R>(eta + off, e);
-          load_col<R>(delta + off, dl);
-#pragma unroll
-          for (int a = 0; a < R; ++a) e[a] = fma(tau, dl[a], e[a]);
-          store_col<R>(eta + off, e);
-        }
-        load_col<R>(Hd + off, hd);
-        load_col<R>(r + off, rr);
-#pragma unroll
-        for (int a = 0; a < R; ++a) rr[a] = fma(tau, hd[a], rr[a]);
+        double rr[R];
+        tcg_step_col<R, DEF>(tau, eta + off, delta + off, Hd + off, r + off, rr);
         store_col<R>(r + off, rr);
       }
       continue;
@@ -950,19 +904,7 @@ __global__ __launch_bounds__(kBlock, DPGO_LB_UPDATE) void k_tcg_update(const dou
           store_col<R>(eta + off, e);
         }
       } else {
-        double hd[R];
-        if constexpr (!DEF) {
-          double e[R], dl[R];
-          load_col<R>(eta + off, e);
-          load_col<R>(delta + off, dl);
-#pragma unroll
-          for (int a = 0; a < R; ++a) e[a] = fma(alpha, dl[a], e[a]);
-          store_col<R>(eta + off, e);
-        }
-        load_col<R>(Hd + off, hd);
-        load_col<R>(r + off, rr);
-#pragma unroll
-        for (int a = 0; a < R; ++a) rr[a] = fma(alpha, hd[a], rr[a]);
+        tcg_step_col<R, DEF>(alpha, eta + off, delta + off, Hd + off, r + off, rr);
       }
       store_col<R>(r + off, rr);
 #pragma unroll

@@ -3,6 +3,29 @@
 
 namespace dpgo_host {
 
+// f(kernel) for the update-kernel instance this handle's state selects:
+//   even pose tile size (span kernels)   ML    DEF (a solve that keeps its directions)   PIPE
+//     block-Jacobi / no preconditioner   0     dirs_on                                   0
+//     multilevel mode (ml_omega > 0)     1     dirs_on                                   pipe ? kUpdatePipe<D, R, DEF> : 0
+//   odd pose tile size: the generic kernel, k_tcg_update<D, R, DEF>
+// ML = 1 is its own instance (3 waves per SIMD).  PIPE: DPGO_UPDATE_PIPE=0 selects the instances that request the next tile
+// behind the last store (same bits, kernels/tcg.h); only the multilevel instances that hold their three waves with a tile in
+// flight have a PIPE = 1 form (kUpdatePipe), and only a launch in which a workgroup can hold a second tile has one to request
+// early: with a tile per workgroup -- every block up to the resident count, sphere2500's 40 tiles -- the reference-order
+// instance runs.
+template <int D, int R, class F>
+int dispatch_tcg_update_mode(const dpgo_problem_s* p, bool ml_mode, F&& f) {
+  const bool def = p->dirs_on;
+  if constexpr (Span<D, R, 1>::kOk) {
+    if (!ml_mode) return def ? f(k_tcg_update_span<D, R, 0, 1, 0>) : f(k_tcg_update_span<D, R, 0, 0, 0>);
+    const bool pipe = options().update_pipe != 0 && pose_tiles(p->n, p->b) > p->grid_u(ml_mode);
+    if (def) return pipe ? f(k_tcg_update_span<D, R, 1, 1, kUpdatePipe<D, R, 1>>) : f(k_tcg_update_span<D, R, 1, 1, 0>);
+    return pipe ? f(k_tcg_update_span<D, R, 1, 0, kUpdatePipe<D, R, 0>>) : f(k_tcg_update_span<D, R, 1, 0, 0>);
+  } else {
+    return def ? f(k_tcg_update<D, R, 1>) : f(k_tcg_update<D, R>);
+  }
+}
+
 int launch_tcg_update(dpgo_problem_s* p, const double* dinv, int first, double* z_out,
                       double ml_omega) {
   const bool ml_mode = ml_omega > 0.0;
@@ -16,31 +39,22 @@ int launch_tcg_update(dpgo_problem_s* p, const double* dinv, int first, double* 
   float* z32 = (ml_omega > 0.0 && !p->ml.empty() && z_out == p->ml[0].x1 && p->ml_vec32_active()) ? p->ml[0].x1f : nullptr;
   CHK(dispatch_dr(p->d, p->r, [&](auto Dc, auto Rc) {
     constexpr int D = decltype(Dc)::value, R = decltype(Rc)::value;
-    // (the span kernels end in the fp32 output, the generic one has none)
+    // (odd tile size: the generic kernel has no fp32 output -- resolve_tcg_storage keeps such blocks off the symmetric
+    // storage, hence off the cycle's fp32 vectors; a state that says otherwise is refused instead of dropping z32)
+    if (!Span<D, R, 1>::kOk && z32) return fail(DPGO_ERR_STATE, "fp32 cycle vectors need the span kernels (even pose tile size)");
     // (a solve that keeps its directions: the deferred instances get neither delta nor eta, only the step-length array)
     const bool def = p->dirs_on;
-    auto go = [&](auto kernel, auto... z32_arg) {
-      return launch(kernel, g, 0, p->stream, p->x1, p->g1, dinv, def ? nullptr : p->delta.get(), p->Hd,
-                    def ? nullptr : p->eta.get(), p->rr, zt, p->pA.in(), p->pA.count(), pb, p->state.in(),
-                    p->state.out(), first, p->n, p->hflag, p->gen, ml_omega, def ? p->dirs_coef.get() : nullptr,
-                    z32_arg...);
-    };
-    if constexpr (Span<D, R, 1>::kOk) {
-      // (its own instance for the multilevel mode: 3 waves per SIMD)
-      // (DPGO_UPDATE_PIPE=0: the instances that request the next tile behind the last store -- same bits, kernels/tcg.h)
-      // (only the multilevel instances that hold their three waves with a tile in flight have a PIPE = 1 form)
-      if (!ml_mode) return def ? go(k_tcg_update_span<D, R, 0, 1, 0>, z32) : go(k_tcg_update_span<D, R, 0, 0, 0>, z32);
-      // (... and only a launch in which a workgroup can hold a second tile has one to request early: with a tile per
-      // workgroup -- every block up to the resident count, sphere2500's 40 tiles -- the reference-order instance runs)
-      const bool pipe = options().update_pipe != 0 && pose_tiles(p->n, p->b) > g;
-      if (def) return go(pipe ? k_tcg_update_span<D, R, 1, 1, kUpdatePipe<D, R, 1>> : k_tcg_update_span<D, R, 1, 1, 0>, z32);
-      return go(pipe ? k_tcg_update_span<D, R, 1, 0, kUpdatePipe<D, R, 0>> : k_tcg_update_span<D, R, 1, 0, 0>, z32);
-    } else {
-      // (odd tile size: the generic kernel has no fp32 output -- resolve_tcg_storage keeps such blocks off the symmetric
-      // storage, hence off the cycle's fp32 vectors; a state that says otherwise is refused instead of dropping z32)
-      if (z32) return fail(DPGO_ERR_STATE, "fp32 cycle vectors need the span kernels (even pose tile size)");
-      return def ? go(k_tcg_update<D, R, 1>) : go(k_tcg_update<D, R>);
-    }
+    return dispatch_tcg_update_mode<D, R>(p, ml_mode, [&](auto kernel) {
+      auto go = [&](auto... z32_arg) {
+        return launch(kernel, g, 0, p->stream, p->x1, p->g1, dinv, def ? nullptr : p->delta.get(), p->Hd,
+                      def ? nullptr : p->eta.get(), p->rr, zt, p->pA.in(), p->pA.count(), pb, p->state.in(),
+                      p->state.out(), first, p->n, p->hflag, p->gen, ml_omega, def ? p->dirs_coef.get() : nullptr,
+                      z32_arg...);
+      };
+      // (the span kernels end in the fp32 output, the generic one has none)
+      if constexpr (Span<D, R, 1>::kOk) return go(z32);
+      else return go();
+    });
   }));
   HIPC(hipGetLastError());
   p->state.advance();
