@@ -11,80 +11,6 @@
 namespace dpgo_host {
 namespace {
 
-// ---------------------------------------------------------------- small dense linear algebra (row-major n x n)
-// Cholesky A = L L^T in place (lower triangle); false if a pivot is not positive
-bool cholesky(std::vector<double>& A, int n) {
-  for (int j = 0; j < n; ++j) {
-    double s = A[j * n + j];
-    for (int k = 0; k < j; ++k) s -= A[j * n + k] * A[j * n + k];
-    if (!(s > 0.0)) return false;
-    const double l = std::sqrt(s);
-    A[j * n + j] = l;
-    for (int i = j + 1; i < n; ++i) {
-      double t = A[i * n + j];
-      for (int k = 0; k < j; ++k) t -= A[i * n + k] * A[j * n + k];
-      A[i * n + j] = t / l;
-    }
-    for (int k = j + 1; k < n; ++k) A[j * n + k] = 0.0;
-  }
-  return true;
-}
-
-// symmetric eigen-decomposition by cyclic Jacobi: ascending eigenvalues w, eigenvectors in the COLUMNS of V
-void jacobi_eig(std::vector<double> A, int n, std::vector<double>& w, std::vector<double>& V) {
-  V.assign((size_t)n * n, 0.0);
-  for (int i = 0; i < n; ++i) V[i * n + i] = 1.0;
-  for (int sweep = 0; sweep < 100; ++sweep) {
-    double off = 0.0, tot = 0.0;
-    for (int i = 0; i < n; ++i)
-      for (int j = 0; j < n; ++j) (i == j ? tot : off) += A[i * n + j] * A[i * n + j];
-    if (off <= 1e-32 * (tot + off) || off == 0.0) break;
-    for (int p = 0; p < n - 1; ++p)
-      for (int q = p + 1; q < n; ++q) {
-        const double apq = A[p * n + q];
-        if (apq == 0.0) continue;
-        const double theta = (A[q * n + q] - A[p * n + p]) / (2.0 * apq);
-        const double t = (theta >= 0 ? 1.0 : -1.0) / (std::fabs(theta) + std::sqrt(theta * theta + 1.0));
-        const double c = 1.0 / std::sqrt(t * t + 1.0), s = t * c;
-        for (int k = 0; k < n; ++k) {  // A <- A J
-          const double akp = A[k * n + p], akq = A[k * n + q];
-          A[k * n + p] = c * akp - s * akq;
-          A[k * n + q] = s * akp + c * akq;
-        }
-        for (int k = 0; k < n; ++k) {  // A <- J^T A
-          const double apk = A[p * n + k], aqk = A[q * n + k];
-          A[p * n + k] = c * apk - s * aqk;
-          A[q * n + k] = s * apk + c * aqk;
-        }
-        for (int k = 0; k < n; ++k) {
-          const double vkp = V[k * n + p], vkq = V[k * n + q];
-          V[k * n + p] = c * vkp - s * vkq;
-          V[k * n + q] = s * vkp + c * vkq;
-        }
-      }
-  }
-  std::vector<int> ord(n);
-  for (int i = 0; i < n; ++i) ord[i] = i;
-  std::stable_sort(ord.begin(), ord.end(), [&](int a, int b) { return A[a * n + a] < A[b * n + b]; });
-  w.resize(n);
-  std::vector<double> Vs((size_t)n * n);
-  for (int j = 0; j < n; ++j) {
-    w[j] = A[ord[j] * n + ord[j]];
-    for (int i = 0; i < n; ++i) Vs[i * n + j] = V[i * n + ord[j]];
-  }
-  V.swap(Vs);
-}
-
-// X = L^-T Y for lower-triangular L (n x n) and Y (n x m), in place
-void solve_lt(const std::vector<double>& Lm, int n, std::vector<double>& Y, int m) {
-  for (int i = n - 1; i >= 0; --i)
-    for (int j = 0; j < m; ++j) {
-      double s = Y[i * m + j];
-      for (int k = i + 1; k < n; ++k) s -= Lm[k * n + i] * Y[k * m + j];
-      Y[i * m + j] = s / Lm[i * n + i];
-    }
-}
-
 // ---------------------------------------------------------------- the solver's device state
 // CW = W C(X) (k_cert_apply) on `g` workgroups: the symmetric copy of Q at one pose per d+1 lanes, or Q at the handle's split
 int launch_cert_apply(dpgo_problem_s* p, int d, int r, bool sym, int g, const double* S, const double* W, double* CW,
@@ -136,6 +62,9 @@ struct Cert {
   static constexpr int kCoefSlots = 8;
   static constexpr int kCoefCap = kCertMaxOut * kCertMaxBlocks * 36;
   static constexpr int kGramWg = 512;  // workgroups of k_cert_gram (partials: kGramWg x kCertMaxPairs x 36)
+
+  explicit Cert(dpgo_problem_s* h) : p(h), d(h->d), r(h->r), n(h->n) {}
+  explicit Cert(Team& t) : p(t.h[0]), team(&t), d(p->d), r(p->r), n(t.N) {}
 
   size_t vec_bytes() const { return (size_t)n * (d + 1) * r * sizeof(double); }
   int flat_grid() const {
@@ -263,16 +192,6 @@ struct Cert {
   }
 };
 
-// r x r identity / diagonal helpers of the coefficient matrices
-void put_block(std::vector<double>& M, int nb, int r, int k, int j, const std::vector<double>& blk) {
-  std::copy(blk.begin(), blk.end(), M.begin() + ((size_t)k * nb + j) * r * r);
-}
-std::vector<double> eye(int r, double s = 1.0) {
-  std::vector<double> I((size_t)r * r, 0.0);
-  for (int a = 0; a < r; ++a) I[a * r + a] = s;
-  return I;
-}
-
 // max_i max diag(Q_ii)
 int q_scale(dpgo_problem_s* p, DevBuf<double>& dv, double* out) {
   const int g = (p->n + kBlock - 1) / kBlock;
@@ -329,11 +248,7 @@ int certify_impl(dpgo_problem_s* p, const double* X, const dpgo_certify_params* 
   *res = dpgo_certify_result{};
   res->status = DPGO_CERT_NOT_CONVERGED;
 
-  Cert c;
-  c.p = p;
-  c.d = p->d;
-  c.r = p->r;
-  c.n = p->n;
+  Cert c(p);
   c.precond = precond;
   c.shift = prm.precond_shift;
   CHK(c.init());
@@ -360,6 +275,8 @@ int certify_impl(dpgo_problem_s* p, const double* X, const dpgo_certify_params* 
 
 // The eigen-solver on Cert's operator, one handle or a team alike.  symmetry_defect (a team): the probe of the operator's
 // symmetry from the two products the solver makes anyway (below).
+// This function is the device side: vectors, launches, Gram read-backs, loop control.  Every coefficient matrix it hands to
+// Cert::combine, and every decision taken from a Gram block, comes from cert_dense.h.
 int cert_run(Cert& c, const double* X, const dpgo_certify_params& prm, double scale, dpgo_certify_result* res,
              double* witness, bool witness_on_host, std::chrono::steady_clock::time_point t0, double* symmetry_defect) {
   dpgo_problem_s* p = c.p;
@@ -370,95 +287,33 @@ int cert_run(Cert& c, const double* X, const dpgo_certify_params& prm, double sc
 
   // ---- deflation space: rows of X and the translation indicator, kept where one product confirms them null
   double *K1, *CK0, *CK1, *Z0, *Z1;
-  CHK(c.vec(&K1));
-  CHK(c.vec(&CK0));
-  CHK(c.vec(&CK1));
-  CHK(c.vec(&Z0));
-  CHK(c.vec(&Z1));
+  for (double** v : {&K1, &CK0, &CK1, &Z0, &Z1}) CHK(c.vec(v));
   CHK(dispatch_dr(c.d, r, [&](auto D, auto R) {
     return launch(k_cert_indicator<D, R>, c.flat_grid(), 0, p->stream, K1, c.n);
   }));
   HIPC(hipGetLastError());
   CHK(c.apply(X, CK0));
   CHK(c.apply(K1, CK1));
-  const int m0 = 2 * r;
-  std::vector<double> Gk((size_t)m0 * m0), Gc((size_t)m0 * m0);
-  {
-    std::vector<double> G;
-    CHK(c.gram({X, K1, CK0, CK1}, {{0, 0}, {0, 1}, {1, 1}, {2, 2}, {2, 3}, {3, 3}}, G));
-    auto fill = [&](std::vector<double>& M, int base) {
-      const int blk[2][2] = {{0, 1}, {1, 2}};
-      for (int bx = 0; bx < 2; ++bx)
-        for (int by = 0; by < 2; ++by)
-          for (int a = 0; a < r; ++a)
-            for (int b = 0; b < r; ++b) {
-              const int k = base + blk[bx][by];
-              const double v = (bx <= by) ? G[(size_t)k * r * r + a * r + b] : G[(size_t)k * r * r + b * r + a];
-              M[(size_t)(bx * r + a) * m0 + by * r + b] = v;
-            }
-    };
-    fill(Gk, 0);
-    fill(Gc, 3);
-  }
-  std::vector<double> sk, Uk;
-  jacobi_eig(Gk, m0, sk, Uk);
-  const double smax = std::max(sk.back(), 0.0);
-  std::vector<int> keep;
-  for (int i = 0; i < m0; ++i)
-    if (sk[i] > 1e-10 * smax) keep.push_back(i);
-  const int m1 = (int)keep.size();
-  // orthonormal basis B^T K of span(K), B = U_keep diag(s^-1/2): m0 x m1
-  std::vector<double> Bm((size_t)m0 * m1);
-  for (int i = 0; i < m0; ++i)
-    for (int j = 0; j < m1; ++j) Bm[(size_t)i * m1 + j] = Uk[(size_t)i * m0 + keep[j]] / std::sqrt(sk[keep[j]]);
-  // |C z|^2 on that basis: B^T Gc B, and its near-null eigen-directions
-  std::vector<double> H((size_t)m1 * m1, 0.0);
-  for (int i = 0; i < m1; ++i)
-    for (int j = 0; j < m1; ++j) {
-      double s = 0.0;
-      for (int a = 0; a < m0; ++a)
-        for (int b = 0; b < m0; ++b) s += Bm[(size_t)a * m1 + i] * Gc[(size_t)a * m0 + b] * Bm[(size_t)b * m1 + j];
-      H[(size_t)i * m1 + j] = s;
-    }
-  std::vector<double> mu, Vh;
-  if (m1 > 0) jacobi_eig(H, m1, mu, Vh);
-  int mz = 0;
-  double cz = 0.0;
-  for (int i = 0; i < m1; ++i)
-    if (std::sqrt(std::max(mu[i], 0.0)) <= null_tol) {
-      ++mz;
-      cz = std::max(cz, std::sqrt(std::max(mu[i], 0.0)));
-    }
-  mz = std::min(mz, 2 * r);
-  res->deflated = mz;
-  res->deflation_residual = cz;
-  const int nzb = (mz + r - 1) / r;  // Z blocks (rows beyond mz are zero)
-  std::vector<double> M((size_t)2 * 2 * r * r, 0.0);
+  std::vector<double> G;
+  CHK(c.gram({X, K1, CK0, CK1}, {{0, 0}, {0, 1}, {1, 1}, {2, 2}, {2, 3}, {3, 3}}, G));
+  const DeflationBasis defl = deflation_basis(G, r, null_tol);
+  res->deflated = defl.mz;
+  res->deflation_residual = defl.cz;
+  const int nzb = defl.blocks(r);  // Z blocks (rows beyond mz are zero)
   // the reported |C z| (in place on CK0, CK1: a team's symmetry probe reads C X first, so there it runs behind the probe)
   auto deflation_residual = [&]() -> int {
     if (nzb == 0) return DPGO_OK;
     // mu is an eigenvalue of a Gram matrix of squares, so sqrt(mu) carries sqrt(round-off) of the
     // LARGEST |C k| (1e-8 of it: an exactly null t beside a non-stationary X reads 1e-11 scale).  C Z is the same
     // combination of C K, and its row norms have no such cancellation.
-    CHK(c.combine({CK0, CK1}, {CK0, CK1}, M));
+    CHK(c.combine({CK0, CK1}, {CK0, CK1}, defl.M));
     std::vector<double> Gz;
     CHK(c.gram({CK0, CK1}, {{0, 0}, {1, 1}}, Gz));
-    double v = 0.0;
-    for (int q = 0; q < mz; ++q)
-      v = std::max(v, std::sqrt(std::max(Gz[(size_t)(q / r) * r * r + (q % r) * r + (q % r)], 0.0)));
-    res->deflation_residual = v;
+    res->deflation_residual = max_row_norm(Gz, r, defl.mz);
     return DPGO_OK;
   };
   if (nzb > 0) {
-    // Z rows = (B V_keep)^T K: coefficient of K row a (block j = a / r) for Z row q (block k = q / r)
-    for (int q = 0; q < mz; ++q)
-      for (int a = 0; a < m0; ++a) {
-        double s = 0.0;
-        for (int j = 0; j < m1; ++j) s += Bm[(size_t)a * m1 + j] * Vh[(size_t)j * m1 + q];
-        const int k = q / r, bq = q % r, jb = a / r, ar = a % r;
-        M[((size_t)k * 2 + jb) * r * r + ar * r + bq] = s;
-      }
-    CHK(c.combine({X, K1}, {Z0, Z1}, M));
+    CHK(c.combine({X, K1}, {Z0, Z1}, defl.M));
     if (!symmetry_defect) CHK(deflation_residual());
   }
   std::vector<const double*> Zb;
@@ -488,68 +343,32 @@ int cert_run(Cert& c, const double* X, const dpgo_certify_params& prm, double sc
       if (out != V) HIPC(hipMemcpyAsync(out, V, c.vec_bytes(), hipMemcpyDeviceToDevice, p->stream));
       return DPGO_OK;
     }
-    std::vector<double> G;
-    CHK(c.gram(B, pairs, G));
-    const int nb = (int)B.size();
-    std::vector<double> M((size_t)nb * r * r, 0.0);
-    put_block(M, nb, r, 0, 0, eye(r));
-    // out row b = v_b - sum_q G[b][q] z_q: coefficient of z_q (row a = q of block j) for output row b is -G[b][a]
-    for (int j = 1; j < nb; ++j)
-      for (int a = 0; a < r; ++a)
-        for (int b = 0; b < r; ++b) M[(size_t)j * r * r + a * r + b] = -G[(size_t)(j - 1) * r * r + b * r + a];
-    return c.combine(B, {out}, M);
+    std::vector<double> Gp;
+    CHK(c.gram(B, pairs, Gp));
+    return c.combine(B, {out}, projection_coefficients(Gp, (int)B.size(), r));
   };
   // W <- Ritz vectors of W (orthonormalised against itself, rotated to diagonalise W C W^T); theta ascending
-  std::vector<double> theta(r, 0.0);
-  {
-    CHK(project(W, nullptr, W2));
-    std::vector<double> G;
-    CHK(c.gram({W2}, {{0, 0}}, G));
-    for (int a = 0; a < r; ++a) G[a * r + a] += 1e-300;
-    if (!cholesky(G, r)) return fail(DPGO_ERR_STATE, "certify: start block is rank deficient");
-    std::vector<double> Y = eye(r);
-    solve_lt(G, r, Y, r);  // W = L^-1 W2 -> coefficient (row b of W gets sum_a Linv[b][a] w2_a): M[a][b] = Y[a][b]
-    CHK(c.combine({W2}, {W}, Y));
-    CHK(c.apply(W, CW));
-    std::vector<double> H;
-    CHK(c.gram({W, CW}, {{0, 1}}, H));
-    for (int a = 0; a < r; ++a)
-      for (int b = 0; b < a; ++b) H[a * r + b] = H[b * r + a] = 0.5 * (H[a * r + b] + H[b * r + a]);
-    std::vector<double> w, V;
-    jacobi_eig(H, r, w, V);
-    CHK(c.combine({W, CW}, {W2, CW2}, [&] {
-      std::vector<double> M((size_t)2 * 2 * r * r, 0.0);
-      put_block(M, 2, r, 0, 0, V);
-      put_block(M, 2, r, 1, 1, V);
-      return M;
-    }()));
-    std::swap(W, W2);
-    std::swap(CW, CW2);
-    theta = w;
-  }
+  std::vector<double> theta(r, 0.0), M;
+  CHK(project(W, nullptr, W2));
+  CHK(c.gram({W2}, {{0, 0}}, G));
+  if (!start_block(G, r, M)) return fail(DPGO_ERR_STATE, "certify: start block is rank deficient");
+  CHK(c.combine({W2}, {W}, M));
+  CHK(c.apply(W, CW));
+  CHK(c.gram({W, CW}, {{0, 1}}, G));
+  CHK(c.combine({W, CW}, {W2, CW2}, ritz_rotation(G, r, theta)));
+  std::swap(W, W2);
+  std::swap(CW, CW2);
   if (symmetry_defect) {
     // A team's pieces form a symmetric operator only if both owners of every shared edge hold the same weight and
     // activity for it.  The start block W and the iterate X have both been multiplied by now (CW above, CK0 = C X of the
-    // deflation step): for a symmetric C the r x r blocks W (C X)^T and (C W) X^T are equal up to rounding.
-    // The bound: each entry is an inner product of length L = (d+1) N; its a-priori worst-case rounding error is
-    // gamma_L |w| |C x| <= L u |W|_F scale' |X|_F with u = 2^-53 and scale' = |C|_2 <= a small multiple of scale (a row of
-    // C holds the pose's own block and its few neighbours'); the rounding inside the two products C X and C W is of
-    // the order (row length) u scale |X|_F |W|_F, far below L u for any team.  Two such entries are subtracted, and a
-    // factor 4 covers scale' / scale: 8 L u, relative to scale |W|_F |X|_F.
-    std::vector<double> G;
+    // deflation step): for a symmetric C the r x r blocks W (C X)^T and (C W) X^T are equal up to rounding
+    // (symmetry_probe's bound).
     CHK(c.gram({W, CK0, CW, X}, {{0, 1}, {2, 3}, {0, 0}, {3, 3}}, G));
-    double dmax = 0.0, w2 = 0.0, x2 = 0.0;
-    for (int e = 0; e < r * r; ++e) dmax = std::max(dmax, std::fabs(G[e] - G[(size_t)r * r + e]));
-    for (int a = 0; a < r; ++a) {
-      w2 += G[(size_t)2 * r * r + a * r + a];
-      x2 += G[(size_t)3 * r * r + a * r + a];
-    }
-    const double defect = dmax / (scale * std::sqrt(w2) * std::sqrt(x2));
-    *symmetry_defect = defect;
-    const double bound = 8.0 * (double)(c.d + 1) * (double)c.n * std::ldexp(1.0, -53);
-    if (!(defect <= bound))
+    const SymmetryProbe probe = symmetry_probe(G, r, scale, c.d, c.n);
+    *symmetry_defect = probe.defect;
+    if (!(probe.defect <= probe.bound))
       return fail(DPGO_ERR_STATE, "team certificate: agents hold different weights or activity for a shared edge "
-                                  "(symmetry defect " + std::to_string(defect) + " of scale)");
+                                  "(symmetry defect " + std::to_string(probe.defect) + " of scale)");
     CHK(deflation_residual());
   }
   bool have_p = false, negative = false;
@@ -557,13 +376,7 @@ int cert_run(Cert& c, const double* X, const dpgo_certify_params& prm, double sc
   int it = 0;
   for (; it < prm.max_iterations; ++it) {
     // residual block Rs = CW - diag(theta) W and its row norms
-    {
-      std::vector<double> M((size_t)2 * r * r, 0.0);
-      put_block(M, 2, r, 0, 0, eye(r));
-      for (int a = 0; a < r; ++a) M[(size_t)r * r + a * r + a] = -theta[a];
-      CHK(c.combine({CW, W}, {Rs}, M));
-    }
-    std::vector<double> G;
+    CHK(c.combine({CW, W}, {Rs}, residual_coefficients(theta, r)));
     CHK(c.gram({Rs}, {{0, 0}}, G));
     resid0 = std::sqrt(std::max(G[0], 0.0));
     if (theta[0] < -eta) negative = true;
@@ -572,8 +385,8 @@ int cert_run(Cert& c, const double* X, const dpgo_certify_params& prm, double sc
     CHK(c.precondition(Rs, T));
     CHK(project(T, W, T));
     CHK(c.apply(T, CT));
-    // Rayleigh-Ritz on S = [W, T, P]
-    const int ns = have_p ? 3 : 2, m = ns * r;
+    // Rayleigh-Ritz on S = [W, T, P]: the upper-triangle blocks of S S^T, then of S (C S)^T
+    const int ns = have_p ? 3 : 2;
     std::vector<const double*> Sb{W, T, P}, CSb{CW, CT, CP};
     std::vector<const double*> B;
     std::vector<std::pair<int, int>> pairs;
@@ -583,38 +396,9 @@ int cert_run(Cert& c, const double* X, const dpgo_certify_params& prm, double sc
       for (int j = i; j < ns; ++j) pairs.push_back({i, j});
     for (int i = 0; i < ns; ++i)
       for (int j = i; j < ns; ++j) pairs.push_back({i, ns + j});
-    std::vector<double> Gr;
-    CHK(c.gram(B, pairs, Gr));
-    std::vector<double> Gs((size_t)m * m), Hs((size_t)m * m);
-    {
-      int k = 0;
-      for (int pass = 0; pass < 2; ++pass) {
-        std::vector<double>& M = pass == 0 ? Gs : Hs;
-        for (int i = 0; i < ns; ++i)
-          for (int j = i; j < ns; ++j, ++k)
-            for (int a = 0; a < r; ++a)
-              for (int b = 0; b < r; ++b) {
-                const double v = Gr[(size_t)k * r * r + a * r + b];
-                M[(size_t)(i * r + a) * m + j * r + b] = v;
-                M[(size_t)(j * r + b) * m + i * r + a] = v;
-              }
-      }
-      for (int i = 0; i < m; ++i)  // (C symmetric: average the two computed halves of the diagonal blocks)
-        for (int j = 0; j < i; ++j) Hs[(size_t)i * m + j] = Hs[(size_t)j * m + i] = 0.5 * (Hs[(size_t)i * m + j] + Hs[(size_t)j * m + i]);
-    }
-    // Jacobi scaling, Cholesky of the Gram matrix; a (near) dependent P is dropped and the step repeated without it
-    std::vector<double> dsc(m);
-    for (int i = 0; i < m; ++i) dsc[i] = Gs[(size_t)i * m + i] > 0 ? 1.0 / std::sqrt(Gs[(size_t)i * m + i]) : 0.0;
-    std::vector<double> Lm(Gs);
-    for (int i = 0; i < m; ++i)
-      for (int j = 0; j < m; ++j) Lm[(size_t)i * m + j] *= dsc[i] * dsc[j];
-    bool okc = cholesky(Lm, m);
-    if (okc) {
-      double dmin = INFINITY, dmax = 0.0;
-      for (int i = 0; i < m; ++i) dmin = std::min(dmin, Lm[(size_t)i * m + i]), dmax = std::max(dmax, Lm[(size_t)i * m + i]);
-      okc = dmin > 1e-7 * dmax;
-    }
-    if (!okc) {
+    CHK(c.gram(B, pairs, G));
+    // a (near) dependent P is dropped and the step repeated without it
+    if (rayleigh_ritz(G, ns, r, theta, M) == Ritz::dependent) {
       if (have_p) {
         have_p = false;
         --it;
@@ -622,69 +406,20 @@ int cert_run(Cert& c, const double* X, const dpgo_certify_params& prm, double sc
       }
       break;  // T depends on W: the iteration has stagnated
     }
-    // A = L^-1 (D Hs D) L^-T; eigenvectors V; coefficients Y = D L^-T V[:, :r]
-    std::vector<double> A((size_t)m * m);
-    for (int i = 0; i < m; ++i)
-      for (int j = 0; j < m; ++j) A[(size_t)i * m + j] = Hs[(size_t)i * m + j] * dsc[i] * dsc[j];
-    // A <- L^-1 A (forward substitution on columns), then A <- A L^-T
-    for (int j = 0; j < m; ++j)
-      for (int i = 0; i < m; ++i) {
-        double s = A[(size_t)i * m + j];
-        for (int k = 0; k < i; ++k) s -= Lm[(size_t)i * m + k] * A[(size_t)k * m + j];
-        A[(size_t)i * m + j] = s / Lm[(size_t)i * m + i];
-      }
-    for (int i = 0; i < m; ++i)
-      for (int j = 0; j < m; ++j) {
-        double s = A[(size_t)i * m + j];
-        for (int k = 0; k < j; ++k) s -= A[(size_t)i * m + k] * Lm[(size_t)j * m + k];
-        A[(size_t)i * m + j] = s / Lm[(size_t)j * m + j];
-      }
-    for (int i = 0; i < m; ++i)
-      for (int j = 0; j < i; ++j) A[(size_t)i * m + j] = A[(size_t)j * m + i] = 0.5 * (A[(size_t)i * m + j] + A[(size_t)j * m + i]);
-    std::vector<double> w, V;
-    jacobi_eig(A, m, w, V);
-    std::vector<double> Y((size_t)m * r);
-    for (int i = 0; i < m; ++i)
-      for (int j = 0; j < r; ++j) Y[(size_t)i * r + j] = V[(size_t)i * m + j];
-    solve_lt(Lm, m, Y, r);
-    for (int i = 0; i < m; ++i)
-      for (int j = 0; j < r; ++j) Y[(size_t)i * r + j] *= dsc[i];
-    // W' = S Y, P' = [T P] Y_TP, CW' = CS Y, CP' = [CT CP] Y_TP   (inputs W T P CW CT CP)
-    {
-      const int nb = 2 * ns;
-      std::vector<double> M((size_t)4 * nb * r * r, 0.0);
-      for (int j = 0; j < ns; ++j)
-        for (int a = 0; a < r; ++a)
-          for (int b = 0; b < r; ++b) {
-            const double y = Y[(size_t)(j * r + a) * r + b];
-            M[((size_t)0 * nb + j) * r * r + a * r + b] = y;
-            M[((size_t)2 * nb + ns + j) * r * r + a * r + b] = y;
-            if (j > 0) {
-              M[((size_t)1 * nb + j) * r * r + a * r + b] = y;
-              M[((size_t)3 * nb + ns + j) * r * r + a * r + b] = y;
-            }
-          }
-      CHK(c.combine(B, {W2, P2, CW2, CP2}, M));
-    }
+    CHK(c.combine(B, {W2, P2, CW2, CP2}, M));
     std::swap(W, W2);
     std::swap(P, P2);
     std::swap(CW, CW2);
     std::swap(CP, CP2);
     have_p = true;
-    for (int a = 0; a < r; ++a) theta[a] = w[a];
   }
   const bool converged = resid0 <= tol;
   if (theta[0] < -eta) negative = true;
   // the reported pair: the first Ritz vector, projected onto the complement of Z once more, normalised, and its exact
   // Rayleigh quotient
   CHK(project(W, nullptr, W2));
-  std::vector<double> G;
   CHK(c.gram({W2}, {{0, 0}}, G));
-  {
-    std::vector<double> M((size_t)r * r, 0.0);
-    for (int a = 0; a < r; ++a) M[a * r + a] = G[a * r + a] > 0 ? 1.0 / std::sqrt(G[a * r + a]) : 0.0;
-    CHK(c.combine({W2}, {W}, M));
-  }
+  CHK(c.combine({W2}, {W}, normalisation_coefficients(G, r)));
   std::vector<double> wcw;
   CHK(c.apply(W, CW, &wcw));
   res->lambda_min = wcw[0];
@@ -856,12 +591,7 @@ int team_certify_impl(const dpgo_team_member* mem, int n_members, const double* 
   out->members = n_members;
   out->poses = t.N;
   dpgo_problem_s* p0 = t.h[0];
-  Cert c;
-  c.p = p0;
-  c.team = &t;
-  c.d = p0->d;
-  c.r = p0->r;
-  c.n = t.N;
+  Cert c(t);
   c.shift = prm.precond_shift;
   CHK(set_device(p0));
   CHK(c.init());
@@ -896,6 +626,26 @@ int team_certify_impl(const dpgo_team_member* mem, int n_members, const double* 
     }
   }
   return cert_run(c, X, prm, scale, &out->cert, witness, false, t0, &out->symmetry_defect);
+}
+
+// The staircase's step along a witness over n poses.  SE-Sync's rule: the first of alpha0, alpha0 / 2, ... whose retraction
+// decreases f below f0 and leaves the gradient above the tolerance (the next solve must not stop at once); alpha0 moves
+// each pose by ~0.1 for a witness spread over all poses.  trial(alpha, &f, &gn) makes the step and evaluates it.
+// alpha, trials: the accepted step (0 if none) and the trials made, either may be null
+template <class Trial>
+int halving_search(int n, double f0, double grad_tol, Trial trial, double* alpha, int* trials) {
+  double a = 0.1 * std::sqrt((double)n);
+  for (int k = 0; k < 60; ++k, a *= 0.5) {
+    double f = 0.0, gn = 0.0;
+    CHK(trial(a, &f, &gn));
+    if (trials) *trials = k + 1;
+    if (f < f0 && gn > grad_tol) {
+      if (alpha) *alpha = a;
+      return DPGO_OK;
+    }
+  }
+  if (alpha) *alpha = 0.0;
+  return fail(DPGO_ERR_STATE, "certify: no step along the witness decreases f");
 }
 
 }  // namespace
@@ -967,12 +717,7 @@ int dpgo_team_certificate_apply_gram_device(const dpgo_team_member* members, int
   CHK(team_check(members, n_members, t));
   dpgo_problem_s* p0 = t.h[0];
   CHK(set_device(p0));
-  Cert c;
-  c.p = p0;
-  c.team = &t;
-  c.d = p0->d;
-  c.r = p0->r;
-  c.n = t.N;
+  Cert c(t);
   CHK(c.S.alloc((size_t)t.N * p0->d * p0->d));
   CHK(c.part.alloc((size_t)kPartialCap * 36));
   double gn2 = 0.0;
@@ -1019,21 +764,12 @@ int dpgo_certify_escape_device(dpgo_problem_t h_next, int r, const double* X_dev
   double f0 = 0.0, gn0 = 0.0;
   CHK(lift(0.0));
   CHK(dpgo_problem_eval_device(p, Xl, &f0, &gn0));
-  // SE-Sync's rule: the first of alpha0, alpha0 / 2, ... whose retraction decreases f and leaves the gradient above the
-  // tolerance (the next solve must not stop at once); alpha0 moves each pose by ~0.1 for a witness spread over all poses
-  double a = 0.1 * std::sqrt((double)p->n);
-  for (int k = 0; k < 60; ++k, a *= 0.5) {
+  auto trial = [&](double a, double* f, double* gn) -> int {
     CHK(lift(a));
     CHK(launch_retract(p, Xl, Xl, 0.0, X_next_dev, nullptr));
-    double f = 0.0, gn = 0.0;
-    CHK(dpgo_problem_eval_device(p, X_next_dev, &f, &gn));
-    if (f < f0 && gn > grad_tol) {
-      if (alpha) *alpha = a;
-      return DPGO_OK;
-    }
-  }
-  if (alpha) *alpha = 0.0;
-  return fail(DPGO_ERR_STATE, "certify: no step along the witness decreases f");
+    return dpgo_problem_eval_device(p, X_next_dev, f, gn);
+  };
+  return halving_search(p->n, f0, grad_tol, trial, alpha, nullptr);
 }
 
 
@@ -1071,27 +807,23 @@ int dpgo_team_escape_device(const dpgo_team_member* members_next, int n_members,
   double gn0 = 0.0;
   CHK(ev.run(t, d, r, X_team_dev, nullptr, &out->f_before, &gn0));
   const int g = std::min(pose_tiles(t.N, d + 1), kMaxGrid);
-  // SE-Sync's rule, as dpgo_certify_escape_device applies it
-  double a = 0.1 * std::sqrt((double)t.N);
-  for (int k = 0; k < 60; ++k, a *= 0.5) {
+  double f = 0.0, gn = 0.0;  // of the last trial
+  auto trial = [&](double a, double* f_out, double* gn_out) -> int {
     CHK(dispatch_dr(d, r + 1, [&](auto D, auto R1) {  // (by the rank it writes: only compiled lifts are instantiated)
       if constexpr (R1 > D)
         return launch(k_cert_lift_retract<D, R1 - 1>, g, 0, p0->stream, X_team_dev, witness_team_dev, a, X_next_team_dev, t.N);
       return fail(DPGO_ERR_UNSUPPORTED, "certify: no lift to rank d");
     }));
     HIPC(hipGetLastError());
-    double f = 0.0, gn = 0.0;
     CHK(ev.run(t, d, r + 1, X_next_team_dev, nullptr, &f, &gn));
-    out->trials = k + 1;
-    if (f < out->f_before && gn > grad_tol) {
-      out->alpha = a;
-      out->f_after = f;
-      out->gradnorm_after = gn;
-      return DPGO_OK;
-    }
-  }
-  out->alpha = 0.0;
-  return fail(DPGO_ERR_STATE, "certify: no step along the witness decreases f");
+    *f_out = f;
+    *gn_out = gn;
+    return DPGO_OK;
+  };
+  CHK(halving_search(t.N, out->f_before, grad_tol, trial, &out->alpha, &out->trials));
+  out->f_after = f;
+  out->gradnorm_after = gn;
+  return DPGO_OK;
 }
 
 }  // extern "C"

@@ -16,12 +16,15 @@
 //   taskpool.h       the set-up code's worker threads (TaskPool), setup_threads, parallel_ranges, pattern_by_ranges
 //   aggregation.h / aggregation.cpp  the hierarchy's set-up over index vectors: aggregates (growth, merge, index runs),
 //                    block patterns of A P and of the next level, run / tile / chunk tables, the additive layout's search
+//   cert_dense.h / cert_dense.cpp    the certificate's host algebra on the r x r Gram blocks: small factorizations, block
+//                    assembly, the coefficient matrices and decisions of every step of the eigen-solver
 #pragma once
 #include "kernels.h"
 #include "handoff.h"
 #include "options.h"
 #include "taskpool.h"
 #include "aggregation.h"
+#include "cert_dense.h"
 
 #include <algorithm>
 #include <atomic>
